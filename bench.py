@@ -8,6 +8,8 @@ forward, backward, bucketed all-reduce, global grad-norm clip and fused AdamW up
 reference's dropout (0.1) active.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--model gpt2]
+    python bench.py --full [...]            # + every secondary measurement and self-check below
+    python bench.py --dump-outputs DIR      # + what the last timed step computed, as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 ``--gpus N > 1`` without a torchrun env starts the N ranks itself (a child
@@ -15,9 +17,21 @@ reference's dropout (0.1) active.
 reporting a smaller run under the requested GPU count.
 
 W untimed warmup steps, then K steps bracketed by barrier + device sync; the max over ranks is
-reported.  The same engine is then timed again at ``--also-batch`` sequences per GPU (default 64,
-the reference's per-GPU batch, ``/root/reference/mingpt/gpt2_config.yaml:14``), reported under
-``extra`` so that rounds stay comparable at a fixed config.
+reported.  A plain run stops there: set-up, warm-up, the K timed steps, the result line.
+
+``--full`` adds everything else, reported in the same JSON line: a second timed pass of the same
+engine at ``--also-batch`` sequences per GPU (default 64, the reference's per-GPU batch in its
+``gpt2_config.yaml``) under ``extra`` so that rounds stay comparable at a fixed config, and at
+N > 1 the replica checksum, the isolated per-bucket collective timing and the compute-only pass
+described below.  Without ``--full`` those fields are null and ``extra`` has no batch entry.
+
+``--dump-outputs DIR`` writes, right after the timed steps (before any ``--full`` pass touches the
+weights), what a caller of the timed path holds after its last step: ``loss.npy`` (the step's
+returned loss), ``grad_norm.npy`` (the global gradient norm the clip used) and ``params.npy`` (the
+updated fp32 master weights: per parameter, in ``named_parameters`` order, all elements or a fixed
+seeded sample of them; ``params_index.json`` names the slices), float32, rank 0 only.  Model init,
+token batches and dropout seeds are seeded, so two builds run with the same arguments see the same
+inputs and can be compared array for array.
 
 Diagnostics in the JSON line (``comm``): the RCCL version the ranks loaded, every rank's device
 name and PCI bus id, the bucket plan (count, bytes per bucket in the wire dtype), and
@@ -30,7 +44,7 @@ PyTorch-ROCm (the reference publishes no numbers).
 
 Gradient wire dtype: fp32 by default, the reference DDP's precision
 (``/root/reference/mingpt/trainer.py:71``); ``--reduce-dtype bf16`` is a labelled variant
-(``config.grad_reduce_dtype``).  At N > 1 a compute-only pass follows the checksum: the same
+(``config.grad_reduce_dtype``).  Under ``--full`` at N > 1 a compute-only pass follows the checksum: the same
 steps with every gradient collective skipped (``StepEngine.train_step_local``), reported as
 ``extra.no_comm`` (null at N = 1 and under ZeRO-1), so a 1 -> N loss splits into exposed
 communication vs compute slowed by the collective kernels sharing the CUs.
@@ -41,10 +55,10 @@ timed step (one phase each), checksum, collective timing, barrier.  A phase that
 (default 150) prints the rank, the phase, how long it has been stuck and the gradient buckets
 whose collective has not completed on the device, then exits the rank with status 4 (the
 launcher then stops the others).  The process group's own timeout (``--pg-timeout``, default
-180 s, RCCL async error handling on) is the backstop.  After the timed loop every rank's fp64
-checksum of its weights is all-gathered: ``comm.ranks_identical`` (null at N = 1).  Per-bucket
-collective time and bus bandwidth, measured in isolation after training, sit next to
-``comm_exposed_ms`` (``comm.bucket_collective_ms`` / ``bucket_busbw_gbs``; null at N = 1).
+180 s, RCCL async error handling on) is the backstop.  Under ``--full``, after the timed loop
+every rank's fp64 checksum of its weights is all-gathered: ``comm.ranks_identical`` (null at
+N = 1), and per-bucket collective time and bus bandwidth, measured in isolation after training, sit
+next to ``comm_exposed_ms`` (``comm.bucket_collective_ms`` / ``bucket_busbw_gbs``; null at N = 1).
 ``MINGPT_BENCH_STALL=rank:phase`` makes that rank hang at that phase (the fail-fast test).
 """
 import argparse
@@ -190,6 +204,44 @@ def _collective_timing(eng, N):
             "collective_total_ms": round(sum(ms), 3)}
 
 
+DUMP_PARAM_ELEMS = 8 << 20  # params.npy: at most 8 Mi float32 (32 MB of the 64 MB a dump may take)
+
+
+def _dump_outputs(out_dir, eng, loss):
+    """``--dump-outputs``: what a caller of the timed path holds after its last step, as float32
+    ``.npy`` files.  ``loss``: the step's return value.  ``grad_norm``: the global gradient norm the
+    step clipped with.  ``params``: the updated weights (fp32 masters; under ZeRO-1, where the
+    masters are sharded, the bf16 weights every rank holds in full), per parameter in
+    ``named_parameters`` order: the whole tensor when it fits an equal share of DUMP_PARAM_ELEMS,
+    else that many elements at sorted indices drawn from a fixed seed.  ``params_index.json``
+    lists (name, offset into params.npy, elements written, elements of the tensor)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    if eng.zero1 and eng.dp is not None:
+        eng.dp.wait_gathers()  # the last step's parameter all-gathers are still in flight
+    s = eng.store
+    masters = {} if eng.zero1 else {id(p): s.master[o:o + n] for p, o, n in zip(s.params, s.offsets, s.numels)}
+    named = list(eng.model.named_parameters())
+    share = max(1024, DUMP_PARAM_ELEMS // max(1, len(named)))
+    pick = torch.Generator().manual_seed(20240521)
+    parts, index, off = [], [], 0
+    for name, p in named:
+        flat = masters.get(id(p), p).detach().reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randperm(flat.numel(), generator=pick)[:share].sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+        index.append([name, off, flat.numel(), p.numel()])
+        off += flat.numel()
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    gnorm = eng.opt.norm_buf[1]  # StepEngine.grad_norm; ZeRO-1's optimizer keeps the same buffer
+    np.save(os.path.join(out_dir, "grad_norm.npy"), gnorm.detach().float().reshape(1).cpu().numpy())
+    with open(os.path.join(out_dir, "params_index.json"), "w") as f:
+        json.dump(index, f)
+
+
 def _comm_diag(eng, info, N, comm_ms, cuda=True):
     """Self-diagnosis of the data-parallel path (collective: every rank calls it)."""
     import torch.distributed as dist
@@ -243,15 +295,22 @@ def main():
                     help="gradient dtype on the wire for N > 1: fp32 (default, the reference DDP's "
                          "precision) or bf16 (half the xGMI bytes; reported as a labelled variant)")
     ap.add_argument("--no-comm-pass", type=int, default=1,
-                    help="N > 1: after the checksum, time the same steps with every gradient "
+                    help="--full, N > 1: after the checksum, time the same steps with every gradient "
                          "collective skipped (dp.no_sync): extra.no_comm (0: skip)")
     ap.add_argument("--zero1", action="store_true",
                     help="shard the AdamW state over the ranks (reduce-scatter + all-gather)")
     ap.add_argument("--profile", default="", help="write a torch.profiler trace to this dir")
     ap.add_argument("--graph", action="store_true",
                     help="replay each step as one hipGraph (single GPU; StepEngine.graph_step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and self-check: the --also-batch pass "
+                         "and, at N > 1, the replica checksum, the per-bucket collective timing and "
+                         "the --no-comm-pass (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, gradient "
+                         "norm, a fixed sample of the updated fp32 weights) as DIR/<name>.npy")
     ap.add_argument("--also-batch", type=int, default=64,
-                    help="second timed pass at this per-GPU batch (0: skip), reported under 'extra'")
+                    help="--full: second timed pass at this per-GPU batch (0: skip), reported under 'extra'")
     ap.add_argument("--comm-at-world1", action="store_true",
                     help="N = 1: drive the RCCL collective path on a one-rank group (plumbing check)")
     ap.add_argument("--comm", default=None, choices=["c10d", "rccl"],
@@ -352,8 +411,12 @@ def main():
     tokens = a.batch * a.seq * a.steps * N
     value = tokens / dt
     max_mem = torch.cuda.max_memory_allocated() / 2 ** 30 if cuda else None
+    if a.dump_outputs:  # before any --full pass steps the weights further
+        wd.phase("dump outputs")
+        if info.rank == 0:
+            _dump_outputs(a.dump_outputs, eng, loss)
     extra = {}
-    if a.also_batch and a.also_batch != a.batch:
+    if a.full and a.also_batch and a.also_batch != a.batch:
         dt2, _, comm2 = timed(a.also_batch, a.steps, min(a.warmup, 2), tag=f" batch{a.also_batch}")
         v2 = a.also_batch * a.seq * a.steps * N / dt2
         base2 = BASELINE_TOK_S_PER_GPU.get(a.also_batch)
@@ -365,14 +428,15 @@ def main():
     if eng.zero1 and eng.dp is not None:
         eng.dp.wait_gathers()  # the last step's parameter all-gathers are still in flight
     sync()
-    identical = _ranks_identical(eng, N)
+    n_checked = N if a.full else 1  # a plain run skips both: their fields are null, as at N = 1
+    identical = _ranks_identical(eng, n_checked)
     wd.phase("collective timing")
-    coll = _collective_timing(eng, N)
+    coll = _collective_timing(eng, n_checked)
     # compute-only pass: the same steps with no gradient collective, so the 1 -> N loss splits
     # into exposed communication (ms_per_step - no_comm) and compute slowed by sharing the node
     # (no_comm vs the N = 1 step).  Replicas diverge from here on: it runs after the checksum.
     extra["no_comm"] = None
-    if N > 1 and a.no_comm_pass and eng.dp is not None and not eng.zero1:
+    if a.full and N > 1 and a.no_comm_pass and eng.dp is not None and not eng.zero1:
         local = lambda x, y: eng.train_step_local([(x, y)])  # noqa: E731
         dt3, _, _ = timed(a.batch, a.steps, min(a.warmup, 2), tag=" no_comm", step_fn=local)
         extra["no_comm"] = {"value": round(a.batch * a.seq * a.steps * N / dt3, 1),
@@ -391,6 +455,7 @@ def main():
             "n_gpus": N,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": round(dt / a.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",

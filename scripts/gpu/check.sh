@@ -6,7 +6,7 @@
 set -o pipefail
 cd "$(dirname "$0")/../.."
 TAG=${1:-check}; shift || true
-TESTS=1; PROF=1; BARGS="--steps 10 --warmup 3"
+TESTS=1; PROF=1; BARGS="--full --steps 10 --warmup 3"
 while [ $# -gt 0 ]; do
   case "$1" in
     --no-tests) TESTS=0 ;;

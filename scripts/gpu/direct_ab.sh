@@ -24,7 +24,7 @@ for rep in 1 2; do
   for so in $SOS; do
     n=$( [ $so = tree ] && echo tree || basename $(dirname $so) )
     if [ $so = tree ]; then unset MINGPT_EXT_SO; else export MINGPT_EXT_SO=$so; fi
-    timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/bench_${n}_r${rep}.json" 2> "$OUT/bench_${n}_r${rep}.err" || { tail "$OUT/bench_${n}_r${rep}.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench_${n}_r${rep}.json" 2> "$OUT/bench_${n}_r${rep}.err" || { tail "$OUT/bench_${n}_r${rep}.err"; exit 1; }
     python -c "import json; j=json.load(open('$OUT/bench_${n}_r${rep}.json')); print('$n', j['value'], j['ms_per_step'], j['extra']['batch64']['value'])"
   done
 done

@@ -18,7 +18,7 @@ for v in A B; do
 done
 for v in A B; do
   E=$([ $v = A ] && echo "$2" || echo "$3")
-  env $E timeout -k 10 500 python bench.py --model gpt2-xl --batch 16 --also-batch 32 --steps 6 --warmup 2 > "$OUT/xl_$v.json" 2> "$OUT/xl_$v.err" || { tail -20 "$OUT/xl_$v.err"; exit 1; }
+  env $E timeout -k 10 500 python bench.py --model gpt2-xl --batch 16 --full --also-batch 32 --steps 6 --warmup 2 > "$OUT/xl_$v.json" 2> "$OUT/xl_$v.err" || { tail -20 "$OUT/xl_$v.err"; exit 1; }
   echo "xl $v"; tail -1 "$OUT/xl_$v.json" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('extra',{}).get('batch32'))"
   env $E timeout -k 10 300 python bench.py --also-batch 0 --steps 10 --warmup 3 > "$OUT/gpt2_$v.json" 2> "$OUT/gpt2_$v.err" || { tail -20 "$OUT/gpt2_$v.err"; exit 1; }
   echo "gpt2 $v"; tail -1 "$OUT/gpt2_$v.json" | cut -c1-160

@@ -15,7 +15,7 @@ for r in 1 2; do
 import json,sys
 for l in open(sys.argv[1]):
     d=json.loads(l); print(sys.argv[2], d['shape'], d['us_tflops'].get('auto'), d['us_tflops'].get('hipblaslt'))" "$OUT/shapes_p${p}_$r.jsonl" "p$p r$r"
-    MINGPT_GEMM_PERSIST=$p timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/bench_p${p}_$r.json" 2> "$OUT/bench_p${p}_$r.err" \
+    MINGPT_GEMM_PERSIST=$p timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench_p${p}_$r.json" 2> "$OUT/bench_p${p}_$r.err" \
       || { tail -20 "$OUT/bench_p${p}_$r.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('bench', sys.argv[2], d['value'], d['ms_per_step'], d['extra'].get('batch64', {}).get('value'))" \
       "$OUT/bench_p${p}_$r.json" "p$p r$r"

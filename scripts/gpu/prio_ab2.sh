@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 TAG=${1:-prio2}; OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 for r in 1 2; do
   for cfg in X=0 MINGPT_COMPUTE_PRIORITY=-1; do
-    env $cfg timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/gpt2_${cfg}_$r.json" 2> "$OUT/gpt2_${cfg}_$r.err" \
+    env $cfg timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/gpt2_${cfg}_$r.json" 2> "$OUT/gpt2_${cfg}_$r.err" \
       || { tail -20 "$OUT/gpt2_${cfg}_$r.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('gpt2', sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], d['extra'].get('batch64', {}).get('value'))" \
       "$OUT/gpt2_${cfg}_$r.json" "$cfg" "$r"

@@ -22,7 +22,7 @@ if [ $TESTS = 1 ]; then
   timeout -k 10 900 python -u -m pytest tests/ -m gpu -q -p no:cacheprovider -x --timeout 300 --timeout-method thread > "$OUT/tests.log" 2>&1
   s=$?; tail -3 "$OUT/tests.log"; [ $s -eq 0 ] || exit $s
 fi
-timeout -k 10 400 python bench.py --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 timeout -k 10 300 python bench.py --steps 5 --warmup 2 --also-batch 0 --comm-at-world1 > "$OUT/bench_comm1.json" 2> "$OUT/bench_comm1.err" || { tail -20 "$OUT/bench_comm1.err"; exit 1; }
 cat "$OUT/bench_comm1.json"

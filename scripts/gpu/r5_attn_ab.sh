@@ -9,7 +9,8 @@ s=$?; tail -3 "$OUT/tests.log"; [ $s -eq 0 ] || exit $s
 for rep in 1 2; do
   for t in tree base; do
     B=bench.py; [ $t = base ] && B=$BASE/bench.py
-    timeout -k 10 300 python $B --steps 10 --warmup 3 > "$OUT/bench_${t}_r${rep}.json" 2> "$OUT/bench_${t}_r${rep}.err" || { tail "$OUT/bench_${t}_r${rep}.err"; exit 1; }
+    F=; grep -q -e --full $B && F=--full  # a base tree from before --full reports extra.batch64 by itself
+    timeout -k 10 300 python $B $F --steps 10 --warmup 3 > "$OUT/bench_${t}_r${rep}.json" 2> "$OUT/bench_${t}_r${rep}.err" || { tail "$OUT/bench_${t}_r${rep}.err"; exit 1; }
     grep '^{' "$OUT/bench_${t}_r${rep}.json" | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$t', j['value'], j['ms_per_step'], j['extra']['batch64']['value'])"
   done
 done

@@ -13,7 +13,7 @@ fi
 for rep in 1 2; do
   for so in "$@"; do
     n=$(basename $(dirname $so))
-    MINGPT_EXT_SO=$so timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/bench_${n}_r$rep.json" 2> "$OUT/bench_${n}_r$rep.err" || { tail "$OUT/bench_${n}_r$rep.err"; exit 1; }
+    MINGPT_EXT_SO=$so timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench_${n}_r$rep.json" 2> "$OUT/bench_${n}_r$rep.err" || { tail "$OUT/bench_${n}_r$rep.err"; exit 1; }
     grep '^{' "$OUT/bench_${n}_r$rep.json" | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$n r$rep', j['value'], j['ms_per_step'], j['extra']['batch64']['value'])"
   done
 done

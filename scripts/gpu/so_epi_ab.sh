@@ -15,6 +15,6 @@ print('$n r$rep', ' '.join('%s:%s=%.1f' % (k.split('(')[0], n2, v[0]) for k, vv 
 done
 for so in "$@"; do
   n=$(basename $(dirname $so))
-  MINGPT_EXT_SO=$so timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail "$OUT/bench_$n.err"; exit 1; }
+  MINGPT_EXT_SO=$so timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail "$OUT/bench_$n.err"; exit 1; }
   grep '^{' "$OUT/bench_$n.json" | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$n', j['value'], j['ms_per_step'], j['extra']['batch64']['value'])"
 done

@@ -11,7 +11,7 @@ for r in 1 2; do
       > "$OUT/xl32_${cfg}_$r.json" 2> "$OUT/xl32_${cfg}_$r.err" || { tail -20 "$OUT/xl32_${cfg}_$r.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('xl32', sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'])" \
       "$OUT/xl32_${cfg}_$r.json" "$cfg" "$r"
-    env $cfg timeout -k 10 300 python bench.py --steps 10 --warmup 3 > "$OUT/gpt2_${cfg}_$r.json" 2> "$OUT/gpt2_${cfg}_$r.err" \
+    env $cfg timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > "$OUT/gpt2_${cfg}_$r.json" 2> "$OUT/gpt2_${cfg}_$r.err" \
       || { tail -20 "$OUT/gpt2_${cfg}_$r.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('gpt2', sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], d['extra'].get('batch64', {}).get('value'))" \
       "$OUT/gpt2_${cfg}_$r.json" "$cfg" "$r"

@@ -4,7 +4,7 @@
 set -o pipefail
 cd "$(dirname "$0")/../.."
 TAG=${1:-xl}; OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-timeout -k 10 500 python bench.py --model gpt2-xl --batch 16 --also-batch 32 --steps 6 --warmup 2 > "$OUT/xl.json" 2> "$OUT/xl.err" || { tail -20 "$OUT/xl.err"; exit 1; }
+timeout -k 10 500 python bench.py --model gpt2-xl --batch 16 --full --also-batch 32 --steps 6 --warmup 2 > "$OUT/xl.json" 2> "$OUT/xl.err" || { tail -20 "$OUT/xl.err"; exit 1; }
 tail -1 "$OUT/xl.json"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
   python3 bench.py --model gpt2-xl --batch 16 --also-batch 0 --steps 3 --warmup 1 > "$OUT/prof_bench.log" 2>&1 || { tail -20 "$OUT/prof_bench.log"; exit 1; }

@@ -14,7 +14,7 @@ done
 for r in $(seq 1 "$ROUNDS"); do
   for so in "$@"; do
     use "$so"
-    timeout -k 10 300 python bench.py --model gpt2-xl --batch 16 --also-batch 32 --steps 6 --warmup 2 \
+    timeout -k 10 300 python bench.py --model gpt2-xl --batch 16 --full --also-batch 32 --steps 6 --warmup 2 \
       > "$OUT/b.json" 2> "$OUT/b.err" || { tail -5 "$OUT/b.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], sys.argv[3], d['value'], d['extra']['batch32']['value'])" "$OUT/b.json" "$so" "$r"
   done

@@ -18,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--device", "cpu", "--model", "gpt-nano", "--seq", "64", "--batch", "4", "--vocab", "65",
          "--steps", "3", "--warmup", "2", "--also-batch", "0"]
+FULL = ["--full"]  # the replica checksum, collective timing and compute-only pass run only under it
 
 
 def _run(args, env_extra=None, timeout=240):
@@ -39,7 +40,7 @@ def _json_line(out: str) -> dict:
 
 @pytest.mark.parametrize("extra_args", [[], ["--zero1"], ["--reduce-dtype", "bf16"]])
 def test_two_ranks_report_identical_replicas_and_collective_times(extra_args):
-    r, _ = _run(["--gpus", "2", *SMALL, *extra_args])
+    r, _ = _run(["--gpus", "2", *SMALL, *FULL, *extra_args])
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
     c = j["comm"]
@@ -58,7 +59,7 @@ def test_two_ranks_report_identical_replicas_and_collective_times(extra_args):
 
 
 def test_one_rank_reports_null_multi_rank_fields():
-    r, _ = _run(["--gpus", "1", *SMALL])
+    r, _ = _run(["--gpus", "1", *SMALL, *FULL])
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
     assert j["extra"]["no_comm"] is None
