@@ -28,13 +28,34 @@ def main():
     ap.add_argument("--prompt", type=int, default=32)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--sample", action="store_true",
+                    help="time do_sample=True instead (this framework only, no reference run)")
+    ap.add_argument("--top-k", type=int, default=40)
+    ap.add_argument("--seed", type=int, default=None,
+                    help="with --sample: the on-device seeded sampler; omitted: torch's generator (host loop)")
     a = ap.parse_args()
-    from bench.baseline_torch import GPT as TorchGPT
     from mingpt_distributed_amd.models import GPT, GPTConfig
 
     torch.manual_seed(0)
     ours = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
+    if a.sample:
+        kw = dict(do_sample=True, top_k=a.top_k or None)
+        if a.seed is not None:
+            kw["seed"] = a.seed
+        for B in map(int, a.batches.split(",")):
+            idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
+            with torch.no_grad():
+                ours.generate(idx, 4, **kw)  # warm-up (kernels, caches, graph capture)
+                out, t = timed(lambda: ours.generate(idx, a.new, **kw))
+            assert out.shape == (B, a.prompt + a.new)
+            print(json.dumps({"metric": "sampled decode tokens/s", "model": "gpt2 (random init)", "batch": B,
+                              "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "seed": a.seed,
+                              "tok_s": round(B * a.new / t, 1), "ms_per_step": round(t / a.new * 1e3, 4)}),
+                  flush=True)
+        return
+    from bench.baseline_torch import GPT as TorchGPT
+
     ref = TorchGPT(p=0.0, attn="sdpa").cuda().eval()
     for B in map(int, a.batches.split(",")):
         idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")

@@ -592,6 +592,51 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// One sampled token per row of logits [B, ld] bf16 (columns >= V are padding, never read): exact
+// top-k + Gumbel-max (sample.hip, the rule in common.h).  params: int32 [8] on the device, {seed lo,
+// seed hi, draw, inv_t fp32 bits, top_k (0: off), 0, 0, 0}; the kernel advances params[2] and, when
+// given, pos_dev[0] by one.  tok (int64, B elements) is written when given, else allocated; seq
+// (int64 [B, L], needs pos_dev) gets seq[b, pos_dev[0] + 1].  Returns tok.
+at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& params,
+                         const c10::optional<at::Tensor>& pos_dev, const c10::optional<at::Tensor>& tok,
+                         const c10::optional<at::Tensor>& seq) {
+  CHECK_BF16(logits); CHECK_DEV(params);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "sample_logits: logits [B, ld], unit column stride");
+  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "sample_logits: 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_logits: rows must be 16-byte aligned (ld % 8 == 0)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
+              params.device() == logits.device(), "sample_logits: params int32 [8] on the logits' device");
+  int* pd = nullptr;
+  if (pos_dev.has_value()) {
+    TORCH_CHECK(pos_dev->scalar_type() == at::kInt && pos_dev->is_cuda() && pos_dev->numel() == 1 &&
+                pos_dev->device() == logits.device(), "sample_logits: pos_dev int32 [1] on the logits' device");
+    pd = pos_dev->data_ptr<int>();
+  }
+  DevGuard g(logits.device());
+  at::Tensor t;
+  if (tok.has_value()) {
+    CHECK_I64(*tok); CHECK_CONTIG(*tok);
+    TORCH_CHECK(tok->numel() == B && tok->device() == logits.device(), "sample_logits: tok int64 with B elements");
+    t = *tok;
+  } else {
+    t = at::empty({B}, logits.options().dtype(at::kLong));
+  }
+  int64_t* seqp = nullptr;
+  long seq_ld = 0;
+  if (seq.has_value()) {
+    CHECK_I64(*seq); CHECK_CONTIG(*seq);
+    TORCH_CHECK(pd && seq->dim() == 2 && seq->size(0) == B && seq->device() == logits.device(),
+                "sample_logits: seq int64 [B, L] with pos_dev");
+    seqp = seq->data_ptr<int64_t>();
+    seq_ld = seq->size(1);
+  }
+  mg::sample_logits(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()), pd,
+                    t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream());
+  return t;
+}
+
 // ------------------------------------------------------------------------------- native RCCL
 // csrc/comm/rccl_comm.cpp.  Every collective runs on the communicator's comm stream after the
 // tensor's device's CURRENT stream (the producers); comm_wait makes that stream wait again.
@@ -738,6 +783,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none());
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
+        py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none());
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });

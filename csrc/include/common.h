@@ -172,6 +172,34 @@ MG_DEVICE void rowdrop8(float (&v)[8], uint64_t seed, long m, int n, int N, uint
   rowdrop4(v + 4, key, m, n + 4, N, thr16, scale);
 }
 
+// ---------------------------------------------------------------- Gumbel-max sampling
+// One token per logits row, exactly distributed as softmax(l / T) over the kept set, from a
+// counter-based hash: the token depends on (seed, draw, row, logits) alone, not on a reduction
+// order, a workgroup size or graph / eager mode.  For batch row b, draw counter d (the column of
+// the produced token in the returned sequence), vocabulary index i < V and a 64-bit seed:
+//   r0 = fmix32(lo32(seed) ^ kSampleSalt)     r1 = fmix32(r0 + hi32(seed))
+//   r2 = fmix32(r1 + d)                       r3 = fmix32(r2 ^ b)
+//   h  = fmix32(r3 + i * 0x9E3779B1)          (all mod 2^32)
+//   u  = ((h >> 8) + 0.5) * 2^-24             (24 bits: never 0 or 1)
+//   g  = -ln(-ln(u))
+// Kept set: { i : l_i >= the min(top_k, V)-th largest logit of the row } on the bf16 logits, ties
+// at the threshold all kept (the reference's `logits[logits < v[:, [-1]]] = -inf`); every i when
+// top-k is off.  Score of a kept element: s_i = (l_i - m) * inv_t + g_i, m the row maximum,
+// inv_t = float32(1 / temperature).  The token is the kept index with the largest s_i, the lowest
+// index on an exact tie.  -inf logits never win; the row maximum must be finite.
+// fp32 evaluation: x = h >> 8 below 2^23 gives u = (x + 0.5) 2^-24 exactly; from 2^23 on u has 25
+// significant bits, so its complement y = ((2^24 - x) - 0.5) 2^-24 is formed instead (exact) and
+// -ln(u) = -log1p(-y).  Accurate logf / log1pf, not the fast intrinsics: g is good to ~1e-6, the
+// score of any contender within 25 of the top to ~1e-5.
+constexpr uint32_t kSampleSalt = 0x5a3b1e97u;
+
+MG_DEVICE float sample_gumbel(uint32_t r3, uint32_t i) {
+  const uint32_t x = fmix32(r3 + i * 0x9E3779B1u) >> 8;
+  const float t = x < (1u << 23) ? -logf(((float)x + 0.5f) * 0x1p-24f)
+                                 : -log1pf(-(((float)((1u << 24) - x) - 0.5f) * 0x1p-24f));
+  return -logf(t);
+}
+
 // ---------------------------------------------------------------- GELU (tanh approximation)
 constexpr float kGeluK0 = 0.7978845608028654f;  // sqrt(2/pi)
 constexpr float kGeluK1 = 0.044715f;

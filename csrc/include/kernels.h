@@ -78,6 +78,16 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
           const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw = nullptr,
           const bf16_t* lnb = nullptr, float eps = 1e-5f, const GemvArgmax* am = nullptr);
 
+// sample.hip -- one sampled token per row of bf16 logits [B, ld] (columns >= V never read; ld % 8
+// == 0, rows 16-byte aligned): exact top-k + Gumbel-max, the rule in common.h.  params (device,
+// 8 x u32): {seed lo, seed hi, draw counter, inv_t as fp32 bits, top_k (<= 0: off), 0, 0, 0} -- read
+// by the kernel, so a captured launch replays with new values.  Writes tok[b] (optional) and, with
+// seq, seq[b * seq_ld + *pos_dev + 1]; then a trailing one-thread kernel advances params[2] and
+// *pos_dev (when given) by one.
+constexpr int kSampleParamWords = 8;
+void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
+                   int64_t* seq, long seq_ld, hipStream_t stream);
+
 // elementwise.hip
 void bias_act_fwd(const bf16_t* x, const bf16_t* b, bf16_t* pre, bf16_t* y, long M, int N, int act,
                   hipStream_t stream);

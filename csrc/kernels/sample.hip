@@ -1,0 +1,262 @@
+// Sampled decode for gfx950: exact top-k + Gumbel-max sampling of one token per logits row.
+//
+// Replaces the reference's per-token host sequence (/root/reference/mingpt/model.py:341-352:
+// divide by the temperature, torch.topk, masked fill, softmax, torch.multinomial) with one kernel
+// that reads the bf16 logits the LM head wrote and leaves the token in device memory, so a decode
+// step needs nothing from the host.  The rule (common.h, 'Gumbel-max sampling') is counter-based:
+// the token depends on (seed, draw, row, logits) only -- not on the block size, the reduction
+// order, or whether the launch is replayed from a hipGraph.
+//
+// One workgroup of 1024 threads per row; the row (100 KB at V = 50257) is loaded once into
+// registers (for_regs; rows past 65536 columns are streamed by every pass instead):
+//   pass A  row maximum, and (top-k on) a 256-bin histogram of the high byte of the 16-bit key;
+//   pass B  (top-k on) histogram of the low byte among the keys in the bin that holds the k-th;
+//           -> the exact k-th largest key, ties included, no sort and no tolerance;
+//   pass C  score (l - max) * inv_t + gumbel of every kept element, argmax as one 64-bit key
+//           (ordered score << 32 | ~index: the lowest index wins an exact tie).
+// Histograms are kept 32 times over (one copy per lane mod 32, the copy picks the LDS bank):
+// logits of one row share a few exponents, and 64 lanes adding to one LDS word serialise.
+//
+// Everything that changes between generate() calls is read from a device parameter block (and the
+// position from pos_dev), so a captured launch replays with a new seed, temperature or k.  The
+// draw counter and the position advance in a one-thread kernel launched after the sampler: the
+// stream order is the "every row has read them" guarantee, with no cross-workgroup hand-off.
+#include "common.h"
+#include "kernels.h"
+
+using namespace mg;
+
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / 64;
+constexpr int kCopies = 32;
+
+// order-preserving 16-bit key of a bf16 bit pattern (-0 counts as +0, as in a float compare)
+MG_DEVICE uint32_t key16(uint32_t bits) {
+  if (bits == 0x8000u) bits = 0u;
+  return (bits & 0x8000u) ? (bits ^ 0xffffu) : (bits | 0x8000u);
+}
+
+MG_DEVICE uint32_t ordered_f32(float s) {
+  if (s == 0.f) s = 0.f;  // -0 -> +0
+  const uint32_t u = __float_as_uint(s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+MG_DEVICE unsigned long long shfl_xor_u64(unsigned long long v, int o) {
+  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <class F>
+MG_DEVICE void for_vec(const uint4& u, int i, F f) {
+  f(i + 0, u.x & 0xffffu); f(i + 1, u.x >> 16);
+  f(i + 2, u.y & 0xffffu); f(i + 3, u.y >> 16);
+  f(i + 4, u.z & 0xffffu); f(i + 5, u.z >> 16);
+  f(i + 6, u.w & 0xffffu); f(i + 7, u.w >> 16);
+}
+
+// f(i, bits) for every element i < V of the row, 8 per 16-byte load; the V % 8 tail one by one
+// (columns >= V are never loaded)
+template <class F>
+MG_DEVICE void for_row(const bf16_t* __restrict__ row, int V, F f) {
+  const int nv = V >> 3;
+  for (int v = threadIdx.x; v < nv; v += kThreads) for_vec(ld16(row + (long)v * 8), v * 8, f);
+  const int i = nv * 8 + (int)threadIdx.x;
+  if (threadIdx.x < 8 && i < V) f(i, (uint32_t)row[i]);
+}
+
+// A row of up to kRegVec * kThreads * 8 = 65536 columns is loaded ONCE, every load in flight
+// together (thread t holds vectors t, t + 1024, ...): the row was written by the LM head's
+// workgroups on every XCD, so a load pays the trip past this XCD's L2, and a pass that walks the
+// row with a loop pays it once per iteration (measured at V = 50257, top_k 40: 21.0 us per call
+// with three streaming passes, 18.8 us from registers; the rest is the one CU's VALU rate over
+// ~15 instructions per element and pass, PERF.md).  Unrolled over the registers, so only for
+// cheap per-element bodies.
+constexpr int kRegVec = 8;
+
+template <class F>
+MG_DEVICE void for_regs(const uint4 (&regs)[kRegVec], uint32_t tail, int V, F f) {
+  const int nv = V >> 3;
+#pragma unroll
+  for (int j = 0; j < kRegVec; ++j) {
+    const int v = (int)threadIdx.x + j * kThreads;
+    if (v < nv) for_vec(regs[j], v * 8, f);
+  }
+  const int i = nv * 8 + (int)threadIdx.x;
+  if (threadIdx.x < 8 && i < V) f(i, tail);
+}
+
+MG_DEVICE void hist_clear(uint32_t* hist) {
+  for (int i = threadIdx.x; i < 256 * kCopies; i += kThreads) hist[i] = 0u;
+}
+
+// The bin (counted from the top) in which the cumulative count reaches `want`, and how many of
+// that bin's elements are still wanted.  hist: 256 x kCopies counts; scan: kWaves + 2 words.
+// Needs 1 <= want <= sum of all counts.  Result broadcast to the block.
+MG_DEVICE void hist_select(const uint32_t* hist, uint32_t* scan, uint32_t want, uint32_t& bin, uint32_t& rest) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __syncthreads();  // the histogram is complete
+  uint32_t c = 0u;
+  if (t < 256) {  // thread t owns bin 255 - t; rotated start: the copies of one bin share no bank
+#pragma unroll 8
+    for (int j = 0; j < kCopies; ++j) c += hist[(255 - t) * kCopies + ((j + t) & (kCopies - 1))];
+  }
+  uint32_t inc = c;  // inclusive scan over descending bins
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (t < 256 && lane == 63) scan[w] = inc;
+  __syncthreads();
+  if (t < 256) {
+    uint32_t before = inc - c;
+    for (int i = 0; i < w; ++i) before += scan[i];
+    if (before < want && want <= before + c) {  // exactly one thread
+      scan[kWaves] = 255u - (uint32_t)t;
+      scan[kWaves + 1] = want - before;
+    }
+  }
+  __syncthreads();
+  bin = scan[kWaves];
+  rest = scan[kWaves + 1];
+  __syncthreads();  // scan and hist may be rewritten
+}
+
+// params: {seed_lo, seed_hi, draw, inv_t (fp32 bits), top_k (<= 0: off), 0, 0, 0}
+__global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                          const uint32_t* params, const int* pos_dev,
+                                                          int64_t* __restrict__ tok, int64_t* __restrict__ seq,
+                                                          long seq_ld) {
+  __shared__ uint32_t hist[256 * kCopies];
+  __shared__ uint32_t scan[kWaves + 2];
+  __shared__ float redf[kWaves];
+  __shared__ unsigned long long redk[kWaves];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const bf16_t* row = logits + (long)b * ld;
+  const uint32_t seed_lo = params[0], seed_hi = params[1], draw = params[2];
+  const float inv_t = __uint_as_float(params[3]);
+  const int top_k = (int)params[4];
+  const bool select = top_k > 0 && top_k < V;  // k >= V keeps every element
+
+  // the row, in registers when it fits (for_regs)
+  const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
+  const bool cached = nv <= kRegVec * kThreads;
+  uint4 regs[kRegVec];
+  uint32_t tail = 0u;
+  if (cached) {
+#pragma unroll
+    for (int j = 0; j < kRegVec; ++j) {
+      const int v = (int)threadIdx.x + j * kThreads;
+      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (threadIdx.x < 8 && ti < V) tail = row[ti];
+  }
+  auto sweep = [&](auto f) {
+    if (cached) for_regs(regs, tail, V, f);
+    else for_row(row, V, f);
+  };
+
+  // ---- pass A: row maximum (+ high-byte histogram)
+  uint32_t* my = hist + (lane & (kCopies - 1));
+  if (select) hist_clear(hist);
+  __syncthreads();
+  float m = -INFINITY;
+  if (select) {
+    sweep([&](int, uint32_t bits) {
+      m = fmaxf(m, bf2f(bits));
+      atomicAdd(my + (key16(bits) >> 8) * kCopies, 1u);
+    });
+  } else {
+    sweep([&](int, uint32_t bits) { m = fmaxf(m, bf2f(bits)); });
+  }
+  m = block_max<kWaves>(m, redf);
+
+  // ---- pass B: the exact k-th largest key
+  uint32_t thr = 0u;
+  if (select) {
+    uint32_t hi, rest, lo, unused;
+    hist_select(hist, scan, (uint32_t)top_k, hi, rest);
+    hist_clear(hist);
+    __syncthreads();
+    sweep([&](int, uint32_t bits) {
+      const uint32_t k = key16(bits);
+      if ((k >> 8) == hi) atomicAdd(my + (k & 0xffu) * kCopies, 1u);
+    });
+    hist_select(hist, scan, rest, lo, unused);
+    thr = (hi << 8) | lo;
+  }
+
+  // ---- pass C: Gumbel-max over the kept set
+  const uint32_t r0 = fmix32(seed_lo ^ kSampleSalt);
+  const uint32_t r1 = fmix32(r0 + seed_hi);
+  const uint32_t r2 = fmix32(r1 + draw);
+  const uint32_t r3 = fmix32(r2 ^ (uint32_t)b);
+  unsigned long long best = 0ull;
+  auto score = [&](int i, uint32_t bits) {
+    if (key16(bits) < thr || bits == 0xff80u) return;  // below the threshold, or -inf
+    const float s = (bf2f(bits) - m) * inv_t + sample_gumbel(r3, (uint32_t)i);
+    const unsigned long long k = ((unsigned long long)ordered_f32(s) << 32) | (0xffffffffu - (uint32_t)i);
+    best = k > best ? k : best;
+  };
+  if (select && cached) {
+    // top-k keeps a few elements per row: mark them in a sweep over the registers (bit 8 j + e =
+    // element e of register j), then score the marked ones one by one -- one copy of the ~100
+    // instructions of Gumbel noise in the code, not one per register element
+    unsigned long long kept = 0ull;
+#pragma unroll
+    for (int j = 0; j < kRegVec; ++j) {
+      if ((int)threadIdx.x + j * kThreads < nv)
+        for_vec(regs[j], j * 8, [&](int e, uint32_t bits) { kept |= key16(bits) >= thr ? 1ull << e : 0ull; });
+    }
+    while (kept) {
+      const int e = __builtin_ctzll(kept);
+      kept &= kept - 1ull;
+      const int i = (((int)threadIdx.x + (e >> 3) * kThreads) << 3) + (e & 7);
+      score(i, (uint32_t)row[i]);
+    }
+    if (threadIdx.x < 8 && ti < V) score(ti, tail);
+  } else {
+    for_row(row, V, score);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long k = shfl_xor_u64(best, o);
+    best = k > best ? k : best;
+  }
+  if (lane == 0) redk[w] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < kWaves; ++i) best = redk[i] > best ? redk[i] : best;
+    long t = (long)(0xffffffffu - (uint32_t)best);
+    if (t >= V) t = V - 1;  // no candidate (a row without a finite maximum): still a valid id
+    if (tok) tok[b] = t;
+    if (seq) {
+      const long p = (long)pos_dev[0] + 1;
+      if (p >= 0 && p < seq_ld) seq[(long)b * seq_ld + p] = t;
+    }
+  }
+}
+
+// after every row of sample_kernel has read them (stream order): next draw, next position
+__global__ __launch_bounds__(64) void sample_advance_kernel(uint32_t* params, int* pos_dev) {
+  if (threadIdx.x == 0) {
+    params[2] += 1u;
+    if (pos_dev) pos_dev[0] += 1;
+  }
+}
+
+}  // namespace
+
+namespace mg {
+
+void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
+                   int64_t* seq, long seq_ld, hipStream_t stream) {
+  sample_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, tok, seq, seq_ld);
+  sample_advance_kernel<<<1, 64, 0, stream>>>(params, pos_dev);
+}
+
+}  // namespace mg

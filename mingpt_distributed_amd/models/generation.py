@@ -11,9 +11,14 @@ GPU path: the prefill runs the gfx950 kernels and keeps each layer's qkv GEMM ou
 appends K/V inside the attention kernel.  CPU path: the same algorithm in plain PyTorch.  When the
 sequence outgrows ``block_size`` the window slides and the cache is rebuilt from the cropped
 context (exactly the reference's cropping semantics).
+
+Sampling: ``seed=None`` is the reference's recipe on torch's global generator (``_sample``).  With a
+seed the draw is counter-based Gumbel-max (``ops.reference.sample_gumbel``; on the GPU the sample
+kernel inside a device-side token loop, ``_GpuCache.sample``): reproducible per (seed, column, row).
 """
 from __future__ import annotations
 
+import struct
 from typing import Optional
 
 import torch
@@ -142,7 +147,7 @@ class _GpuCache:
         self.logits = self._run(idx, 0)
         return self.logits
 
-    def _run(self, idx, pos0, pos_dev=None, greedy=None):
+    def _run(self, idx, pos0, pos_dev=None, greedy=None, sample=None):
         """Prefill (pos0 == 0) or one decode step at position pos0 (or at ``pos_dev[0]``, an int32
         device scalar, when captured in a hipGraph).  ``greedy`` = (tok [B, 1] int64, pos_dev,
         seq [B, Tmax + 1] int64, part [B, G] int64 or None): the step needs nothing from the host.
@@ -150,7 +155,9 @@ class _GpuCache:
         key per (row, workgroup) in part and advances pos_dev, and the NEXT step's embedding
         kernel reduces the keys into its input token (also written to tok and seq[:, pos]) --
         no cross-workgroup hand-off inside a kernel.  Without it the argmax runs in torch and
-        writes tok and seq[:, pos + 1] itself."""
+        writes tok and seq[:, pos + 1] itself.  ``sample`` = (tok, pos_dev, seq, params): the
+        sample kernel (sample.hip) draws tok and seq[:, pos + 1] from this step's logits by the
+        device parameter block ``params`` and advances pos_dev and the draw counter."""
         C, G, bf = self.C, self.G, self.bf
         m = self.model
         tr, cfg = m.transformer, m.config
@@ -209,6 +216,9 @@ class _GpuCache:
             tok.view(B).copy_(nxt)
             seq.index_copy_(1, (pd.long() + 1), nxt.view(B, 1))
             pd.add_(1)
+        if sample is not None:
+            tok, pd, seq, params = sample
+            C.sample_logits(logits, V, params, pd, tok, seq)
         return logits[:, :V]
 
     def _fresh(self):
@@ -217,6 +227,7 @@ class _GpuCache:
             self.stamp = st
             self.__dict__.pop("_graph", None)
             self.__dict__.pop("_ggraph", None)
+            self.__dict__.pop("_sgraph", None)
 
     def step(self, tok, pos):
         """One decode step.  Decoding is launch-bound (B rows through ~5 kernels per layer), so
@@ -278,6 +289,52 @@ class _GpuCache:
         last = 0xFFFFFFFF - (k & 0xFFFFFFFF)
         return torch.cat([g["seq"][:, pos + 1:pos + n], last.view(B, 1)], dim=1)
 
+    def _sample_params(self, words):
+        """The device parameter block of the sample kernel (one per decode state: the captured
+        step bakes its pointer in), set to ``words`` (``_sample_words``)."""
+        p = self.__dict__.get("_sparams")
+        if p is None:
+            p = self._sparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
+        p.copy_(torch.tensor(words, dtype=torch.int32))
+        return p
+
+    def sample_prefill(self, words):
+        """The token [B] drawn from the prefill logits (the first token of a context window)."""
+        return self.C.sample_logits(self.logits, self.model.config.vocab_size, self._sample_params(words))
+
+    def sample(self, tok, pos, n, words):
+        """n sampled decode steps starting with token ``tok`` [B, 1] at position ``pos``: each step
+        is the plain LM head followed by the sample kernel, which writes the next token into the
+        buffer the next step's embedding reads and advances the device position and draw counter.
+        Seed, temperature and top-k live in the device parameter block (``words``), so the one
+        captured step serves every call; the n replays are queued back to back without a host
+        round trip.  Returns the n new tokens [B, n] (positions pos + 1 .. pos + n)."""
+        assert pos + n <= self.tmax
+        B = tok.shape[0]
+        self._fresh()
+        g = getattr(self, "_sgraph", None)
+        if g is None:
+            dev = tok.device
+            g = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
+                 "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev)}
+            self._sgraph = g  # workspaces are allocated outside the capture (eager warm-up step)
+            g["params"] = self._sample_params(words)
+            self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
+        if _GRAPH_DECODE and "graph" not in g:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
+            g["graph"] = graph
+        g["tok"].copy_(tok)
+        g["pos"].fill_(pos)
+        self._sample_params(words)
+        for _ in range(n):
+            if _GRAPH_DECODE:
+                g["graph"].replay()
+            else:
+                self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
+        return g["seq"][:, pos + 1:pos + 1 + n]
+
     @staticmethod
     def _greedy_seed(g, tok, pos):
         """Point the greedy loop's device state at token ``tok`` [B, 1] at position ``pos``."""
@@ -289,6 +346,14 @@ class _GpuCache:
 
 
 _I64_MIN = -(1 << 63)
+
+
+def _sample_words(seed, draw, temperature, top_k):
+    """The sample kernel's parameter block as 8 int32: seed low / high word, draw counter,
+    float32(1 / temperature) as bits, top_k (0: off)."""
+    s32 = lambda x: ((x & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+    inv_t = struct.unpack("<i", struct.pack("<f", 1.0 / temperature))[0]
+    return [s32(seed), s32(seed >> 32), s32(draw), inv_t, min(int(top_k or 0), 0x7FFFFFFF), 0, 0, 0]
 
 
 def _weight_stamp(model):
@@ -311,8 +376,22 @@ _GRAPH_DECODE = True  # set False to launch the decode step eagerly
 
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
-             top_k: Optional[int] = None, use_cache: bool = True):
+             top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None):
+    """``seed`` (with ``do_sample``): draw by the counter-based Gumbel-max rule (common.h,
+    ``ops.reference.sample_gumbel``) instead of torch's global generator -- the tokens depend on
+    (seed, column, batch row, logits) only, and on the GPU the whole token loop stays on the device
+    (``_GpuCache.sample``).  ``seed=None`` leaves every path as it was."""
     bs = model.block_size
+    seeded = do_sample and seed is not None
+    if seeded:
+        R.check_sample_args(temperature, top_k)
+        seed = int(seed) & ((1 << 64) - 1)
+
+    def pick(logits, col):
+        if seeded:
+            return R.sample_gumbel(logits, temperature, top_k, seed, col)
+        return _sample(logits, temperature, do_sample, top_k)
+
     # ZeRO-1: the KV-cache path launches the kernels directly (never model.forward), so neither
     # the fused ops' per-bucket waits nor the engine's forward pre-hook run: wait here for every
     # in-flight parameter all-gather (stream-ordered) before any decode kernel reads the weights
@@ -321,10 +400,12 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         for _ in range(max_new_tokens):
             idx_cond = idx if idx.size(1) <= bs else idx[:, -bs:]
             logits, _ = model(idx_cond)
-            idx = torch.cat((idx, _sample(logits[:, -1, :], temperature, do_sample, top_k)), dim=1)
+            idx = torch.cat((idx, pick(logits[:, -1, :], idx.size(1))), dim=1)
         return idx
     if idx.is_cuda and not do_sample and max_new_tokens > 0:
         return _generate_greedy_gpu(model, idx, max_new_tokens)
+    if idx.is_cuda and seeded and max_new_tokens > 0:
+        return _generate_sample_gpu(model, idx, max_new_tokens, temperature, top_k, seed)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
@@ -333,7 +414,7 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             cache = _gpu_cache(model, idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond)
             cache.pos = idx_cond.size(1)
             logits = cache.logits
-        idx_next = _sample(logits, temperature, do_sample, top_k)
+        idx_next = pick(logits, T)
         idx = torch.cat((idx, idx_next), dim=1)
         if idx.size(1) > bs:
             cache = None  # window slides: rebuild from the cropped context next step
@@ -362,5 +443,28 @@ def _generate_greedy_gpu(model, idx, max_new_tokens):
         n = min(end - T, bs - L)
         if n > 0:
             out[:, T:T + n] = cache.greedy(out[:, T - 1:T], L, n)
+            T += n
+    return out
+
+
+def _generate_sample_gpu(model, idx, max_new_tokens, temperature, top_k, seed):
+    """Seeded sampling on the GPU, the host glue of ``_generate_greedy_gpu``: one prefill per context
+    window whose logits give the window's first token (the sample kernel), then the device-side
+    token loop (``_GpuCache.sample``) for every position the window still has room for.  The draw
+    counter of a token is its column in the returned sequence."""
+    bs = model.block_size
+    B, T0 = idx.shape
+    out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
+    out[:, :T0] = idx
+    T, end = T0, T0 + max_new_tokens
+    while T < end:
+        ctx = out[:, max(0, T - bs):T]
+        L = ctx.size(1)
+        cache = _gpu_cache(model, ctx, bs)
+        out[:, T] = cache.sample_prefill(_sample_words(seed, T, temperature, top_k))
+        T += 1
+        n = min(end - T, bs - L)
+        if n > 0:
+            out[:, T:T + n] = cache.sample(out[:, T - 1:T], L, n, _sample_words(seed, T, temperature, top_k))
             T += n
     return out

@@ -218,13 +218,15 @@ class GPT(nn.Module):
     # -------------------------------------------------------------------------------- generation
     @torch.no_grad()
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
-                 top_k: Optional[int] = None, use_cache: bool = True):
+                 top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
-        prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2))."""
+        prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
+        ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
+        (``generation.generate``); None draws from torch's global generator as before."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
-                        top_k=top_k, use_cache=use_cache)
+                        top_k=top_k, use_cache=use_cache, seed=seed)
 
     # -------------------------------------------------------------------------------- optimizer
     def configure_optimizers(self, train_config):

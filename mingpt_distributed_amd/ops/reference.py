@@ -66,6 +66,58 @@ def mlp(x, w_fc, b_fc, w_proj, b_proj, resid_p: float, training: bool):
     return F.dropout(linear(gelu_tanh(linear(x, w_fc, b_fc)), w_proj, b_proj), resid_p, training)
 
 
+SAMPLE_SALT = 0x5A3B1E97  # csrc/include/common.h kSampleSalt
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h: torch.Tensor) -> torch.Tensor:
+    """murmur3 finaliser on uint32 values held in int64 (a wrapped int64 product keeps its low 32 bits)."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def check_sample_args(temperature: float, top_k) -> None:
+    if not temperature > 0:
+        raise ValueError(f"sampling needs temperature > 0, got {temperature}")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"sampling needs top_k >= 1 (or None), got {top_k}")
+
+
+def sample_inv_t(temperature: float) -> float:
+    """float32(1 / temperature), the factor both the kernel and this file multiply by."""
+    return float(torch.tensor(1.0 / temperature, dtype=torch.float32).item())
+
+
+def sample_gumbel(logits: torch.Tensor, temperature: float, top_k, seed: int, draw: int, row0: int = 0):
+    """One token per row of ``logits`` [B, V] by the Gumbel-max rule of ``csrc/include/common.h``
+    ('Gumbel-max sampling'; the kernel is ``csrc/kernels/sample.hip``), in integer ops and fp64 on
+    the logits' device.  ``draw`` is the column of the produced token in the returned sequence,
+    row b of ``logits`` is batch row ``row0 + b``.  Returns [B, 1] int64."""
+    check_sample_args(temperature, top_k)
+    B, V = logits.shape
+    dev = logits.device
+    seed &= (1 << 64) - 1
+    s = torch.tensor([(seed & _M32) ^ SAMPLE_SALT], dtype=torch.int64, device=dev)
+    r1 = _fmix32((_fmix32(s) + (seed >> 32)) & _M32)
+    r2 = _fmix32((r1 + (draw & _M32)) & _M32)
+    rows = (torch.arange(B, dtype=torch.int64, device=dev) + row0) & _M32
+    r3 = _fmix32(r2 ^ rows).view(B, 1)
+    i = torch.arange(V, dtype=torch.int64, device=dev).view(1, V)
+    h = _fmix32((r3 + ((i * 0x9E3779B1) & _M32)) & _M32)
+    u = ((h >> 8).double() + 0.5) * 2.0 ** -24
+    g = -torch.log(-torch.log(u))
+    l = logits.double()
+    score = (l - l.max(dim=-1, keepdim=True).values) * sample_inv_t(temperature) + g
+    if top_k is not None:
+        kth = torch.topk(l, min(int(top_k), V), dim=-1).values[:, -1:]
+        score = score.masked_fill(l < kth, float("-inf"))
+    score = score.masked_fill(l == float("-inf"), float("-inf"))
+    return score.argmax(dim=-1, keepdim=True)
+
+
 def cross_entropy(logits, targets, ignore_index: int = -1):
     return F.cross_entropy(logits.reshape(-1, logits.size(-1)).float(), targets.reshape(-1),
                            ignore_index=ignore_index)

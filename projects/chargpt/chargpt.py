@@ -76,7 +76,8 @@ def main(argv):
                 context = "O God, O God!"
                 context = "".join(c for c in context if c in train_dataset.stoi) or text[:8]
                 x = train_dataset.encode(context)[None].to(trainer.engine.device)
-                y = model.generate(x, 500, temperature=1.0, do_sample=True, top_k=10)[0]
+                y = model.generate(x, 500, temperature=1.0, do_sample=True, top_k=10,
+                                   seed=config.system.seed + trainer.iter_num)[0]
                 print(train_dataset.decode(y))
             torch.save(model.state_dict(), os.path.join(config.system.work_dir, "model.pt"))
             model.train()

@@ -35,7 +35,8 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--device", default="auto")
-    ap.add_argument("--seed", type=int, default=3407)
+    ap.add_argument("--seed", type=int, default=3407,
+                    help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
     a = ap.parse_args(argv)
     dev = a.device if a.device != "auto" else ("cuda" if torch.cuda.is_available() else "cpu")
     set_seed(a.seed)
@@ -59,7 +60,7 @@ def main(argv=None):
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
     x = x.expand(a.num_samples, -1).contiguous()
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
-                       top_k=a.top_k)
+                       top_k=a.top_k, seed=a.seed)
     outs = []
     for i in range(a.num_samples):
         out = tok.decode(y[i].cpu().squeeze()) if tok is not None else y[i].tolist()
