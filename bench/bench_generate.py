@@ -23,6 +23,54 @@ def timed(fn):
     return out, time.perf_counter() - t0
 
 
+def ragged(model, a):
+    """Greedy tokens/s of ``generate_batch`` per batch size B: (a) B prompts of --prompt tokens each,
+    next to the rectangular ``generate`` on the same prompts; (b) B prompts spread evenly over
+    --min-len .. --max-len tokens; (c) the prompts of (b) as B sequential B = 1 ``generate`` calls.
+    Every case is warmed up, then the cases are timed --reps times in turn; the median is reported
+    with the spread.  Tokens counted: B * --new generated tokens per case."""
+    import statistics
+
+    for B in map(int, a.batches.split(",")):
+        g = torch.Generator().manual_seed(B)
+        equal = torch.randint(0, 50257, (B, a.prompt), generator=g).cuda()
+        lens = [round(a.min_len + (a.max_len - a.min_len) * i / max(B - 1, 1)) for i in range(B)]
+        mixed = [torch.randint(0, 50257, (n,), generator=g).cuda() for n in lens]
+        # separate models for the B-row and the one-row states: a model keeps one decode state, and
+        # alternating batch sizes on it would re-allocate and re-capture inside the timed window
+        solo = type(model)(model.config, verbose=False).cuda().to(torch.bfloat16).eval()
+        solo.load_state_dict(model.state_dict())
+        cases = {
+            "a_equal_generate_batch": lambda: model.generate_batch(list(equal), a.new)[0],
+            "a_equal_generate_rectangular": lambda: model.generate(equal, a.new),
+            "b_mixed_generate_batch": lambda: model.generate_batch(mixed, a.new)[0],
+            "c_mixed_sequential_b1": lambda: [solo.generate(p[None], a.new) for p in mixed],
+        }
+        with torch.no_grad():
+            for fn in cases.values():  # warm-up at the timed shapes (kernels, states, graph capture)
+                fn()
+            assert torch.equal(cases["a_equal_generate_batch"](), cases["a_equal_generate_rectangular"]())
+            got = cases["b_mixed_generate_batch"]()
+            for b, row in enumerate(cases["c_mixed_sequential_b1"]()):
+                same = torch.equal(row[0], got[b, :lens[b] + a.new])
+                if not same:  # B-row and one-row GEMMs may round differently: report, do not hide
+                    print(json.dumps({"note": "mixed row differs from its B = 1 run", "row": b}), flush=True)
+            times = {k: [] for k in cases}
+            for _ in range(a.reps):
+                for k, fn in cases.items():
+                    times[k].append(timed(fn)[1])
+        res = {"metric": "ragged greedy decode tokens/s", "model": "gpt2 (random init)", "batch": B,
+               "equal_prompt": a.prompt, "mixed_lengths": lens, "new_tokens": a.new, "reps": a.reps}
+        for k, ts in times.items():
+            res[k + "_tok_s"] = round(B * a.new / statistics.median(ts), 1)
+            res[k + "_tok_s_range"] = [round(B * a.new / max(ts), 1), round(B * a.new / min(ts), 1)]
+        res["b_over_c"] = round(statistics.median(times["c_mixed_sequential_b1"]) /
+                                statistics.median(times["b_mixed_generate_batch"]), 2)
+        res["a_batch_over_rectangular"] = round(statistics.median(times["a_equal_generate_rectangular"]) /
+                                                statistics.median(times["a_equal_generate_batch"]), 3)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prompt", type=int, default=32)
@@ -33,12 +81,20 @@ def main():
     ap.add_argument("--top-k", type=int, default=40)
     ap.add_argument("--seed", type=int, default=None,
                     help="with --sample: the on-device seeded sampler; omitted: torch's generator (host loop)")
+    ap.add_argument("--ragged", action="store_true",
+                    help="time generate_batch (this framework only): equal lengths, mixed lengths, and the "
+                         "mixed prompts as sequential B = 1 generate calls")
+    ap.add_argument("--min-len", type=int, default=16, help="--ragged: shortest mixed prompt")
+    ap.add_argument("--max-len", type=int, default=256, help="--ragged: longest mixed prompt")
+    ap.add_argument("--reps", type=int, default=5, help="--ragged: timed repetitions per case (alternating)")
     a = ap.parse_args()
     from mingpt_distributed_amd.models import GPT, GPTConfig
 
     torch.manual_seed(0)
     ours = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
+    if a.ragged:
+        return ragged(ours, a)
     if a.sample:
         kw = dict(do_sample=True, top_k=a.top_k or None)
         if a.seed is not None:

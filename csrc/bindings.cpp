@@ -93,12 +93,14 @@ at::Tensor layernorm_bwd_plain(const at::Tensor& dy, const at::Tensor& x, const 
 
 // ------------------------------------------------------------------------------- embedding
 // pos_dev (int32 [1], optional; decode with T == 1): the position row of wpe is read on the device.
+// pos_stride 1 (ragged batches): pos_dev is int32 [B] and row b takes wpe row pos_dev[b].
 // am_part (int64 [B, G], optional, with pos_dev): greedy decode -- the token of row b is the argmax
 // of the previous step's LM-head keys am_part[b] (gemv with am_part), written to tok[b] (idx may
 // be that same buffer) and to seq[b, pos] when given.
 at::Tensor embedding_fwd(const at::Tensor& idx, const at::Tensor& wte, const at::Tensor& wpe,
                          double p, int64_t seed, const c10::optional<at::Tensor>& pos_dev,
-                         const c10::optional<at::Tensor>& am_part, const c10::optional<at::Tensor>& seq) {
+                         const c10::optional<at::Tensor>& am_part, const c10::optional<at::Tensor>& seq,
+                         int64_t pos_stride) {
   CHECK_I64(idx); CHECK_BF16(wte); CHECK_BF16(wpe); CHECK_CONTIG(idx);
   CHECK_CONTIG(wte); CHECK_CONTIG(wpe);
   TORCH_CHECK(idx.dim() == 2, "idx must be [B, T]");
@@ -108,7 +110,13 @@ at::Tensor embedding_fwd(const at::Tensor& idx, const at::Tensor& wte, const at:
   if (pos_dev.has_value()) {
     TORCH_CHECK(T == 1 && pos_dev->scalar_type() == at::kInt && pos_dev->is_cuda(),
                 "embedding_fwd: pos_dev (int32 cuda) is for one-token decode steps");
+    TORCH_CHECK((pos_stride == 0 || pos_stride == 1) && pos_dev->is_contiguous() &&
+                pos_dev->numel() >= (pos_stride ? B : 1) && pos_dev->device() == idx.device(),
+                "embedding_fwd: pos_dev int32 [1] (pos_stride 0) or [B] (pos_stride 1)");
+    TORCH_CHECK(pos_stride == 0 || !am_part.has_value(), "embedding_fwd: am_part needs pos_stride 0");
     pd = pos_dev->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos_stride == 0, "embedding_fwd: pos_stride needs pos_dev");
   }
   const unsigned long long* ap = nullptr;
   int groups = 0;
@@ -130,7 +138,7 @@ at::Tensor embedding_fwd(const at::Tensor& idx, const at::Tensor& wte, const at:
   auto out = at::empty({B, T, D}, wte.options());
   mg::embedding_fwd(idx.data_ptr<int64_t>(), bp(wte), bp(wpe), bp(out), (int)(B * T), (int)T,
                     (int)D, (int)wte.size(0), (float)p, (uint64_t)seed, cur_stream(), pd, ap, groups,
-                    ap ? idx.data_ptr<int64_t>() : nullptr, seqp, seq_ld);
+                    ap ? idx.data_ptr<int64_t>() : nullptr, seqp, seq_ld, (int)pos_stride, (int)wpe.size(0));
   return out;
 }
 
@@ -553,13 +561,14 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
   return y;
 }
 
-// pos_dev (int32 [1] on the device, optional): the position is read by the kernel (hipGraph decode)
+// pos_dev (int32 [1] on the device, optional): the position is read by the kernel (hipGraph decode);
+// with pos_stride 1 it is int32 [B], one position per row (ragged batches)
 // part / counters (optional): the decode state's own workspace (kernels.h); without them a
 // temporary pair is allocated for this call (tests; not for captured graphs)
 at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, int64_t H,
                             int64_t pos, const c10::optional<at::Tensor>& pos_dev,
                             const c10::optional<at::Tensor>& part,
-                            const c10::optional<at::Tensor>& counters) {
+                            const c10::optional<at::Tensor>& counters, int64_t pos_stride) {
   CHECK_BF16(qkv_new); CHECK_BF16(cache); CHECK_CONTIG(qkv_new); CHECK_CONTIG(cache);
   TORCH_CHECK(cache.dim() == 3, "cache must be [B, Tmax, 3D]");
   const int64_t B = cache.size(0), Tmax = cache.size(1), D3 = cache.size(2), D = D3 / 3;
@@ -571,7 +580,12 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   const int* pd = nullptr;
   if (pos_dev.has_value()) {
     TORCH_CHECK(pos_dev->scalar_type() == at::kInt && pos_dev->is_cuda(), "pos_dev must be int32 cuda");
+    TORCH_CHECK((pos_stride == 0 || pos_stride == 1) && pos_dev->is_contiguous() &&
+                pos_dev->numel() >= (pos_stride ? B : 1) && pos_dev->device() == cache.device(),
+                "attention_decode: pos_dev int32 [1] (pos_stride 0) or [B] (pos_stride 1)");
     pd = pos_dev->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos_stride == 0, "attention_decode: pos_stride needs pos_dev");
   }
   const int64_t np = (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)(D / H));
   at::Tensor pt, ct;
@@ -588,7 +602,8 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
     ct = at::zeros({B * H}, cache.options().dtype(at::kInt));
   }
   mg::attention_decode(bp(qkv_new), bp(cache), bp(out), (int)B, (int)H, (int)(D / H), Tmax, (int)pos,
-                       cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd);
+                       cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd,
+                       (int)pos_stride);
   return out;
 }
 
@@ -635,6 +650,33 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
   mg::sample_logits(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()), pd,
                     t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream());
   return t;
+}
+
+// Ragged batches: the end of a decode step for every row that is not finished (kernels.h,
+// pick_ragged).  logits [B, ld] bf16 as for sample_logits; params int32 [8] (word 5: the stop token,
+// negative for none); pos, done int32 [B]; tok int64 with B elements; seq int64 [B, L].  All
+// updated in place.
+void pick_ragged(const at::Tensor& logits, int64_t V, const at::Tensor& params, const at::Tensor& pos,
+                 const at::Tensor& done, const at::Tensor& tok, const at::Tensor& seq, bool greedy) {
+  CHECK_BF16(logits); CHECK_DEV(params);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "pick_ragged: logits [B, ld], unit column stride");
+  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "pick_ragged: 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "pick_ragged: rows must be 16-byte aligned (ld % 8 == 0)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
+              params.device() == logits.device(), "pick_ragged: params int32 [8] on the logits' device");
+  for (const at::Tensor* t : {&pos, &done})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() == B &&
+                t->device() == logits.device(), "pick_ragged: pos and done int32 [B] on the logits' device");
+  CHECK_I64(tok); CHECK_CONTIG(tok); CHECK_I64(seq); CHECK_CONTIG(seq);
+  TORCH_CHECK(tok.numel() == B && tok.device() == logits.device(), "pick_ragged: tok int64 with B elements");
+  TORCH_CHECK(seq.dim() == 2 && seq.size(0) == B && seq.size(1) >= 2 && seq.device() == logits.device(),
+              "pick_ragged: seq int64 [B, L]");
+  DevGuard g(logits.device());
+  mg::pick_ragged(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()),
+                  pos.data_ptr<int>(), done.data_ptr<int>(), tok.data_ptr<int64_t>(), seq.data_ptr<int64_t>(),
+                  seq.size(1), greedy, cur_stream());
 }
 
 // ------------------------------------------------------------------------------- native RCCL
@@ -721,7 +763,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("drop_p"), py::arg("drop_seed"));
   m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("p"),
         py::arg("seed"), py::arg("pos_dev") = py::none(), py::arg("am_part") = py::none(),
-        py::arg("seq") = py::none());
+        py::arg("seq") = py::none(), py::arg("pos_stride") = 0);
   // debug builds: OR of the device error words (1/2 = token id out of range in embedding fwd/bwd,
   // 4 = cross-entropy target >= V), cleared on read; always 0 in release builds
   m.def("debug_error_bits", []() -> int64_t { return (int64_t)mg::debug_error_bits(); });
@@ -782,9 +824,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_supported", &mg::gemv_supported);
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
-        py::arg("counters") = py::none());
+        py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
         py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none());
+  m.def("pick_ragged", &pick_ragged, py::arg("logits"), py::arg("V"), py::arg("params"), py::arg("pos"),
+        py::arg("done"), py::arg("tok"), py::arg("seq"), py::arg("greedy"));
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });

@@ -28,7 +28,9 @@ void embedding_fwd(const int64_t* idx, const bf16_t* wte, const bf16_t* wpe, bf1
                    int am_groups = 0,             //   = argmax over the LM-head GEMV's keys
                    int64_t* tok = nullptr,        //   am_part[m][0 .. am_groups), written to tok[m]
                    int64_t* seq = nullptr,        //   and seq[m * seq_ld + *pos_dev]
-                   long seq_ld = 0);
+                   long seq_ld = 0,
+                   int pos_stride = 0,  // 1 (ragged batches): row m takes wpe row pos_dev[m], clamped
+                   int pos_rows = 0);   //   to [0, pos_rows); 0: every row takes *pos_dev, as before
 unsigned int debug_error_bits();  // MG_DEBUG builds: device range-check bits, cleared on read
 void embedding_bwd(const int64_t* idx, const bf16_t* dout, float* dwte, float* dwpe, int M, int T,
                    int D, int V, float p, uint64_t seed, hipStream_t stream);
@@ -87,6 +89,15 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
 constexpr int kSampleParamWords = 8;
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
                    int64_t* seq, long seq_ld, hipStream_t stream);
+// Ragged batches: per-row device state pos [B], done [B] (int32), tok [B], seq [B, seq_ld].  One
+// kernel, one workgroup per row: a row with done[b] set is left alone; otherwise the token t -- the
+// argmax of the row's V logits, first index on ties (greedy), or the Gumbel-max draw with counter
+// pos[b] + 1 and batch row b -- is written to tok[b] and seq[b, pos[b] + 1], pos[b] advances by one
+// and done[b] is set when t == (int)params[5] (the stop token; negative: none).  params[2] is not
+// used and nothing is advanced after the launch.  A row whose pos[b] + 1 would reach seq_ld - 1 is
+// left alone too.
+void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos, int* done, int64_t* tok,
+                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream);
 
 // elementwise.hip
 void bias_act_fwd(const bf16_t* x, const bf16_t* b, bf16_t* pre, bf16_t* y, long M, int N, int act,
@@ -140,10 +151,12 @@ void attention_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, con
 // one decode step: appends K/V of qkv_new [B, 3D] at row pos of cache [B, Tmax, 3D]; out [B, D].
 // part (attention_decode_part_floats(B, H, hd) floats) and counters (B * H, zero; the kernel leaves
 // them zero) are the caller's workspace: one per decode state, so a captured hipGraph never sees
-// another state's (possibly freed) buffers.
+// another state's (possibly freed) buffers.  pos_dev: the position in device memory (clamped to
+// [0, Tmax)), one for the batch (pos_stride 0) or one per row (pos_stride 1, ragged batches: row b
+// appends at cache row pos_dev[b] and attends to keys 0..pos_dev[b], with its own split count).
 size_t attention_decode_part_floats(int B, int H, int hd);
 void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, int H, int hd,
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                      const int* pos_dev = nullptr);
+                      const int* pos_dev = nullptr, int pos_stride = 0);
 
 }  // namespace mg

@@ -34,8 +34,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
                                                           float scale_log2, int S, int CH,  // CH: set below
                                                           int KPS,
                                                           float* __restrict__ part,
-                                                          unsigned* __restrict__ counters) {
-  if (pos_dev) pos = min(max(*pos_dev, 0), (int)Tmax - 1);  // hipGraph decode: position in device memory
+                                                          unsigned* __restrict__ counters,
+                                                          int pos_stride) {
   __shared__ float qs[128];
   __shared__ float sc[256];
   __shared__ float red[16];
@@ -43,6 +43,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   __shared__ int last_flag;
   const int bh = blockIdx.x / S, sp = blockIdx.x % S;
   const int b = bh / H, hh = bh % H;
+  // hipGraph decode: position in device memory -- one for the batch (pos_stride 0) or one per row
+  // (pos_stride 1, ragged batches: everything below -- the appended cache row, the key range, Se,
+  // CH and the early return -- is per row, and the last-arrival counter is per (b, h) already).
+  // A right-padded prefill leaves garbage K/V in cache rows at or past a row's length; no step
+  // reads it: row pos is taken from qkv_new, and written here before any later step reads it.
+  if (pos_dev) pos = min(max(pos_dev[(long)b * pos_stride], 0), (int)Tmax - 1);
   const long ld = 3L * D;
   const bf16_t* qrow = qkv_new + (long)b * ld + hh * hd;
   bf16_t* cb = cache + (long)b * Tmax * ld;
@@ -189,7 +195,7 @@ size_t attention_decode_part_floats(int B, int H, int hd) {
 // memory once another batch size had re-allocated it.
 void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, int H, int hd,
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                      const int* pos_dev) {
+                      const int* pos_dev, int pos_stride) {
   // fixed grid (graph replays move pos only); the kernel uses ceil(L / 128) of the S splits, so
   // each holds <= 256 keys for Tmax <= 4096 (checked by the binding)
   const int S = kDecSplitsMax;
@@ -201,7 +207,7 @@ void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, 
   const int kps = B * H <= 32 ? 256 : 128;
   attn_decode_kernel<<<B * H * S, 256, 0, stream>>>(qkv_new, cache, out, H, hd, H * hd, Tmax, pos, pos_dev,
                                                     1.4426950408889634f / sqrtf((float)hd), S, CH, kps,
-                                                    part, counters);
+                                                    part, counters, pos_stride);
 }
 
 }  // namespace mg

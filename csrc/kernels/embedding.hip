@@ -4,6 +4,8 @@
 // embedding gather, broadcast add of the positional table and dropout become one pass.
 //
 // fwd: out[m, :] = dropout(wte[idx[m], :] + wpe[m % T, :]); one wave per token row, 16-B loads.
+//      Decode steps (T == 1) read the position from device memory: one for the batch
+//      (pos_stride 0) or one per row (pos_stride 1, ragged batches).
 // bwd: dwte[idx[m], :] += g[m, :]  -- fp32 atomics into the main-grad buffer, each wave
 //      instruction adding 64 contiguous floats (256 contiguous bytes: the full-rate atomic shape);
 //      dwpe[t, :] += sum_b g[b*T + t, :]  -- a deterministic column reduction, no atomics.
@@ -22,7 +24,8 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict_
                                                       unsigned int* __restrict__ err,
                                                       uint64_t seed, uint32_t thr, float scale,
                                                       int use_dropout, const uint64_t* sofs,
-                                                      const int* __restrict__ pos_dev,
+                                                      const int* __restrict__ pos_dev, int pos_stride,
+                                                      int pos_rows,
                                                       const unsigned long long* __restrict__ am_part,
                                                       int am_groups, int64_t* __restrict__ tok_out,
                                                       int64_t* __restrict__ seq, long seq_ld) {
@@ -54,7 +57,9 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict_
     tok = idx[m];
   }
   MG_CHECK_INDEX(tok, tok >= 0 && tok < V, 0, err, 1u)
-  const int t = pos_dev ? *pos_dev : (int)(m % T);  // decode step: one token at a device position
+  int t = pos_dev ? *pos_dev : (int)(m % T);  // decode step: one token at a device position
+  // ragged decode (pos_stride 1): row m sits at its own position, kept inside wpe's rows
+  if (pos_dev && pos_stride) t = min(max(pos_dev[m * pos_stride], 0), pos_rows - 1);
   for (int c = lane * 8; c < D; c += 512) {
     float a[8], p[8];
     unpack8(ld16(wte + tok * D + c), a);
@@ -134,12 +139,12 @@ namespace mg {
 void embedding_fwd(const int64_t* idx, const bf16_t* wte, const bf16_t* wpe, bf16_t* out, int M,
                    int T, int D, int V, float p, uint64_t seed, hipStream_t stream, const int* pos_dev,
                    const unsigned long long* am_part, int am_groups, int64_t* tok, int64_t* seq,
-                   long seq_ld) {
+                   long seq_ld, int pos_stride, int pos_rows) {
   const uint32_t thr = dropout_threshold16(p);  // the residual-stream mask (common.h)
   emb_fwd_kernel<<<cdiv(M, 4), 256, 0, stream>>>(idx, wte, wpe, out, M, T, D, V, debug_err_word(), seed, thr,
                                                  dropout_scale16(thr), p > 0.f,
-                                                 graph_seed_ofs(), pos_dev, am_part, am_groups, tok, seq,
-                                                 seq_ld);
+                                                 graph_seed_ofs(), pos_dev, pos_stride, pos_rows, am_part,
+                                                 am_groups, tok, seq, seq_ld);
 }
 
 void embedding_bwd(const int64_t* idx, const bf16_t* dout, float* dwte, float* dwpe, int M, int T,

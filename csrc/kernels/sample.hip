@@ -21,6 +21,10 @@
 // position from pos_dev), so a captured launch replays with a new seed, temperature or k.  The
 // draw counter and the position advance in a one-thread kernel launched after the sampler: the
 // stream order is the "every row has read them" guarantee, with no cross-workgroup hand-off.
+//
+// Ragged batches (pick_ragged): every row has its own position, draw counter (position + 1) and
+// finished flag in device memory, read and written by the row's own workgroup only -- the sampler
+// in its RAGGED form or the greedy pick kernel, both ending in ragged_finish.  No advance kernel.
 #include "common.h"
 #include "kernels.h"
 
@@ -125,9 +129,53 @@ MG_DEVICE void hist_select(const uint32_t* hist, uint32_t* scan, uint32_t want, 
   __syncthreads();  // scan and hist may be rewritten
 }
 
-// params: {seed_lo, seed_hi, draw, inv_t (fp32 bits), top_k (<= 0: off), 0, 0, 0}
+// order-preserving key of a float with the index inverted in the low half: the max key is the
+// FIRST index among equal values (the amax_key of gemv.hip, whose fused argmax ranks the same
+// stored bf16 logits)
+MG_DEVICE unsigned long long amax_key(float v, int n) {
+  const uint32_t u = __float_as_uint(v);
+  const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)k << 32) | (uint32_t)(0xffffffffu - (uint32_t)n);
+}
+
+// max of one key per thread over the workgroup, valid in thread 0
+MG_DEVICE unsigned long long block_max_key(unsigned long long best, unsigned long long* redk) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long k = shfl_xor_u64(best, o);
+    best = k > best ? k : best;
+  }
+  if (lane == 0) redk[w] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < kWaves; ++i) best = redk[i] > best ? redk[i] : best;
+  }
+  return best;
+}
+
+// Ragged decode: the end of row b's step, by one thread of the row's own workgroup.  p is the
+// row's position as the workgroup read it (pos[b]); the picked token t goes to tok[b] and
+// seq[b, p + 1], the position moves on, and the row is finished once t is the stop token
+// (params[5], negative: none).  Nobody else reads or writes pos[b], done[b], tok[b] or row b of
+// seq in this launch, so there is no hand-off and no trailing advance kernel.  The position never
+// reaches seq_ld - 1 = Tmax (the cache's and wpe's row count): a row that would is left as it is.
+MG_DEVICE void ragged_finish(long t, int b, int p, int eos, int* pos, int* done, int64_t* tok, int64_t* seq,
+                             long seq_ld) {
+  if (p < 0 || (long)p + 1 >= seq_ld - 1) return;
+  tok[b] = t;
+  seq[(long)b * seq_ld + p + 1] = t;
+  pos[b] = p + 1;
+  if (eos >= 0 && t == (long)eos) done[b] = 1;
+}
+
+// params: {seed_lo, seed_hi, draw, inv_t (fp32 bits), top_k (<= 0: off), eos (ragged), 0, 0}
+// RAGGED: per-row state -- the draw counter is pos_dev[b] + 1 (the column of the produced token in
+// the row's own sequence), a row whose done[b] is set is skipped, and ragged_finish ends the row.
+template <bool RAGGED>
 __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
-                                                          const uint32_t* params, const int* pos_dev,
+                                                          const uint32_t* params, int* pos_dev, int* done,
                                                           int64_t* __restrict__ tok, int64_t* __restrict__ seq,
                                                           long seq_ld) {
   __shared__ uint32_t hist[256 * kCopies];
@@ -136,7 +184,12 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
   __shared__ unsigned long long redk[kWaves];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bf16_t* row = logits + (long)b * ld;
-  const uint32_t seed_lo = params[0], seed_hi = params[1], draw = params[2];
+  int rpos = 0;
+  if constexpr (RAGGED) {
+    if (done[b]) return;  // the whole workgroup: a finished row changes nothing
+    rpos = pos_dev[b];
+  }
+  const uint32_t seed_lo = params[0], seed_hi = params[1], draw = RAGGED ? (uint32_t)(rpos + 1) : params[2];
   const float inv_t = __uint_as_float(params[3]);
   const int top_k = (int)params[4];
   const bool select = top_k > 0 && top_k < V;  // k >= V keeps every element
@@ -233,11 +286,53 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     for (int i = 1; i < kWaves; ++i) best = redk[i] > best ? redk[i] : best;
     long t = (long)(0xffffffffu - (uint32_t)best);
     if (t >= V) t = V - 1;  // no candidate (a row without a finite maximum): still a valid id
-    if (tok) tok[b] = t;
-    if (seq) {
-      const long p = (long)pos_dev[0] + 1;
-      if (p >= 0 && p < seq_ld) seq[(long)b * seq_ld + p] = t;
+    if constexpr (RAGGED) {
+      ragged_finish(t, b, rpos, (int)params[5], pos_dev, done, tok, seq, seq_ld);
+    } else {
+      if (tok) tok[b] = t;
+      if (seq) {
+        const long p = (long)pos_dev[0] + 1;
+        if (p >= 0 && p < seq_ld) seq[(long)b * seq_ld + p] = t;
+      }
     }
+  }
+}
+
+// Ragged greedy pick: one workgroup per logits row, the argmax over the first V bf16 columns
+// (16-byte loads, first index on ties), then ragged_finish.
+__global__ __launch_bounds__(kThreads) void pick_greedy_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                               const uint32_t* params, int* pos, int* done,
+                                                               int64_t* __restrict__ tok,
+                                                               int64_t* __restrict__ seq, long seq_ld) {
+  __shared__ unsigned long long redk[kWaves];
+  const int b = blockIdx.x;
+  if (done[b]) return;  // the whole workgroup: a finished row changes nothing
+  const int p = pos[b];
+  const bf16_t* row = logits + (long)b * ld;
+  unsigned long long best = 0ull;
+  auto rank = [&](int i, uint32_t bits) {
+    const unsigned long long k = amax_key(bf2f(bits), i);
+    best = k > best ? k : best;
+  };
+  // a row that fits the registers is loaded with every load in flight together, as in the sampler
+  const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
+  if (nv <= kRegVec * kThreads) {
+    uint4 regs[kRegVec];
+#pragma unroll
+    for (int j = 0; j < kRegVec; ++j) {
+      const int v = (int)threadIdx.x + j * kThreads;
+      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    const uint32_t tail = (threadIdx.x < 8 && ti < V) ? (uint32_t)row[ti] : 0u;
+    for_regs(regs, tail, V, rank);
+  } else {
+    for_row(row, V, rank);
+  }
+  best = block_max_key(best, redk);
+  if (threadIdx.x == 0) {
+    long t = (long)(0xffffffffu - (uint32_t)best);
+    if (t >= V) t = V - 1;
+    ragged_finish(t, b, p, (int)params[5], pos, done, tok, seq, seq_ld);
   }
 }
 
@@ -255,8 +350,14 @@ namespace mg {
 
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
                    int64_t* seq, long seq_ld, hipStream_t stream) {
-  sample_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, tok, seq, seq_ld);
+  sample_kernel<false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, nullptr, tok, seq, seq_ld);
   sample_advance_kernel<<<1, 64, 0, stream>>>(params, pos_dev);
+}
+
+void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos, int* done, int64_t* tok,
+                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream) {
+  if (greedy) pick_greedy_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld);
+  else sample_kernel<true><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld);
 }
 
 }  // namespace mg

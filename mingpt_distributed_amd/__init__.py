@@ -6,7 +6,7 @@ buffers, fused AdamW), ``parallel`` (RCCL data parallel engine), ``trainer``, ``
 """
 __version__ = "0.1.0"
 
-from .models import GPT, GPTConfig, OptimizerConfig  # noqa: E402
+from .models import GPT, GPTConfig, OptimizerConfig, generate, generate_batch  # noqa: E402
 from .optim import create_optimizer  # noqa: E402
 from .trainer import GPTTrainer, GPTTrainerConfig, ModelSnapshot, Trainer  # noqa: E402
 from .data import CharDataset, DataConfig  # noqa: E402
@@ -14,4 +14,4 @@ from .utils import CfgNode, set_seed, setup_logging, print_model_size  # noqa: E
 
 __all__ = ["GPT", "GPTConfig", "OptimizerConfig", "create_optimizer", "GPTTrainer", "GPTTrainerConfig",
            "ModelSnapshot", "Trainer", "CharDataset", "DataConfig", "CfgNode", "set_seed", "setup_logging",
-           "print_model_size"]
+           "print_model_size", "generate", "generate_batch"]

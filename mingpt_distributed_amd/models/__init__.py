@@ -1,4 +1,6 @@
 from .config import GPTConfig, OptimizerConfig, PRESETS
 from .gpt import GPT, Block, CausalSelfAttention, MLP
+from .generation import generate, generate_batch
 
-__all__ = ["GPTConfig", "OptimizerConfig", "PRESETS", "GPT", "Block", "CausalSelfAttention", "MLP"]
+__all__ = ["GPTConfig", "OptimizerConfig", "PRESETS", "GPT", "Block", "CausalSelfAttention", "MLP", "generate",
+           "generate_batch"]

@@ -15,9 +15,14 @@ context (exactly the reference's cropping semantics).
 Sampling: ``seed=None`` is the reference's recipe on torch's global generator (``_sample``).  With a
 seed the draw is counter-based Gumbel-max (``ops.reference.sample_gumbel``; on the GPU the sample
 kernel inside a device-side token loop, ``_GpuCache.sample``): reproducible per (seed, column, row).
+
+Ragged batches (``generate_batch``): prompts of different lengths, right-padded, decoded together;
+each row has its own position and finished flag in device memory (``_GpuCache.ragged``), stops at
+its own stop token, and computes what the single-prompt path computes for that row alone.
 """
 from __future__ import annotations
 
+import gc
 import struct
 from typing import Optional
 
@@ -114,13 +119,32 @@ def bf16_weights(model):
     return get
 
 
+def _capture(fn):
+    """(graph, fn()) with fn's launches captured into a new hipGraph.  Python's cyclic garbage is
+    collected first and the collector stays off until the capture ends: a decode state and its
+    model refer to each other, so a dropped model's graphs are freed by the collector, and a
+    graph destroyed while a stream is capturing is a HIP error raised from a destructor (the
+    process aborts).  ``torch.cuda.graph`` no longer collects on entry by itself."""
+    gc.collect()
+    on = gc.isenabled()
+    gc.disable()
+    try:
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = fn()
+    finally:
+        if on:
+            gc.enable()
+    return graph, out
+
+
 class _GpuCache:
     """KV caches ([B, Tmax, 3D] qkv rows per layer) plus the captured decode steps of one model at
     one batch size.  Kept on the model across ``generate`` calls (``_gpu_cache``): a later call
     with the same batch re-prefills into the same buffers and replays the same hipGraphs, unless
     a weight changed storage or version since the capture (then the graphs are re-captured)."""
 
-    def __init__(self, model, idx, tmax):
+    def __init__(self, model, idx, tmax, last=None):
         from ..ops._ext import ext
         from ..ops import gemm as G
 
@@ -141,13 +165,13 @@ class _GpuCache:
                                     device=idx.device, dtype=torch.float32)
         self.dec_cnt = torch.zeros(B * H, device=idx.device, dtype=torch.int32)
         self.stamp = _weight_stamp(model)
-        self.logits = self._run(idx, 0)
+        self.logits = self._run(idx, 0, last=last)
 
-    def prefill(self, idx):
-        self.logits = self._run(idx, 0)
+    def prefill(self, idx, last=None):
+        self.logits = self._run(idx, 0, last=last)
         return self.logits
 
-    def _run(self, idx, pos0, pos_dev=None, greedy=None, sample=None):
+    def _run(self, idx, pos0, pos_dev=None, greedy=None, sample=None, last=None, ragged=None):
         """Prefill (pos0 == 0) or one decode step at position pos0 (or at ``pos_dev[0]``, an int32
         device scalar, when captured in a hipGraph).  ``greedy`` = (tok [B, 1] int64, pos_dev,
         seq [B, Tmax + 1] int64, part [B, G] int64 or None): the step needs nothing from the host.
@@ -157,7 +181,12 @@ class _GpuCache:
         no cross-workgroup hand-off inside a kernel.  Without it the argmax runs in torch and
         writes tok and seq[:, pos + 1] itself.  ``sample`` = (tok, pos_dev, seq, params): the
         sample kernel (sample.hip) draws tok and seq[:, pos + 1] from this step's logits by the
-        device parameter block ``params`` and advances pos_dev and the draw counter."""
+        device parameter block ``params`` and advances pos_dev and the draw counter.
+        ``last`` (prefill of a right-padded batch): int64 [B], the column whose logits row b
+        returns (its length - 1) instead of the last one.  ``ragged`` = (state, greedy): a decode
+        step of a ragged batch -- ``pos_dev`` is the state's int32 [B], row b embeds its token at
+        ``pos[b]``, appends K/V at and attends up to its own cache row, and the pick kernel
+        (``pick_ragged``) ends the step per row (``_GpuCache.ragged``)."""
         C, G, bf = self.C, self.G, self.bf
         m = self.model
         tr, cfg = m.transformer, m.config
@@ -174,6 +203,9 @@ class _GpuCache:
                                 greedy[2]).view(B * T, D)
         elif pos0 == 0:
             x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0).view(B * T, D)
+        elif ragged is not None:  # one position per row, picked on the device
+            x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0, pos_dev,
+                                pos_stride=1).view(B * T, D)
         elif pos_dev is not None:  # the position row is picked on the device (one kernel)
             x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0, pos_dev).view(B * T, D)
         else:  # single token at position pos0
@@ -202,12 +234,18 @@ class _GpuCache:
             if pos0 == 0:
                 self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
                 y, _, _ = C.attention_fwd(qkv, B, T, H, 0.0, 0)
+            elif ragged is not None:
+                y = C.attention_decode(qkv, self.caches[i], H, pos0, pos_dev, self.dec_part, self.dec_cnt,
+                                       pos_stride=1)
             else:
                 y = C.attention_decode(qkv, self.caches[i], H, pos0, pos_dev, self.dec_part, self.dec_cnt)
             x = lin(y, a.c_proj.weight, a.c_proj.bias, "resid", resid=x)
             u = lin(x, mm.c_fc.weight, mm.c_fc.bias, "gelu", ln=blk.ln_2)
             x = lin(u, mm.c_proj.weight, mm.c_proj.bias, "resid", resid=x)
-        last = x.view(B, T, D)[:, -1].contiguous()
+        if last is not None:  # right-padded prefill: row b's hidden state at its own last token
+            last = x.view(B, T, D)[torch.arange(B, device=x.device), last].contiguous()
+        else:
+            last = x.view(B, T, D)[:, -1].contiguous()
         am = (part, pos_dev) if part is not None else None
         logits = lin(last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8, ln=tr.ln_f, am=am)
         if greedy is not None and part is None:  # small vocab (no fused argmax): same in torch
@@ -219,6 +257,9 @@ class _GpuCache:
         if sample is not None:
             tok, pd, seq, params = sample
             C.sample_logits(logits, V, params, pd, tok, seq)
+        if ragged is not None:
+            st, rg = ragged
+            C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], rg)
         return logits[:, :V]
 
     def _fresh(self):
@@ -228,6 +269,7 @@ class _GpuCache:
             self.__dict__.pop("_graph", None)
             self.__dict__.pop("_ggraph", None)
             self.__dict__.pop("_sgraph", None)
+            self.__dict__.pop("_rgraph", None)
 
     def step(self, tok, pos):
         """One decode step.  Decoding is launch-bound (B rows through ~5 kernels per layer), so
@@ -241,10 +283,7 @@ class _GpuCache:
             g = self._graph = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32,
                                                                      device=tok.device)}
             self._run(g["tok"], pos, g["pos"])  # warm-up (workspaces, lazy kernel attributes)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                g["logits"] = self._run(g["tok"], max(pos, 1), g["pos"])
-            g["graph"] = graph
+            g["graph"], g["logits"] = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"]))
         g["tok"].copy_(tok)
         g["pos"].fill_(pos)
         g["graph"].replay()
@@ -271,10 +310,8 @@ class _GpuCache:
             self._greedy_seed(g, tok, pos)
             self._run(g["tok"], max(pos, 1), g["pos"], (g["tok"], g["pos"], g["seq"], g["part"]))
         if _GRAPH_DECODE and "graph" not in g:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._run(g["tok"], max(pos, 1), g["pos"], (g["tok"], g["pos"], g["seq"], g["part"]))
-            g["graph"] = graph
+            g["graph"], _ = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"],
+                                                       (g["tok"], g["pos"], g["seq"], g["part"])))
         self._greedy_seed(g, tok, pos)
         for _ in range(n):
             if _GRAPH_DECODE:
@@ -296,7 +333,15 @@ class _GpuCache:
         if p is None:
             p = self._sparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
         p.copy_(torch.tensor(words, dtype=torch.int32))
+        self._rwords = None  # the sampler's advance kernel moves the draw counter: nothing to reuse
         return p
+
+    def _ragged_params(self, st, words):
+        """Set the parameter block for the ragged loop, which only reads it: an unchanged block is
+        not uploaded again (a host-to-device copy waits for the queued replays to drain)."""
+        if self.__dict__.get("_rwords") != list(words):
+            st["params"].copy_(torch.tensor(words, dtype=torch.int32))
+            self._rwords = list(words)
 
     def sample_prefill(self, words):
         """The token [B] drawn from the prefill logits (the first token of a context window)."""
@@ -321,10 +366,8 @@ class _GpuCache:
             g["params"] = self._sample_params(words)
             self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
         if _GRAPH_DECODE and "graph" not in g:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
-            g["graph"] = graph
+            g["graph"], _ = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"],
+                                                       sample=(g["tok"], g["pos"], g["seq"], g["params"])))
         g["tok"].copy_(tok)
         g["pos"].fill_(pos)
         self._sample_params(words)
@@ -334,6 +377,71 @@ class _GpuCache:
             else:
                 self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
         return g["seq"][:, pos + 1:pos + 1 + n]
+
+    # ----------------------------------------------------------------- ragged batches
+    def ragged_state(self):
+        """The per-row device state of the ragged loop, allocated once per decode state (the
+        captured step bakes the pointers in): ``pos`` int32 [B] (position of the row's newest
+        token), ``done`` int32 [B], ``tok`` int64 [B, 1] (the newest token, the next step's input),
+        ``seq`` int64 [B, tmax + 1] and the sample parameter block ``params``."""
+        st = self.__dict__.get("_rstate")
+        if st is None:
+            dev, B = self.caches[0].device, self.B
+            st = self._rstate = {"pos": torch.zeros(B, dtype=torch.int32, device=dev),
+                                 "done": torch.zeros(B, dtype=torch.int32, device=dev),
+                                 "tok": torch.zeros(B, 1, dtype=torch.long, device=dev),
+                                 "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
+                                 "params": self._sample_params([0] * 8)}
+        return st
+
+    def ragged_start(self, idx, lengths, words, greedy):
+        """Point the ragged state at a prefilled right-padded batch ``idx`` [B, Tp] with ``lengths``
+        [B] (``self.logits`` = row b's logits at column lengths[b] - 1) and pick every row's first
+        token with the loop's own pick kernel: pos = lengths - 1 and done = 0 going in."""
+        st = self.ragged_state()
+        st["seq"].zero_()
+        st["seq"][:, :idx.size(1)].copy_(idx)
+        st["pos"].copy_(lengths - 1)
+        st["done"].zero_()
+        self._ragged_params(st, words)
+        logits = self.logits  # [B, V] view of the padded [B, ld] buffer the LM head wrote
+        self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
+                           greedy)
+        return st
+
+    def ragged(self, n, words, greedy):
+        """n decode steps of a ragged batch on the current device state (``ragged_state``): embed
+        ``tok[b]`` at ``pos[b]``, the blocks with per-row decode attention, the plain LM head, then
+        the pick kernel -- greedy argmax or the seeded draw with counter ``pos[b] + 1`` -- which
+        writes the row's next token and advances its position, or leaves a finished row alone.  A
+        finished row keeps flowing through the step with its token and position frozen (it re-embeds
+        the same token and rewrites the same cache row), so the launch shapes never change: one
+        captured graph per mode (``_rgraph[greedy]``), replayed back to back with no host round
+        trip.  Resumable: n calls of one step equal one call of n steps.  ``words``: the parameter
+        block (``_ragged_words``).  Returns the state; the last step's logits are
+        ``_rgraph[greedy]["logits"]``."""
+        self._fresh()
+        st = self.ragged_state()
+        self._ragged_params(st, words)
+        gs = self.__dict__.setdefault("_rgraph", {})
+        g = gs.get(greedy)
+        run = lambda: self._run(st["tok"], 1, st["pos"], ragged=(st, greedy))
+        if g is None:
+            # eager warm-up (workspaces, lazy kernel attributes) with every row marked finished:
+            # the step is idempotent then, so the state the caller set up is left as it is
+            g = gs[greedy] = {}
+            done = st["done"].clone()
+            st["done"].fill_(1)
+            run()
+            st["done"].copy_(done)
+        if _GRAPH_DECODE and "graph" not in g:
+            g["graph"], g["logits"] = _capture(run)
+        for _ in range(n):
+            if _GRAPH_DECODE:
+                g["graph"].replay()
+            else:
+                g["logits"] = run()
+        return st
 
     @staticmethod
     def _greedy_seed(g, tok, pos):
@@ -360,13 +468,21 @@ def _weight_stamp(model):
     return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
 
-def _gpu_cache(model, idx, tmax):
+def _ragged_words(seed, temperature, top_k, eos_token):
+    """The parameter block of the ragged pick kernels: ``_sample_words`` (the draw counter is not
+    used: it is the row's position + 1) with the stop token in word 5, -1 for none."""
+    w = _sample_words(seed, 0, temperature, top_k)
+    w[5] = -1 if eos_token is None else int(eos_token)
+    return w
+
+
+def _gpu_cache(model, idx, tmax, last=None):
     """The model's decode state for this batch size (re-prefilled), or a new one."""
     c = model.__dict__.get("_mg_decode_cache")
     if c is not None and c.B == idx.size(0) and c.tmax == tmax and c.caches[0].device == idx.device:
-        c.prefill(idx)
+        c.prefill(idx, last)
         return c
-    c = _GpuCache(model, idx, tmax)
+    c = _GpuCache(model, idx, tmax, last)
     model.__dict__["_mg_decode_cache"] = c
     return c
 
@@ -468,3 +584,127 @@ def _generate_sample_gpu(model, idx, max_new_tokens, temperature, top_k, seed):
             out[:, T:T + n] = cache.sample(out[:, T - 1:T], L, n, _sample_words(seed, T, temperature, top_k))
             T += n
     return out
+
+
+# --------------------------------------------------------------------------- ragged batches
+_EARLY_EXIT = True  # set False to replay every step even after every row has stopped
+_EXIT_EVERY = 16    # replays between two reads of the finished flags
+
+
+def _ragged_prompts(prompts):
+    """(rows, device): the unpadded int64 prompts of either input form, on the first one's device."""
+    if isinstance(prompts, tuple) and len(prompts) == 2 and torch.is_tensor(prompts[0]) and prompts[0].dim() == 2:
+        idx, lengths = prompts
+        lengths = torch.as_tensor(lengths).to("cpu", torch.long).view(-1)
+        if lengths.numel() != idx.size(0):
+            raise ValueError(f"generate_batch: {idx.size(0)} rows, {lengths.numel()} lengths")
+        if lengths.numel() and (int(lengths.min()) < 1 or int(lengths.max()) > idx.size(1)):
+            raise ValueError(f"generate_batch: every length must be in 1..{idx.size(1)}, got {lengths.tolist()}")
+        rows = [idx[b, :int(n)] for b, n in enumerate(lengths.tolist())]
+    else:
+        rows = [torch.as_tensor(p) for p in prompts]
+        if any(r.dim() != 1 or r.numel() < 1 for r in rows):
+            raise ValueError("generate_batch: every prompt must be a 1-D tensor of 1 or more tokens")
+    if not rows:
+        raise ValueError("generate_batch: no prompts")
+    device = rows[0].device
+    return [r.to(device=device, dtype=torch.long) for r in rows], device
+
+
+@torch.no_grad()
+def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
+                   top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
+                   pad_token: int = 0):
+    """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``.
+
+    ``prompts``: a sequence of 1-D int64 tensors (1 or more tokens each), or a pair ``(idx [B, Tp]
+    right-padded, lengths [B])`` -- positions at or past a row's length are ignored, whatever they
+    hold.  ``tokens`` is int64 [B, max(len) + max_new_tokens]: row b holds its prompt, its generated
+    tokens directly after it (``eos_token``, if produced, is the row's last token) and ``pad_token``
+    in the rest; ``lengths`` int64 [B] counts the valid tokens per row, prompt included.
+
+    Every row is the single-prompt algorithm applied to that row alone: greedy takes the argmax of
+    the row's last-position logits (first index on ties); sampling is the seeded Gumbel-max rule of
+    ``generate(seed=...)`` with the draw counter = the column of the produced token in the row's
+    own unpadded sequence and the batch row index b (``do_sample`` without a seed draws one seed
+    from torch's global generator first).  A row stops after ``eos_token`` or ``max_new_tokens``
+    tokens.  There is no sliding window here: ``max(len) + max_new_tokens`` must fit ``block_size``
+    (ValueError otherwise).
+
+    On the GPU the right-padded batch is prefilled once and the token loop is one captured step
+    replayed back to back (``_GpuCache.ragged``): per-row positions and finished flags live in
+    device memory.  On the CPU each row runs through the cache path on its own."""
+    rows, device = _ragged_prompts(prompts)
+    V, bs = model.config.vocab_size, model.block_size
+    lens = [r.numel() for r in rows]
+    B, Lmax = len(rows), max(lens)
+    if max_new_tokens < 0:
+        raise ValueError(f"generate_batch: max_new_tokens must be >= 0, got {max_new_tokens}")
+    if Lmax + max_new_tokens > bs:
+        raise ValueError(f"generate_batch: longest prompt ({Lmax}) + max_new_tokens ({max_new_tokens}) exceeds "
+                         f"block_size ({bs}); this entry point has no sliding window")
+    if not 0 <= int(pad_token) < V:
+        raise ValueError(f"generate_batch: pad_token {pad_token} is not a token id (vocab {V})")
+    if eos_token is not None and not 0 <= int(eos_token) < V:
+        raise ValueError(f"generate_batch: eos_token {eos_token} is not a token id (vocab {V})")
+    R.check_sample_args(temperature, top_k)
+    if do_sample and seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+    seed = int(seed or 0) & ((1 << 64) - 1)
+    before_use(*model.parameters())
+    lengths = torch.tensor(lens, dtype=torch.long, device=device)
+    tokens = torch.full((B, Lmax + max_new_tokens), int(pad_token), dtype=torch.long, device=device)
+    for b, r in enumerate(rows):
+        tokens[b, :lens[b]] = r
+    lo, hi = tokens.aminmax()  # the padding is pad_token, a valid id
+    if int(lo) < 0 or int(hi) >= V:
+        raise ValueError(f"generate_batch: prompt token outside [0, {V})")
+    if max_new_tokens == 0:
+        return tokens, lengths
+    if device.type == "cuda":
+        return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
+                                   do_sample, top_k, seed, eos_token, int(pad_token))
+    for b, r in enumerate(rows):  # the executable definition of the semantics
+        cache = _CpuCache(model, r.view(1, -1))
+        logits, n = cache.logits, lens[b]
+        for _ in range(max_new_tokens):
+            if do_sample:
+                nxt = R.sample_gumbel(logits, temperature, top_k, seed, n, row0=b)
+            else:
+                nxt = logits.argmax(dim=-1, keepdim=True)
+            tokens[b, n] = nxt.view(())
+            n += 1
+            if eos_token is not None and int(nxt) == int(eos_token):
+                break
+            if n < lens[b] + max_new_tokens:
+                logits = cache.step(nxt, n - 1)
+        lengths[b] = n
+    return tokens, lengths
+
+
+def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
+                        pad_token):
+    """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
+    causal attention makes every position before a row's length exact -- take row b's logits at
+    column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
+    ragged step max_new_tokens - 1 times.  With a stop token the finished flags are read every
+    ``_EXIT_EVERY`` replays; stopping early changes nothing, since a step leaves finished rows as
+    they are."""
+    B, Lmax = idx.shape
+    cache = _gpu_cache(model, idx, model.block_size, last=lengths - 1)
+    words = _ragged_words(seed, temperature, top_k, eos_token)
+    greedy = not do_sample
+    st = cache.ragged_start(idx, lengths, words, greedy)
+    n = max_new_tokens - 1
+    check = _EARLY_EXIT and eos_token is not None  # without a stop token no row finishes early
+    while n > 0:
+        k = min(n, _EXIT_EVERY) if check else n
+        cache.ragged(k, words, greedy)
+        n -= k
+        if check and n > 0 and bool(st["done"].all()):
+            break
+    out_len = st["pos"].long() + 1
+    W = Lmax + max_new_tokens
+    cols = torch.arange(W, device=idx.device).view(1, W)
+    tokens = torch.where(cols < out_len.view(B, 1), st["seq"][:, :W], torch.full_like(cols, pad_token))
+    return tokens, out_len

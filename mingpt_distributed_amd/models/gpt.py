@@ -228,6 +228,18 @@ class GPT(nn.Module):
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
                         top_k=top_k, use_cache=use_cache, seed=seed)
 
+    @torch.no_grad()
+    def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
+                       top_k: Optional[int] = None, seed: Optional[int] = None,
+                       eos_token: Optional[int] = None, pad_token: int = 0):
+        """Decode prompts of different lengths in one batch, each row stopping at ``eos_token`` or
+        after ``max_new_tokens``; returns ``(tokens, lengths)`` (``generation.generate_batch``).  No
+        sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``."""
+        from .generation import generate_batch
+
+        return generate_batch(self, prompts, max_new_tokens, temperature=temperature, do_sample=do_sample,
+                              top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token)
+
     # -------------------------------------------------------------------------------- optimizer
     def configure_optimizers(self, train_config):
         """Upstream-minGPT API: AdamW with weight decay on Linear weights only."""

@@ -10,6 +10,13 @@ is one fused-kernel decode step against the KV cache.
 
     python projects/generate/generate.py --weights /path/to/gpt2 --prompt "Andrej Karpathy, the" \
         --num-samples 5 --steps 20 --device cuda
+
+Several prompts (``--prompt`` repeated, and / or ``--prompt-file`` with one prompt per line) are
+decoded together in one ragged batch (``GPT.generate_batch``): every prompt keeps its own length,
+``--num-samples`` rows each, and a row stops at the tokenizer's ``<|endoftext|>``.
+
+    python projects/generate/generate.py --weights /path/to/gpt2 --prompt "The capital of France" \
+        --prompt "Once upon a time, in a land far away," --num-samples 2 --steps 40 --device cuda
 """
 import argparse
 import os
@@ -28,7 +35,9 @@ def main(argv=None):
     ap.add_argument("--model-type", default="gpt2")
     ap.add_argument("--weights", default=None, help="local GPT-2 checkpoint (file or HF directory)")
     ap.add_argument("--random-init", action="store_true")
-    ap.add_argument("--prompt", default="")
+    ap.add_argument("--prompt", action="append", default=None,
+                    help="prompt text; repeat it to decode several prompts in one ragged batch")
+    ap.add_argument("--prompt-file", default=None, help="a file with one prompt per non-empty line")
     ap.add_argument("--num-samples", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--top-k", type=int, default=40)
@@ -53,9 +62,15 @@ def main(argv=None):
         tok = BPETokenizer()
     except Exception as e:  # vocab files absent: fall back to raw token ids
         print(f"(no BPE vocabulary available: {e}; printing token ids)")
-    if tok is not None:
-        x = tok(a.prompt if a.prompt else "<|endoftext|>").to(dev) if a.prompt else \
-            torch.tensor([[50256]], dtype=torch.long, device=dev)
+    texts = list(a.prompt or [])
+    if a.prompt_file:
+        with open(a.prompt_file, "r", encoding="utf-8") as f:
+            texts += [ln.rstrip("\n") for ln in f if ln.strip()]
+    if len(texts) > 1:
+        return generate_many(model, tok, texts, a, dev)
+    prompt = texts[0] if texts else ""
+    if tok is not None and prompt:
+        x = tok(prompt).to(dev)
     else:
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
     x = x.expand(a.num_samples, -1).contiguous()
@@ -64,6 +79,29 @@ def main(argv=None):
     outs = []
     for i in range(a.num_samples):
         out = tok.decode(y[i].cpu().squeeze()) if tok is not None else y[i].tolist()
+        outs.append(out)
+        print("-" * 80)
+        print(out)
+    return outs
+
+
+def generate_many(model, tok, texts, a, dev):
+    """Several prompts in one ragged batch: ``--num-samples`` rows per prompt, each with its own
+    length, stopped at ``<|endoftext|>`` when the tokenizer has one.  Without a vocabulary a prompt
+    is a line of token ids."""
+    if tok is not None:
+        rows = [tok(t)[0] if t else torch.tensor([50256]) for t in texts]
+        eos = tok.encoder.encoder.get("<|endoftext|>")
+    else:
+        rows = [torch.tensor([int(w) for w in t.split()] or [0], dtype=torch.long) for t in texts]
+        eos = None
+    rows = [r.to(dev) for r in rows for _ in range(a.num_samples)]
+    y, n = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
+                                top_k=a.top_k, seed=a.seed, eos_token=eos)
+    outs = []
+    for i in range(len(rows)):
+        ids = y[i, :int(n[i])].cpu()
+        out = tok.decode(ids) if tok is not None else ids.tolist()
         outs.append(out)
         print("-" * 80)
         print(out)
