@@ -1,5 +1,7 @@
-"""Per-tile phase times of attn_bwd64_kernel from a -DMG_BWD64_STAMPS build (s_memtime per wave at
-8 points of each tile of the first 64 workgroups = key block 0 at the GPT-2 B = 128 shape):
+"""Per-tile phase times of attn_bwd64_kernel / attn_bwdchain_kernel (whichever the backward mode
+takes: MINGPT_ATTN_BWD_MODE=2 / 3, default auto) from a -DMG_BWD64_STAMPS build (s_memtime per wave
+at 8 points of each tile of the first 64 workgroups = key block 0 at the GPT-2 B = 128 shape; the
+"second item" is the next item from the counter, or the chain's key block 1):
     MINGPT_EXT_SO=build/ab/stamps/_C.so python bench/dev/bwd64_stamps.py"""
 import os
 import sys

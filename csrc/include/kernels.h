@@ -137,11 +137,17 @@ void attention_fwd(const bf16_t* qkv, bf16_t* out, float* lse, uint32_t* dmask, 
 // delta [B*H*T] and dq [attention_bwd_workspace_floats] fp32 are workspaces; writes all three
 // slots of dqkv
 size_t attention_bwd_workspace_floats(int B, int T, int H, int hd);
+// backward schedule (also MINGPT_ATTN_BWD_MODE): 0 auto; 1 persistent (b, h) workgroups, dQ summed
+// in place; 2 key-block items with fp32 dQ partials and a finalize pass; 3 chained: a workgroup
+// per (b, h) runs its key blocks in order with a running dQ sum and no finalize (hd = 64 with more
+// than one key block and attention_set_bwd64 on; elsewhere 3 means 0).  Auto: 1 for a single key
+// block, 3 where it exists and B*H fills the CUs in near-whole rounds, else 2.
 void attention_set_bwd_mode(int mode);
+// 1 (default): hd = 64 backward kernels attn_bwd64_kernel / attn_bwdchain_kernel; 0: the general kernel
 void attention_set_bwd64(int on);
 #ifdef MG_BWD64_STAMPS
 void attention_bwd64_stamps(unsigned long long* host);  // diagnostic build only
-#endif  // 1 (default): hd = 64 key-block backward attn_bwd64_kernel; 0: the general kernel  // 0 auto, 1 persistent (b, h) workgroups, 2 key-block partials
+#endif
 // dbias (fp32 [3D] or null): += the column sums of dqkv (the qkv bias gradient), fused into the
 // backward kernels where the schedule allows
 void attention_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse,

@@ -700,7 +700,23 @@ MG_DEVICE void dma_dword(const u32x4_t& rs, uint32_t voff, uint32_t soff, uint32
 //  * every LDS address is a per-lane base computed once per kernel plus an immediate.
 // Register budget: dK^T / dV^T of 2 groups (128), K / V fragments (64), two S / dP~ pairs (64), the
 // next tile's staged Q / dO (32), row constants of two subtiles (64), operand fragments.
-__global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
+//
+// Two schedules share this body (two kernels below, the tile body and every image the same):
+//  * CHAIN = false, attn_bwd64_kernel: a work item is one (key block, b, h); every item writes an
+//    fp32 dQ partial per query tile and attn_dq_finalize_kernel sums them.
+//  * CHAIN = true, attn_bwdchain_kernel: a workgroup takes a whole (b, h) from the counter and runs
+//    its key blocks in ascending order as consecutive items.  dQ of a query tile is a running fp32
+//    sum in the workspace: key block 0 starts it, later blocks reload it and add their own dQ
+//    (accumulated from zero, then run + p: the finalize's 0 + p0 + p1 + ... bit for bit), and the
+//    tile's last contributor -- the key block it is a diagonal tile of -- scales, rounds and stores
+//    bf16 rows straight into dqkv's Q slot.  No partials, no finalize pass.  The running sum is
+//    private to the kernel and the lane that stores an element reloads it, so it is kept in
+//    fragment order by whole 128-row tiles: tile (bh, qt), wave w, 8 x 16 bytes per lane, each
+//    instruction one contiguous KiB.  The dQ MFMAs take their operands swapped (K^T as A, dS as
+//    B): dQ^T with the query on the lane, dK^T / dV^T's register layout, so store_row writes the
+//    bf16 rows as 16-byte stores.
+template <bool CHAIN>
+MG_DEVICE void bwd64_body(const AttnArgs& a) {
   [[maybe_unused]] int bwd64_it = 0;  // stamps (diagnostic build): the work item's ordinal
   BWD64_PE(0);
   constexpr int BQ = 128, KB = 256, NT = 256, NKS = 4, NO = 2, KW = 8;
@@ -716,7 +732,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
   const long ld = 3L * a.D;
   const int ntw = 2 * ((a.T + 63) / 64);
   const int nqt = (a.T + BQ - 1) / BQ;
-  const int n_items = BH * ((a.T + KB - 1) / KB);
+  const int nkb = (a.T + KB - 1) / KB;
+  const int n_items = CHAIN ? BH : BH * nkb;  // what the counter hands out: chains, or items
 
   char* const sQ = smem + OFF_Q;
   char* const sK = smem + OFF_K;
@@ -729,6 +746,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
   // attn_bwd_pre_kernel): a workgroup that starts late (CUs held by a concurrent kernel) takes
   // fewer.  The next item is known one item ahead, so its K / V / first-tile loads are issued
   // under the current item's last tile and epilogue instead of after them.
+  // CHAIN: the counter hands out (b, h) chains; a chain's items are (kb, bh), kb = 0, 1, ..., in
+  // the same encoding, and only a chain's last item takes its successor from the counter.
   int item = blockIdx.x;
   int bh, kb, b, hh, kb0, qt0;
   int mykey[2];
@@ -743,6 +762,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
     for (int g = 0; g < 2; ++g) mykey[g] = kb0 + 64 * w + 32 * g + l32;
   };
   setup(item);
+  // the item after the current one comes from the counter (CHAIN: else it is this chain's next block)
+  auto from_counter = [&]() {
+    if constexpr (CHAIN) return kb + 1 == nkb;
+    else return true;
+  };
 
   // K and V rows of an item, raw, by LDS-DMA into the dS^T image (K at OFF_DS, V 32 KiB on):
   // 8 rows x 128 B per instruction, 8 per wave each; rows past T read 0 (descriptor extent).  No
@@ -920,6 +944,29 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
   convert_kv();
   __syncthreads();
 
+  // One bf16 row per lane (the lane's key, or its query for the chained schedule's dQ^T) from
+  // accumulators with d = n*32 + 8*(r>>2) + 4*h32 + (r&3), as
+  // 16-byte stores (T21): the lanes l32 and l32 + 32 hold interleaved 4-column pieces of one
+  // row; one v_permlane32_swap per dword gives each the 8 contiguous columns of a 16-column step
+  // (lanes < 32: columns 16 k .. + 7, the others 16 k + 8 .. + 15): half the store instructions
+  // of the row-per-lane 8-byte form, which was store-issue bound
+  // Buffer stores through a descriptor whose extent ends with row T - 1: every lane stores (rows
+  // past T are dropped by the range check), no per-lane branch.
+  auto store_row = [&](const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, const f32x16 (&acc)[NO], float scale) {
+#pragma unroll
+    for (int n = 0; n < NO; ++n)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const f32x16& c = acc[n];
+        const uint32_t x0 = pack2(c[8 * k] * scale, c[8 * k + 1] * scale), x1 = pack2(c[8 * k + 2] * scale, c[8 * k + 3] * scale);
+        const uint32_t y0 = pack2(c[8 * k + 4] * scale, c[8 * k + 5] * scale), y1 = pack2(c[8 * k + 6] * scale, c[8 * k + 7] * scale);
+        const auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{s0[0], s1[0], s0[1], s1[1]}, rs,
+                                               voff + (uint32_t)((n * 32 + 16 * k) * 2), 0, 0);
+      }
+  };
+
   int nxt = 0, nbh = 0, nb = 0, nhh = 0, nkb0 = 0;  // the next item (valid if has_next)
   int nn_raw = 0;  // thread 0: the counter value of the item after the next one
   bool has_next = false;
@@ -1085,7 +1132,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
     // the item after the next one, fetched here (after commit's vmcnt(0)), so that its return is
     // long in by the epilogue's end, where it is published: a wait for it there would also wait
     // for every store issued before it
-    if (!more && has_next && threadIdx.x == 0) nn_raw = atomicAdd(a.work, 1);
+    if (!more && has_next && from_counter() && threadIdx.x == 0) nn_raw = atomicAdd(a.work, 1);
     BWD64_STAMP(qt - qt0, 4);
     // dQ[32 queries of subtile w][64] = dS (c K), over the keys that precede some query of it
     const int q0w = qbase + 32 * w;
@@ -1101,6 +1148,29 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
       const int kc[2] = {tr_off(8 * hh32 + 4 + trq2, trc2), tr_off(8 * hh32 + 4 + trq2, 32 + trc2)};
       f32x16 dq[NO] = {f32x16{0}, f32x16{0}};
       const char* sdSh = sdS + (w >> 1) * KB * ROWB;
+      // CHAIN: this wave's 8 KiB of the tile's running sum (fragment order), and what the earlier
+      // key blocks left there.  The loads are issued here -- after the tile's barrier and commit's
+      // vmcnt(0), never from the previous tile's issue(): at an item boundary that would put a load
+      // behind the same lane's still-draining store of the address -- and the 16 MFMA steps hide
+      // them.  sc1: served by the L2, so a line this CU read one item earlier (and this lane has
+      // rewritten since) cannot come back stale from the vector L1; 0-3 % over a plain load.  The
+      // stores are plain, not non-temporal: the lines stay in the XCD's L2 for this re-read.
+      // (Key block 0's zeros through a descriptor of extent 0 instead of the branch: 40 bytes of
+      // scratch per lane, not kept.)
+      [[maybe_unused]] f32x16 run[NO] = {f32x16{0}, f32x16{0}};
+      [[maybe_unused]] __amdgpu_buffer_rsrc_t rws;
+      if constexpr (CHAIN) {
+        const uint64_t worg = (((uint64_t)bh * nqt + qt) * 4 + w) * 8192;
+        rws = kv_rsrc(reinterpret_cast<const bf16_t*>(a.dq), worg + 8192, worg);
+        if (kb > 0) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rws, (uint32_t)(lo * 16 + i * 1024), 0, 16);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) run[i >> 2][4 * (i & 3) + j] = __uint_as_float(v[j]);
+          }
+        }
+      }
       {
         // all 16 key steps, also on diagonal tiles (the steps past the subtile's last query add
         // exact zeros; a trimmed loop of runtime length measured slower).  The fragments of step
@@ -1120,24 +1190,53 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
 #pragma unroll
         for (int kk = 0; kk < KB / 16; ++kk) {
 #pragma unroll
-          for (int n = 0; n < NO; ++n)
-            dq[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk % R], fb[kk % R][n], dq[n], 0, 0, 0);
+          for (int n = 0; n < NO; ++n) {
+            if constexpr (CHAIN)  // dQ^T: lane = query, the rows 32 columns of d
+              dq[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk % R][n], fa[kk % R], dq[n], 0, 0, 0);
+            else
+              dq[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk % R], fb[kk % R][n], dq[n], 0, 0, 0);
+          }
           if (kk + R < KB / 16) ld_step(kk + R);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       BWD64_STAMP(qt - qt0, 5);
-      // key-block partial: buffer stores through one descriptor whose extent ends at row T of
-      // this sequence (rows past it are dropped), row offsets in SGPRs
-      const uint64_t org = ((uint64_t)kb * a.dq_part + ((uint64_t)b * a.T + qbase) * a.D + (uint64_t)hh * 64) * 4;
-      const uint64_t end = ((uint64_t)kb * a.dq_part + ((uint64_t)b + 1) * a.T * a.D) * 4;
-      const __amdgpu_buffer_rsrc_t rs = kv_rsrc(reinterpret_cast<const bf16_t*>(a.dq), end, org);
+      if constexpr (CHAIN) {
+        // run + p_kb, explicit adds in ascending key-block order from run = 0: the finalize's sum.
+        // (The running sum as the MFMAs' C operand would round differently.)
+        f32x16 sum[NO];
 #pragma unroll
-      for (int n = 0; n < NO; ++n) {
-        const int voff = ((32 * w + 4 * h32) * a.D + n * 32 + l32) * 4;
+        for (int n = 0; n < NO; ++n) sum[n] = run[n] + dq[n];
+        if constexpr (DIAG) {
+          // this key block is the tile's last contributor: bf16(sum * ln2 * dscale), the finalize's
+          // product and rounding, into the Q slot; descriptor from row qbase through row T - 1
+          const uint64_t org = ((uint64_t)b * a.T + qbase) * ld * 2;
+          const __amdgpu_buffer_rsrc_t rsq = kv_rsrc(a.dqkv, org + (uint64_t)(a.T - qbase) * ld * 2, org);
+          store_row(rsq, (uint32_t)(((32 * w + (lo & 31)) * ld + hh * 64 + 8 * (lo >> 5)) * 2), sum,
+                    0.6931471805599453f * a.dscale);
+        } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dq[n][r]), rs, voff, ((r & 3) + 8 * (r >> 2)) * a.D * 4, 0);
+          for (int i = 0; i < 8; ++i) {
+            const f32x16& c = sum[i >> 2];
+            const int r = 4 * (i & 3);
+            __builtin_amdgcn_raw_buffer_store_b128(
+                u32x4_t{__float_as_uint(c[r]), __float_as_uint(c[r + 1]), __float_as_uint(c[r + 2]), __float_as_uint(c[r + 3])},
+                rws, (uint32_t)(lo * 16 + i * 1024), 0, 0);
+          }
+        }
+      } else {
+        // key-block partial: buffer stores through one descriptor whose extent ends at row T of
+        // this sequence (rows past it are dropped), row offsets in SGPRs
+        const uint64_t org = ((uint64_t)kb * a.dq_part + ((uint64_t)b * a.T + qbase) * a.D + (uint64_t)hh * 64) * 4;
+        const uint64_t end = ((uint64_t)kb * a.dq_part + ((uint64_t)b + 1) * a.T * a.D) * 4;
+        const __amdgpu_buffer_rsrc_t rs = kv_rsrc(reinterpret_cast<const bf16_t*>(a.dq), end, org);
+#pragma unroll
+        for (int n = 0; n < NO; ++n) {
+          const int voff = ((32 * w + 4 * h32) * a.D + n * 32 + l32) * 4;
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(dq[n][r]), rs, voff, ((r & 3) + 8 * (r >> 2)) * a.D * 4, 0);
+        }
       }
     }
     BWD64_STAMP(qt - qt0, 6);
@@ -1150,29 +1249,15 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
   // d = n*32 + 8*(r>>2) + 4*h32 + (r&3)
   const float sc = a.scale_log2 * 0.6931471805599453f * a.dscale;  // dscale / sqrt(hd)
   const float vs = a.thr ? a.dscale : 1.f;
-  // 16-byte stores (T21): the lanes l32 and l32 + 32 hold interleaved 4-column pieces of one key
-  // row; one v_permlane32_swap per dword gives each the 8 contiguous columns of a 16-column step
-  // (lanes < 32: columns 16 k .. + 7, the others 16 k + 8 .. + 15): half the store instructions
-  // of the row-per-lane 8-byte form, which was store-issue bound
-  // Buffer stores through a descriptor whose extent ends with row T - 1: every lane stores (rows
-  // past T are dropped by the range check), no per-lane branch.
-  auto store_row = [&](const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, const f32x16 (&acc)[NO], float scale) {
-#pragma unroll
-    for (int n = 0; n < NO; ++n)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const f32x16& c = acc[n];
-        const uint32_t x0 = pack2(c[8 * k] * scale, c[8 * k + 1] * scale), x1 = pack2(c[8 * k + 2] * scale, c[8 * k + 3] * scale);
-        const uint32_t y0 = pack2(c[8 * k + 4] * scale, c[8 * k + 5] * scale), y1 = pack2(c[8 * k + 6] * scale, c[8 * k + 7] * scale);
-        const auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{s0[0], s1[0], s0[1], s1[1]}, rs,
-                                               voff + (uint32_t)((n * 32 + 16 * k) * 2), 0, 0);
-      }
-  };
   for (;;) {
   nxt = __builtin_amdgcn_readfirstlane(*sItem);  // published by the barrier that ended the prologue
   has_next = nxt < n_items;
+  if constexpr (CHAIN) {
+    if (kb + 1 < nkb) {  // this chain's next key block; the counter's value waits in *sItem
+      nxt = item + BH;
+      has_next = true;
+    }
+  }
   nbh = nxt % BH;
   nkb0 = (nxt / BH) * KB;
   nb = nbh / a.H;
@@ -1231,7 +1316,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
     }
   }
   // the item after the next one; read after the next item's prologue barrier
-  if (threadIdx.x == 0 && has_next) *sItem = nn_raw + (int)gridDim.x;
+  if (threadIdx.x == 0 && has_next && from_counter()) *sItem = nn_raw + (int)gridDim.x;
   BWD64_PE(3);
   if (!has_next) break;
   ++bwd64_it;
@@ -1244,12 +1329,19 @@ __global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) {
   // K / V landed (and this item's stores drained).  Waiting for the DMA alone -- vmcnt(16), the
   // 16 dK / dV stores being younger -- took the transition from 6.3k to 4.0k cycles but measured
   // no faster per kernel (profiles/round6_attn_bwd64_transition_ab.txt), so the count-free wait stays.
+  // CHAIN needs it for correctness: the next key block reloads the running dQ sums this item
+  // stored, and only this wait puts every lane's stores before its own reloads.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   convert_kv();
   __syncthreads();
   }
 }
+
+// One body, two kernels (not a template: tests/test_isa_hazards.py pins the key-block kernel's
+// symbol and loop structure).
+__global__ __launch_bounds__(256, 1) void attn_bwd64_kernel(const AttnArgs a) { bwd64_body<false>(a); }
+__global__ __launch_bounds__(256, 1) void attn_bwdchain_kernel(const AttnArgs a) { bwd64_body<true>(a); }
 
 // partial mode: dqkv Q slot = bf16(scale * sum of the dQ partials of key blocks kb <= t / KB)
 __global__ __launch_bounds__(256) void attn_dq_finalize_kernel(const float* __restrict__ dq,
@@ -1298,22 +1390,47 @@ int nks_for_bwd(int hd) { return nks_for(hd); }
 
 int bwd_keys_per_block(int hd) { return nks_for_bwd(hd) > 4 ? 128 : 256; }
 
-// Key-block mode (one workgroup per (key block, b, h), heaviest key blocks first, then a finalize
-// pass over the fp32 dQ partials) by default: measured in the GPT-2 step (B=64, T=1024, hd=64;
-// profiles/round2_attn_bwd_modes.txt) it beats the persistent schedule (one workgroup per (b, h)
-// sweeping its key blocks, dQ summed in place) even where B*H fills the chip in whole rounds --
-// the in-place read-add-store of dQ costs the persistent kernel more than the finalize pass.
-// Persistent mode is used when there is a single key block (no partial sum to form).
+// Three schedules of the backward (mode 0 chooses; MINGPT_ATTN_BWD_MODE / attention_set_bwd_mode
+// force one, for tests and A/Bs):
+//  1 persistent: attn_bwd_kernel<.., true>, one workgroup per (b, h) sweeping its key blocks, dQ
+//    read-added-stored in place as dwords by 8 waves.  Chosen when there is a single key block (no
+//    sum to form).  With more key blocks it lost to key-block mode in the GPT-2 step even where B*H
+//    fills the chip in whole rounds (784 vs 639 + 122 us at B = 64, profiles/
+//    round2_attn_bwd_modes.txt): that verdict is about this kernel's in-place dQ, not about chains.
+//  2 key-block: one work item per (key block, b, h), heaviest key blocks first, an fp32 dQ partial
+//    per item and query tile, then attn_dq_finalize_kernel over the partials (at its HBM roofline:
+//    212 us per layer at B = 128, all of it traffic the result does not need).
+//  3 chained (hd = 64, more than one key block, attention_set_bwd64 on; elsewhere mode 3 means
+//    mode 0's choice): attn_bwdchain_kernel, a workgroup per (b, h) chain of key-block items with
+//    a running fp32 dQ sum in fragment order and the bf16 dQ rows stored by the last contributor
+//    (see bwd64_body).  No finalize, a workspace of one fp32 dQ instead of one per key block.
+//    Every chain is the same amount of work, so the chained kernel runs ceil(c / n) rounds of one
+//    chain time for c = B*H chains on n CUs, while key-block items spread over the CUs whatever c
+//    is: auto takes chains when their fill c / (ceil(c / n) * n) reaches kChainFill.
 // (The one-wave-per-SIMD key-block backward of round 3, 4 waves x 64 keys with the whole register
 // file, measured 1,453 vs 1,251 us at B = 128 and was removed: PERF.md, round 3.)
-int g_bwd_mode = -1;  // 0 auto, 1 force persistent, 2 force key-block (tests, MINGPT_ATTN_BWD_MODE)
+int g_bwd_mode = -1;  // 0 auto, 1 persistent, 2 key-block, 3 chained (tests, MINGPT_ATTN_BWD_MODE)
 
-bool bwd_persistent(int T, int hd) {
+// Break-even fill of the chained schedule: (chained kernel) / (key-block kernel + finalize), both
+// timed at fill 1.0 (attention_bwd, T = 1024, H = 12, p = 0.1, MI355X, 256 CUs): 1,020 vs 1,231 us at
+// B = 128 (6 rounds), 512 vs 617 us at B = 64 (3 rounds): 0.83 both times.  GPT-2 (H = 12) at any
+// multiple of B = 64 has fill 1.0; gpt2-xl (H = 25, B = 16 / 32: 400 / 800 chains, fill 0.78)
+// stays on key blocks, although a part-filled round runs faster than a full one (measured 318 vs
+// 330 us at B = 16, 623 vs 646 at B = 32): the rule is the conservative one.  B*H < n: fill
+// B*H / n, so the small shapes of the tests stay on key blocks too.  PERF.md, chained backward.
+constexpr double kChainFill = 0.83;
+
+int bwd_mode() {
   if (g_bwd_mode < 0) {
     const char* e = getenv("MINGPT_ATTN_BWD_MODE");
     g_bwd_mode = e ? atoi(e) : 0;
   }
-  if (g_bwd_mode) return g_bwd_mode == 1;
+  return g_bwd_mode;
+}
+
+bool bwd_persistent(int T, int hd) {
+  const int m = bwd_mode();
+  if (m == 1 || m == 2) return m == 1;
   return T <= bwd_keys_per_block(hd);
 }
 
@@ -1321,23 +1438,17 @@ bool bwd_persistent(int T, int hd) {
 // kernel of the same arithmetic, for a bitwise comparison)
 int g_bwd64 = -1;
 
-bool use_bwd64(const AttnArgs& a) {
+bool bwd64_on() {
   if (g_bwd64 < 0) {
     const char* e = getenv("MINGPT_ATTN_BWD64");
     g_bwd64 = e ? atoi(e) : 1;
   }
-  return g_bwd64 && a.hd == 64 && a.dq_part;
+  return g_bwd64 != 0;
 }
 
-void launch_bwd64(const AttnArgs& a, hipStream_t stream) {
-  constexpr int smem = 3 * 128 * ROWB + 256 * ROWB + 2 * 256 * ROWB + 2 * 128 * 4 + 2 * 8 * 128 * 4 + 16;
-  static_assert(smem <= 160 * 1024, "attn_bwd64_kernel LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)attn_bwd64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
-  // one workgroup per CU (the LDS holds one), each sweeping work items (attn_bwd64_kernel)
+bool use_bwd64(const AttnArgs& a) { return bwd64_on() && a.hd == 64 && a.dq_part; }
+
+int cu_count() {
   static int ncu[64] = {0};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -1347,14 +1458,42 @@ void launch_bwd64(const AttnArgs& a, hipStream_t stream) {
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     ncu[dev] = n > 0 ? n : 256;
   }
+  return ncu[dev];
+}
+
+// the chained schedule (mode 3, or auto where the chains fill the CUs in near-whole rounds)
+bool bwd_chained(int B, int T, int H, int hd) {
+  const int m = bwd_mode();
+  if ((m != 0 && m != 3) || hd != 64 || T <= 256 || !bwd64_on()) return false;
+  if (m == 3) return true;
+  const long c = (long)B * H, n = cu_count();
+  return (double)c >= kChainFill * (double)(cdiv(c, n) * n);
+}
+
+void launch_bwd64(const AttnArgs& a, hipStream_t stream, bool chained) {
+  constexpr int smem = 3 * 128 * ROWB + 256 * ROWB + 2 * 256 * ROWB + 2 * 128 * 4 + 2 * 8 * 128 * 4 + 16;
+  static_assert(smem <= 160 * 1024, "attn_bwd64_kernel LDS budget");
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)attn_bwd64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipFuncSetAttribute((const void*)attn_bwdchain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr = true;
+  }
+  // one workgroup per CU (the LDS holds one), each sweeping work items / chains (bwd64_body)
+  const int ncu = cu_count();
+  if (chained) {
+    const int chains = a.B * a.H;
+    attn_bwdchain_kernel<<<chains < ncu ? chains : ncu, 256, smem, stream>>>(a);
+    return;
+  }
   const int items = a.B * a.H * ((a.T + 255) / 256);
-  attn_bwd64_kernel<<<items < ncu[dev] ? items : ncu[dev], 256, smem, stream>>>(a);
+  attn_bwd64_kernel<<<items < ncu ? items : ncu, 256, smem, stream>>>(a);
 }
 
 template <int NKS, int KW>
 void launch_bwd(const AttnArgs& a, hipStream_t stream) {
   if constexpr (NKS == 4) {
-    if (use_bwd64(a)) return launch_bwd64(a, stream);
+    if (use_bwd64(a)) return launch_bwd64(a, stream, false);
   }
   constexpr int smem_p = bwd_smem<NKS, KW, true>(), smem_k = bwd_smem<NKS, KW, false>();
   static_assert(smem_p <= 160 * 1024 && smem_k <= 160 * 1024, "attention backward LDS budget");
@@ -1398,9 +1537,11 @@ void attention_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, con
   int lg = 0;
   while ((8 << lg) < hd) ++lg;
   const long nthreads = (long)B * T * H << lg;
+  const bool chained = bwd_chained(B, T, H, hd);  // implies use_bwd64(a)
   a.work = use_bwd64(a) ? reinterpret_cast<int*>(dq + attention_bwd_workspace_floats(B, T, H, hd) - 64) : nullptr;
   attn_bwd_pre_kernel<<<(unsigned)cdiv(nthreads, 256), 256, 0, stream>>>(dout, out, delta, B * T, T, H, hd, lg, a.work);
-  switch (nks_for(hd)) {
+  if (chained) launch_bwd64(a, stream, true);
+  else switch (nks_for(hd)) {
     case 1: launch_bwd<1, 8>(a, stream); break;
     case 2: launch_bwd<2, 8>(a, stream); break;
     case 3: launch_bwd<3, 8>(a, stream); break;
@@ -1408,7 +1549,7 @@ void attention_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, con
     case 6: launch_bwd<6, 4>(a, stream); break;
     default: launch_bwd<8, 4>(a, stream); break;
   }
-  if (!persistent) {
+  if (!persistent && !chained) {  // the chained kernel stored the bf16 dQ rows itself
     const long n8 = (long)B * T * (H * hd / 8);
     attn_dq_finalize_kernel<<<(unsigned)cdiv(n8, 256), 256, 0, stream>>>(
         dq, dqkv, B * T, H * hd, T, bwd_keys_per_block(hd), a.dq_part, 0.6931471805599453f * a.dscale);
@@ -1431,6 +1572,8 @@ void attention_bwd64_stamps(unsigned long long* host) {
 size_t attention_bwd_workspace_floats(int B, int T, int H, int hd) {
   const size_t one = (size_t)B * T * H * hd;
   if (bwd_persistent(T, hd)) return one;
+  // chained: ONE running sum, laid out by whole 128-row tiles, + the chain counter
+  if (bwd_chained(B, T, H, hd)) return (size_t)B * H * ((T + 127) / 128) * 128 * 64 + 64;
   const int kb = bwd_keys_per_block(hd);
   return one * (size_t)((T + kb - 1) / kb) + 64;  // + attn_bwd64_kernel's work counter
 }
