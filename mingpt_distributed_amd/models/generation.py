@@ -12,6 +12,11 @@ appends K/V inside the attention kernel.  CPU path: the same algorithm in plain 
 sequence outgrows ``block_size`` the window slides and the cache is rebuilt from the cropped
 context (exactly the reference's cropping semantics).
 
+GPU host code: ``_GpuCache.prefill`` and ``_GpuCache._decode`` are the two step bodies (embedding,
+``_blocks``, ``_head``).  Every device-side token loop (``step``, ``greedy``, ``sample``, ``ragged``)
+is a closure around ``_decode`` that ends with the loop's own tail, driven by one ``_Loop`` (eager
+warm-up, capture once as a hipGraph, replay); the loops of a state live in ``_GpuCache._loops``.
+
 Sampling: ``seed=None`` is the reference's recipe on torch's global generator (``_sample``).  With a
 seed the draw is counter-based Gumbel-max (``ops.reference.sample_gumbel``; on the GPU the sample
 kernel inside a device-side token loop, ``_GpuCache.sample``): reproducible per (seed, column, row).
@@ -41,10 +46,7 @@ def _sample(logits, temperature, do_sample, top_k):
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
         logits[logits < v[:, [-1]]] = -float("Inf")
     probs = F.softmax(logits, dim=-1)
-    if do_sample:
-        return torch.multinomial(probs, num_samples=1)
-    _, idx_next = torch.topk(probs, k=1, dim=-1)
-    return idx_next
+    return torch.multinomial(probs, num_samples=1)
 
 
 # ------------------------------------------------------------------------------------ CPU
@@ -52,47 +54,42 @@ class _CpuCache:
     def __init__(self, model, idx):
         self.model = model
         self.k, self.v = [], []
-        self.logits = self._prefill(idx)
+        tr = model.transformer
 
-    def _prefill(self, idx):
-        m = self.model
-        tr = m.transformer
-        B, T = idx.shape
-        x = tr.wte.weight[idx] + tr.wpe.weight[:T]
-        for blk in tr.h:
-            h = blk.ln_1(x)
-            C = x.shape[-1]
-            q, k, v = F.linear(h, blk.attn.c_attn.weight, blk.attn.c_attn.bias).split(C, dim=2)
-            H = m.config.n_head
-            f = lambda t: t.view(B, T, H, C // H).transpose(1, 2)
-            q, k, v = f(q), f(k), f(v)
+        def attend(i, q, k, v):  # the whole prompt at once: layer i's keys / values start here
             self.k.append(k)
             self.v.append(v)
-            y = R.causal_attention(q, k, v, 0.0, False).transpose(1, 2).reshape(B, T, C)
+            return R.causal_attention(q, k, v, 0.0, False)
+
+        self.logits = self._body(tr.wte.weight[idx] + tr.wpe.weight[:idx.size(1)], attend)
+
+    def _body(self, x, attend):
+        """Last-position logits of the blocks and the LM head on x [B, T, C]; layer i's attention
+        output is ``attend(i, q, k, v)`` ([B, H, T, hd] each)."""
+        m = self.model
+        tr = m.transformer
+        B, T, C = x.shape
+        H = m.config.n_head
+        f = lambda t: t.view(B, T, H, C // H).transpose(1, 2)
+        for i, blk in enumerate(tr.h):
+            h = blk.ln_1(x)
+            q, k, v = F.linear(h, blk.attn.c_attn.weight, blk.attn.c_attn.bias).split(C, dim=2)
+            y = attend(i, f(q), f(k), f(v)).transpose(1, 2).reshape(B, T, C)
             x = x + F.linear(y, blk.attn.c_proj.weight, blk.attn.c_proj.bias)
             x = x + blk.mlp(blk.ln_2(x))
         return m.lm_head(tr.ln_f(x[:, -1]))
 
     def step(self, tok, pos):
-        m = self.model
-        tr = m.transformer
-        B = tok.shape[0]
-        x = tr.wte.weight[tok[:, 0]] + tr.wpe.weight[pos]
-        x = x.unsqueeze(1)
-        H = m.config.n_head
-        for i, blk in enumerate(tr.h):
-            h = blk.ln_1(x)
-            C = x.shape[-1]
-            q, k, v = F.linear(h, blk.attn.c_attn.weight, blk.attn.c_attn.bias).split(C, dim=2)
-            f = lambda t: t.view(B, 1, H, C // H).transpose(1, 2)
-            q, k, v = f(q), f(k), f(v)
+        tr = self.model.transformer
+
+        def attend(i, q, k, v):  # one new token against the layer's cached keys / values
             self.k[i] = torch.cat([self.k[i], k], dim=2)
             self.v[i] = torch.cat([self.v[i], v], dim=2)
-            att = (q @ self.k[i].transpose(-1, -2)) / (C // H) ** 0.5
-            y = (F.softmax(att, dim=-1) @ self.v[i]).transpose(1, 2).reshape(B, 1, C)
-            x = x + F.linear(y, blk.attn.c_proj.weight, blk.attn.c_proj.bias)
-            x = x + blk.mlp(blk.ln_2(x))
-        return m.lm_head(tr.ln_f(x[:, -1]))
+            att = (q @ self.k[i].transpose(-1, -2)) / q.size(-1) ** 0.5
+            return F.softmax(att, dim=-1) @ self.v[i]
+
+        x = tr.wte.weight[tok[:, 0]] + tr.wpe.weight[pos]
+        return self._body(x.unsqueeze(1), attend)
 
 
 # ------------------------------------------------------------------------------------ GPU
@@ -138,9 +135,36 @@ def _capture(fn):
     return graph, out
 
 
+_GRAPH_DECODE = True  # set False to launch the decode step eagerly
+
+
+class _Loop:
+    """One device-side token loop: ``step()`` launches one decode step on persistent device
+    buffers (``state``, kept here for the loop's owner) that its own kernels advance, and returns
+    the step's logits.  Decoding is launch-bound (B rows through ~5 kernels per layer), so the step
+    is captured once as a hipGraph and the replays are queued back to back without a host round
+    trip.  ``warm`` (default: ``step``) runs once, eagerly, when the loop is built: workspaces and
+    lazy kernel attributes are set up outside the capture."""
+
+    def __init__(self, step, state, warm=None):
+        self.step, self.state = step, state
+        self.graph = self.logits = None
+        (warm or step)()
+
+    def run(self, n):
+        """n steps; ``logits`` is the last step's (a buffer the replays rewrite)."""
+        if _GRAPH_DECODE and self.graph is None:
+            self.graph, self.logits = _capture(self.step)
+        for _ in range(n):
+            if _GRAPH_DECODE:
+                self.graph.replay()
+            else:
+                self.logits = self.step()
+
+
 class _GpuCache:
-    """KV caches ([B, Tmax, 3D] qkv rows per layer) plus the captured decode steps of one model at
-    one batch size.  Kept on the model across ``generate`` calls (``_gpu_cache``): a later call
+    """KV caches ([B, Tmax, 3D] qkv rows per layer) plus the captured decode steps (``_loops``) of
+    one model at one batch size.  Kept on the model across ``generate`` calls (``_gpu_cache``): a later call
     with the same batch re-prefills into the same buffers and replays the same hipGraphs, unless
     a weight changed storage or version since the capture (then the graphs are re-captured)."""
 
@@ -165,183 +189,190 @@ class _GpuCache:
                                     device=idx.device, dtype=torch.float32)
         self.dec_cnt = torch.zeros(B * H, device=idx.device, dtype=torch.int32)
         self.stamp = _weight_stamp(model)
-        self.logits = self._run(idx, 0, last=last)
+        self._loops = {}  # the device-side token loops (_Loop) by name, built on first use
+        self.prefill(idx, last)
+
+    def _lin(self, skinny, inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
+        """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first (fused into
+        the skinny GEMM's staging at decode time)."""
+        C, G, bf = self.C, self.G, self.bf
+        eps = self.model.config.layer_norm_eps
+        if skinny:
+            code = {"none": 0, "bias": 1, "gelu": 2, "resid": 3}[epi]
+            lw, lb = (bf(ln.weight), bf(ln.bias)) if ln is not None else (None, None)
+            if am is not None:
+                return C.gemv(inp, bf(w), code, None, None, ld, lw, lb, eps, am[0], am[1])
+            return C.gemv(inp, bf(w), code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
+        if ln is not None:
+            inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
+        if epi == "gelu":
+            pre = torch.empty((inp.shape[0], w.shape[0]), dtype=torch.bfloat16, device=inp.device)
+            return G.gemm_nt(inp, bf(w), bias=bf(b), epi="gelu", pre_out=pre)
+        return G.gemm_nt(inp, bf(w), bias=bf(b) if b is not None else None, epi=epi, resid=resid,
+                         ld=ld or None)
+
+    def _blocks(self, x, attend, skinny):
+        """The transformer blocks on rows x [M, D]; ``attend(i, qkv)`` is layer i's attention on its
+        qkv projection [M, 3D], cache update included.  ``skinny``: the projections go through
+        the skinny GEMM (gemv.hip) instead of the MFMA GEMM."""
+        for i, blk in enumerate(self.model.transformer.h):
+            a, mm = blk.attn, blk.mlp
+            qkv = self._lin(skinny, x, a.c_attn.weight, a.c_attn.bias, "bias", ln=blk.ln_1)
+            y = attend(i, qkv)
+            x = self._lin(skinny, y, a.c_proj.weight, a.c_proj.bias, "resid", resid=x)
+            u = self._lin(skinny, x, mm.c_fc.weight, mm.c_fc.bias, "gelu", ln=blk.ln_2)
+            x = self._lin(skinny, u, mm.c_proj.weight, mm.c_proj.bias, "resid", resid=x)
+        return x
+
+    def _head(self, x_last, skinny, am=None):
+        """ln_f and the LM head on x_last [B, D]: logits [B, ld], ld = V rounded up to 8 (the
+        columns from V on are padding).  ``am`` = (part, pos): see ``_decode``."""
+        m = self.model
+        V = m.config.vocab_size
+        return self._lin(skinny, x_last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8,
+                         ln=m.transformer.ln_f, am=am)
 
     def prefill(self, idx, last=None):
-        self.logits = self._run(idx, 0, last=last)
+        """Run the prompt idx [B, T] on the MFMA GEMM path, keep every layer's qkv rows as the
+        cache and set ``logits`` [B, V] to the last position's -- or, for a right-padded batch, to
+        those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
+        C, bf = self.C, self.bf
+        tr, cfg = self.model.transformer, self.model.config
+        B, T = idx.shape
+        D, H = cfg.n_embed, cfg.n_head
+        x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0).view(B * T, D)
+
+        def attend(i, qkv):
+            self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
+            return C.attention_fwd(qkv, B, T, H, 0.0, 0)[0]
+
+        x = self._blocks(x, attend, False).view(B, T, D)
+        if last is not None:  # right-padded prefill: row b's hidden state at its own last token
+            x = x[torch.arange(B, device=x.device), last]
+        else:
+            x = x[:, -1]
+        self.logits = self._head(x.contiguous(), False)[:, :cfg.vocab_size]
         return self.logits
 
-    def _run(self, idx, pos0, pos_dev=None, greedy=None, sample=None, last=None, ragged=None):
-        """Prefill (pos0 == 0) or one decode step at position pos0 (or at ``pos_dev[0]``, an int32
-        device scalar, when captured in a hipGraph).  ``greedy`` = (tok [B, 1] int64, pos_dev,
-        seq [B, Tmax + 1] int64, part [B, G] int64 or None): the step needs nothing from the host.
-        With ``part`` (LM head on the skinny GEMM, V > 8192) the LM-head kernel leaves one argmax
-        key per (row, workgroup) in part and advances pos_dev, and the NEXT step's embedding
-        kernel reduces the keys into its input token (also written to tok and seq[:, pos]) --
-        no cross-workgroup hand-off inside a kernel.  Without it the argmax runs in torch and
-        writes tok and seq[:, pos + 1] itself.  ``sample`` = (tok, pos_dev, seq, params): the
-        sample kernel (sample.hip) draws tok and seq[:, pos + 1] from this step's logits by the
-        device parameter block ``params`` and advances pos_dev and the draw counter.
-        ``last`` (prefill of a right-padded batch): int64 [B], the column whose logits row b
-        returns (its length - 1) instead of the last one.  ``ragged`` = (state, greedy): a decode
-        step of a ragged batch -- ``pos_dev`` is the state's int32 [B], row b embeds its token at
-        ``pos[b]``, appends K/V at and attends up to its own cache row, and the pick kernel
-        (``pick_ragged``) ends the step per row (``_GpuCache.ragged``)."""
-        C, G, bf = self.C, self.G, self.bf
-        m = self.model
-        tr, cfg = m.transformer, m.config
-        B, T = idx.shape
-        D, H, eps = cfg.n_embed, cfg.n_head, cfg.layer_norm_eps
-        wpe = bf(tr.wpe.weight)
+    def _decode(self, tok, pos, hpos, pos_stride=0, am_part=None, seq=None):
+        """One decode step, with nothing from the host: embed token ``tok`` [B, 1] (int64, on the
+        device) at position ``pos`` (int32 on the device: [1], or with ``pos_stride`` 1 one per
+        row, [B]), run the blocks -- each row appends its K/V at and attends up to its own cache
+        row -- and return the LM head's padded logits [B, ld].  ``hpos``: a host-side position for
+        the decode-attention binding's range check (the kernel reads ``pos``).
+
+        ``am_part`` (int64 [B, G]; LM head on the skinny GEMM, V > 8192) fuses the greedy argmax:
+        the LM-head kernel leaves one argmax key per (row, workgroup) in it and advances ``pos``,
+        and the NEXT step's embedding kernel reduces the keys into its input token, which it also
+        writes to ``tok`` and ``seq[:, pos]`` -- no cross-workgroup hand-off inside a kernel."""
+        C, bf = self.C, self.bf
+        tr, cfg = self.model.transformer, self.model.config
+        B, D, H = tok.shape[0], cfg.n_embed, cfg.n_head
         # decode rows (B <= 8) go through the skinny GEMM (gemv.hip): at M = B the MFMA GEMM has
-        # one row tile and walks K latency-bound; prefill uses the MFMA GEMM
-        skinny = pos0 > 0 and C.gemv_supported(B * T, 4 * D)
-        V = cfg.vocab_size
-        part = greedy[3] if greedy is not None else None
-        if part is not None:  # fused greedy: the token is the argmax of the previous LM head
-            x = C.embedding_fwd(idx, bf(tr.wte.weight), wpe, 0.0, 0, pos_dev, part,
-                                greedy[2]).view(B * T, D)
-        elif pos0 == 0:
-            x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0).view(B * T, D)
-        elif ragged is not None:  # one position per row, picked on the device
-            x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0, pos_dev,
-                                pos_stride=1).view(B * T, D)
-        elif pos_dev is not None:  # the position row is picked on the device (one kernel)
-            x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe, 0.0, 0, pos_dev).view(B * T, D)
-        else:  # single token at position pos0
-            x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), wpe[pos0:pos0 + 1], 0.0, 0).view(B * T, D)
-
-        def lin(inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
-            """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first (fused into
-            the skinny GEMM's staging at decode time)."""
-            if skinny:
-                code = {"none": 0, "bias": 1, "gelu": 2, "resid": 3}[epi]
-                lw, lb = (bf(ln.weight), bf(ln.bias)) if ln is not None else (None, None)
-                if am is not None:
-                    return C.gemv(inp, bf(w), code, None, None, ld, lw, lb, eps, am[0], am[1])
-                return C.gemv(inp, bf(w), code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
-            if ln is not None:
-                inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
-            if epi == "gelu":
-                pre = torch.empty((inp.shape[0], w.shape[0]), dtype=torch.bfloat16, device=inp.device)
-                return G.gemm_nt(inp, bf(w), bias=bf(b), epi="gelu", pre_out=pre)
-            return G.gemm_nt(inp, bf(w), bias=bf(b) if b is not None else None, epi=epi, resid=resid,
-                             ld=ld or None)
-
-        for i, blk in enumerate(tr.h):
-            a, mm = blk.attn, blk.mlp
-            qkv = lin(x, a.c_attn.weight, a.c_attn.bias, "bias", ln=blk.ln_1)
-            if pos0 == 0:
-                self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
-                y, _, _ = C.attention_fwd(qkv, B, T, H, 0.0, 0)
-            elif ragged is not None:
-                y = C.attention_decode(qkv, self.caches[i], H, pos0, pos_dev, self.dec_part, self.dec_cnt,
-                                       pos_stride=1)
-            else:
-                y = C.attention_decode(qkv, self.caches[i], H, pos0, pos_dev, self.dec_part, self.dec_cnt)
-            x = lin(y, a.c_proj.weight, a.c_proj.bias, "resid", resid=x)
-            u = lin(x, mm.c_fc.weight, mm.c_fc.bias, "gelu", ln=blk.ln_2)
-            x = lin(u, mm.c_proj.weight, mm.c_proj.bias, "resid", resid=x)
-        if last is not None:  # right-padded prefill: row b's hidden state at its own last token
-            last = x.view(B, T, D)[torch.arange(B, device=x.device), last].contiguous()
-        else:
-            last = x.view(B, T, D)[:, -1].contiguous()
-        am = (part, pos_dev) if part is not None else None
-        logits = lin(last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8, ln=tr.ln_f, am=am)
-        if greedy is not None and part is None:  # small vocab (no fused argmax): same in torch
-            tok, pd, seq, _ = greedy
-            nxt = logits[:, :V].argmax(-1)
-            tok.view(B).copy_(nxt)
-            seq.index_copy_(1, (pd.long() + 1), nxt.view(B, 1))
-            pd.add_(1)
-        if sample is not None:
-            tok, pd, seq, params = sample
-            C.sample_logits(logits, V, params, pd, tok, seq)
-        if ragged is not None:
-            st, rg = ragged
-            C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], rg)
-        return logits[:, :V]
+        # one row tile and walks K latency-bound
+        skinny = C.gemv_supported(B, 4 * D)
+        x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
+                            pos_stride).view(B, D)
+        x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part,
+                                                              self.dec_cnt, pos_stride), skinny)
+        return self._head(x, skinny, am=(am_part, pos) if am_part is not None else None)
 
     def _fresh(self):
         st = _weight_stamp(self.model)
         if st != self.stamp:  # a weight moved or changed: captured pointers / bf16 copies are stale
             self.stamp = st
-            self.__dict__.pop("_graph", None)
-            self.__dict__.pop("_ggraph", None)
-            self.__dict__.pop("_sgraph", None)
-            self.__dict__.pop("_rgraph", None)
+            self._loops.clear()
+
+    def _loop(self, key, make):
+        """The loop kept under ``key``; ``make()`` builds it on first use and again after a weight
+        change, which drops every loop with its graph and buffers."""
+        self._fresh()
+        if key not in self._loops:
+            self._loops[key] = make()
+        return self._loops[key]
+
+    @staticmethod
+    def _seed(st, tok, pos):
+        """Point a rectangular loop's device state at token ``tok`` [B, 1] at position ``pos``."""
+        st["tok"].copy_(tok)
+        st["pos"].fill_(pos)
+        st["hpos"] = max(pos, 1)
 
     def step(self, tok, pos):
-        """One decode step.  Decoding is launch-bound (B rows through ~5 kernels per layer), so
-        the step is captured once as a hipGraph over static token / position buffers and
-        replayed; the KV caches are persistent buffers the captured kernels append to."""
-        if not _GRAPH_DECODE:
-            return self._run(tok, pos)
-        self._fresh()
-        g = getattr(self, "_graph", None)
-        if g is None:
-            g = self._graph = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32,
-                                                                     device=tok.device)}
-            self._run(g["tok"], pos, g["pos"])  # warm-up (workspaces, lazy kernel attributes)
-            g["graph"], g["logits"] = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"]))
-        g["tok"].copy_(tok)
-        g["pos"].fill_(pos)
-        g["graph"].replay()
-        return g["logits"]
+        """One decode step with token ``tok`` [B, 1] at position ``pos``, over static token /
+        position buffers; the KV caches are persistent buffers the kernels append to.  Returns
+        the logits [B, V]."""
+        V = self.model.config.vocab_size
+
+        def make():
+            st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=tok.device),
+                  "hpos": max(pos, 1)}
+            return _Loop(lambda: self._decode(st["tok"], st["pos"], st["hpos"])[:, :V], st)
+
+        lp = self._loop("step", make)
+        self._seed(lp.state, tok, pos)
+        lp.run(1)
+        return lp.logits
 
     def greedy(self, tok, pos, n):
-        """n greedy decode steps starting with token ``tok`` [B, 1] at position ``pos``: the captured
-        step takes its input token and position from device buffers that its own kernels advance
-        (fused argmax, see ``_run``), so the n replays are queued back to back without a host round
-        trip.  Returns the n new tokens [B, n] (positions pos + 1 .. pos + n)."""
+        """n greedy decode steps starting with token ``tok`` [B, 1] at position ``pos``: the step
+        takes its input token and position from device buffers that its own kernels advance (the
+        fused argmax of ``_decode``; for a small vocabulary the argmax in torch).  Returns the n
+        new tokens [B, n] (positions pos + 1 .. pos + n)."""
         assert pos + n <= self.tmax
         B = tok.shape[0]
-        self._fresh()
-        g = getattr(self, "_ggraph", None)
         cfg = self.model.config
-        fused = self.C.gemv_supported(B, 4 * cfg.n_embed) and cfg.vocab_size > 8192
-        if g is None:
+        V = cfg.vocab_size
+
+        def seed(st):
+            self._seed(st, tok, pos)
+            if st["part"] is not None:  # keys that every real logit loses to, argmax = tok
+                st["part"].zero_()
+                st["part"][:, :1].copy_(-1 - tok)  # bits 0xffffffff_(0xffffffff - tok)
+
+        def make():
             dev = tok.device
-            g = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
-                 "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
-                 "part": (torch.zeros(B, self.C.gemv_argmax_groups(cfg.vocab_size, B), dtype=torch.long,
-                                      device=dev) if fused else None)}
-            self._ggraph = g  # workspaces are allocated outside the capture (eager warm-up step)
-            self._greedy_seed(g, tok, pos)
-            self._run(g["tok"], max(pos, 1), g["pos"], (g["tok"], g["pos"], g["seq"], g["part"]))
-        if _GRAPH_DECODE and "graph" not in g:
-            g["graph"], _ = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"],
-                                                       (g["tok"], g["pos"], g["seq"], g["part"])))
-        self._greedy_seed(g, tok, pos)
-        for _ in range(n):
-            if _GRAPH_DECODE:
-                g["graph"].replay()
-            else:
-                self._run(g["tok"], max(pos, 1), g["pos"], (g["tok"], g["pos"], g["seq"], g["part"]))
-        if g["part"] is None:
-            return g["seq"][:, pos + 1:pos + 1 + n]
+            fused = self.C.gemv_supported(B, 4 * cfg.n_embed) and V > 8192
+            st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
+                  "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
+                  "part": (torch.zeros(B, self.C.gemv_argmax_groups(V, B), dtype=torch.long, device=dev)
+                           if fused else None)}
+            seed(st)
+            if fused:
+                return _Loop(lambda: self._decode(st["tok"], st["pos"], st["hpos"], am_part=st["part"],
+                                                  seq=st["seq"])[:, :V], st)
+
+            def step():  # small vocab (no fused argmax): the same in torch
+                logits = self._decode(st["tok"], st["pos"], st["hpos"])[:, :V]
+                nxt = logits.argmax(-1)
+                st["tok"].view(B).copy_(nxt)
+                st["seq"].index_copy_(1, st["pos"].long() + 1, nxt.view(B, 1))
+                st["pos"].add_(1)
+                return logits
+
+            return _Loop(step, st)
+
+        lp = self._loop("greedy", make)
+        st = lp.state
+        seed(st)  # again: the warm-up step moved the state
+        lp.run(n)
+        if st["part"] is None:
+            return st["seq"][:, pos + 1:pos + 1 + n]
         # the last step's token is still in its LM-head keys: reduce them here (unsigned max =
         # signed max after flipping the top bit; low word = 0xffffffff - column)
-        k = (g["part"] ^ _I64_MIN).max(dim=1).values ^ _I64_MIN
+        k = (st["part"] ^ _I64_MIN).max(dim=1).values ^ _I64_MIN
         last = 0xFFFFFFFF - (k & 0xFFFFFFFF)
-        return torch.cat([g["seq"][:, pos + 1:pos + n], last.view(B, 1)], dim=1)
+        return torch.cat([st["seq"][:, pos + 1:pos + n], last.view(B, 1)], dim=1)
 
     def _sample_params(self, words):
-        """The device parameter block of the sample kernel (one per decode state: the captured
-        step bakes its pointer in), set to ``words`` (``_sample_words``)."""
+        """The device parameter block of the sample kernel, owned by the sampled loop (its
+        captured step bakes the pointer in) and used by ``sample_prefill``, set to ``words``
+        (``_sample_words``)."""
         p = self.__dict__.get("_sparams")
         if p is None:
             p = self._sparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
         p.copy_(torch.tensor(words, dtype=torch.int32))
-        self._rwords = None  # the sampler's advance kernel moves the draw counter: nothing to reuse
         return p
-
-    def _ragged_params(self, st, words):
-        """Set the parameter block for the ragged loop, which only reads it: an unchanged block is
-        not uploaded again (a host-to-device copy waits for the queued replays to drain)."""
-        if self.__dict__.get("_rwords") != list(words):
-            st["params"].copy_(torch.tensor(words, dtype=torch.int32))
-            self._rwords = list(words)
 
     def sample_prefill(self, words):
         """The token [B] drawn from the prefill logits (the first token of a context window)."""
@@ -352,38 +383,38 @@ class _GpuCache:
         is the plain LM head followed by the sample kernel, which writes the next token into the
         buffer the next step's embedding reads and advances the device position and draw counter.
         Seed, temperature and top-k live in the device parameter block (``words``), so the one
-        captured step serves every call; the n replays are queued back to back without a host
-        round trip.  Returns the n new tokens [B, n] (positions pos + 1 .. pos + n)."""
+        captured step serves every call.  Returns the n new tokens [B, n] (positions pos + 1 ..
+        pos + n)."""
         assert pos + n <= self.tmax
         B = tok.shape[0]
-        self._fresh()
-        g = getattr(self, "_sgraph", None)
-        if g is None:
+        V = self.model.config.vocab_size
+
+        def make():
             dev = tok.device
-            g = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
-                 "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev)}
-            self._sgraph = g  # workspaces are allocated outside the capture (eager warm-up step)
-            g["params"] = self._sample_params(words)
-            self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
-        if _GRAPH_DECODE and "graph" not in g:
-            g["graph"], _ = _capture(lambda: self._run(g["tok"], max(pos, 1), g["pos"],
-                                                       sample=(g["tok"], g["pos"], g["seq"], g["params"])))
-        g["tok"].copy_(tok)
-        g["pos"].fill_(pos)
+            st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
+                  "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev), "hpos": max(pos, 1)}
+            params = self._sample_params(words)
+
+            def step():
+                logits = self._decode(st["tok"], st["pos"], st["hpos"])
+                self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"])
+                return logits[:, :V]
+
+            return _Loop(step, st)
+
+        lp = self._loop("sample", make)
+        self._seed(lp.state, tok, pos)
         self._sample_params(words)
-        for _ in range(n):
-            if _GRAPH_DECODE:
-                g["graph"].replay()
-            else:
-                self._run(g["tok"], max(pos, 1), g["pos"], sample=(g["tok"], g["pos"], g["seq"], g["params"]))
-        return g["seq"][:, pos + 1:pos + 1 + n]
+        lp.run(n)
+        return lp.state["seq"][:, pos + 1:pos + 1 + n]
 
     # ----------------------------------------------------------------- ragged batches
     def ragged_state(self):
         """The per-row device state of the ragged loop, allocated once per decode state (the
-        captured step bakes the pointers in): ``pos`` int32 [B] (position of the row's newest
-        token), ``done`` int32 [B], ``tok`` int64 [B, 1] (the newest token, the next step's input),
-        ``seq`` int64 [B, tmax + 1] and the sample parameter block ``params``."""
+        captured steps bake the pointers in, and it outlives them): ``pos`` int32 [B] (position of
+        the row's newest token), ``done`` int32 [B], ``tok`` int64 [B, 1] (the newest token, the
+        next step's input), ``seq`` int64 [B, tmax + 1] and the pick kernels' own parameter block
+        ``params``."""
         st = self.__dict__.get("_rstate")
         if st is None:
             dev, B = self.caches[0].device, self.B
@@ -391,8 +422,17 @@ class _GpuCache:
                                  "done": torch.zeros(B, dtype=torch.int32, device=dev),
                                  "tok": torch.zeros(B, 1, dtype=torch.long, device=dev),
                                  "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
-                                 "params": self._sample_params([0] * 8)}
+                                 "params": torch.zeros(8, dtype=torch.int32, device=dev)}
+            self._rwords = None  # the words last uploaded to params (_ragged_params)
         return st
+
+    def _ragged_params(self, st, words):
+        """Set the ragged parameter block, which the pick kernels only read and nothing else
+        writes: an unchanged block is not uploaded again (a host-to-device copy waits for the
+        queued replays to drain)."""
+        if self._rwords != list(words):
+            st["params"].copy_(torch.tensor(words, dtype=torch.int32))
+            self._rwords = list(words)
 
     def ragged_start(self, idx, lengths, words, greedy):
         """Point the ragged state at a prefilled right-padded batch ``idx`` [B, Tp] with ``lengths``
@@ -416,41 +456,26 @@ class _GpuCache:
         writes the row's next token and advances its position, or leaves a finished row alone.  A
         finished row keeps flowing through the step with its token and position frozen (it re-embeds
         the same token and rewrites the same cache row), so the launch shapes never change: one
-        captured graph per mode (``_rgraph[greedy]``), replayed back to back with no host round
-        trip.  Resumable: n calls of one step equal one call of n steps.  ``words``: the parameter
-        block (``_ragged_words``).  Returns the state; the last step's logits are
-        ``_rgraph[greedy]["logits"]``."""
-        self._fresh()
+        loop per mode (``_loops[("ragged", greedy)]``).  Resumable: n calls of one step equal one
+        call of n steps.  ``words``: the parameter block (``_ragged_words``).  Returns the state;
+        the last step's logits are the loop's ``logits``."""
         st = self.ragged_state()
         self._ragged_params(st, words)
-        gs = self.__dict__.setdefault("_rgraph", {})
-        g = gs.get(greedy)
-        run = lambda: self._run(st["tok"], 1, st["pos"], ragged=(st, greedy))
-        if g is None:
-            # eager warm-up (workspaces, lazy kernel attributes) with every row marked finished:
-            # the step is idempotent then, so the state the caller set up is left as it is
-            g = gs[greedy] = {}
-            done = st["done"].clone()
-            st["done"].fill_(1)
-            run()
-            st["done"].copy_(done)
-        if _GRAPH_DECODE and "graph" not in g:
-            g["graph"], g["logits"] = _capture(run)
-        for _ in range(n):
-            if _GRAPH_DECODE:
-                g["graph"].replay()
-            else:
-                g["logits"] = run()
-        return st
+        V = self.model.config.vocab_size
 
-    @staticmethod
-    def _greedy_seed(g, tok, pos):
-        """Point the greedy loop's device state at token ``tok`` [B, 1] at position ``pos``."""
-        g["tok"].copy_(tok)
-        g["pos"].fill_(pos)
-        if g["part"] is not None:  # keys that every real logit loses to, argmax = tok
-            g["part"].zero_()
-            g["part"][:, :1].copy_(-1 - tok)  # bits 0xffffffff_(0xffffffff - tok)
+        def step():
+            logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
+            self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy)
+            return logits[:, :V]
+
+        def warm():  # with every row marked finished the step is idempotent: the state the caller
+            done = st["done"].clone()  # set up is left as it is
+            st["done"].fill_(1)
+            step()
+            st["done"].copy_(done)
+
+        self._loop(("ragged", greedy), lambda: _Loop(step, st, warm)).run(n)
+        return st
 
 
 _I64_MIN = -(1 << 63)
@@ -487,9 +512,6 @@ def _gpu_cache(model, idx, tmax, last=None):
     return c
 
 
-_GRAPH_DECODE = True  # set False to launch the decode step eagerly
-
-
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None):
@@ -519,9 +541,12 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             idx = torch.cat((idx, pick(logits[:, -1, :], idx.size(1))), dim=1)
         return idx
     if idx.is_cuda and not do_sample and max_new_tokens > 0:
-        return _generate_greedy_gpu(model, idx, max_new_tokens)
-    if idx.is_cuda and seeded and max_new_tokens > 0:
-        return _generate_sample_gpu(model, idx, max_new_tokens, temperature, top_k, seed)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.logits.argmax(-1),
+                                      lambda c, tok, L, n, T: c.greedy(tok, L, n))
+    if idx.is_cuda and seeded and max_new_tokens > 0:  # the draw counter of a token is its column T
+        words = lambda T: _sample_words(seed, T, temperature, top_k)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.sample_prefill(words(T)),
+                                      lambda c, tok, L, n, T: c.sample(tok, L, n, words(T)))
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
@@ -540,11 +565,14 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     return idx
 
 
-def _generate_greedy_gpu(model, idx, max_new_tokens):
-    """Greedy decode on the GPU: one prefill per context window, then the device-side token loop
-    (``_GpuCache.greedy``) for every position the window still has room for.  Once the sequence
-    outgrows block_size, each token is a fresh prefill of the last block_size tokens -- the
-    reference's crop-every-step semantics (``/root/reference/mingpt/model.py:333``)."""
+def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop):
+    """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
+    window's first token ``first(cache, T)`` [B], then the device-side token loop ``loop(cache,
+    tok, L, n, T)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
+    position ``L``) for every position the window still has room for.  ``T`` is the column of the
+    call's first token in the returned sequence.  Once the sequence outgrows block_size, each token
+    is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
+    (``/root/reference/mingpt/model.py:333``)."""
     bs = model.block_size
     B, T0 = idx.shape
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
@@ -554,34 +582,11 @@ def _generate_greedy_gpu(model, idx, max_new_tokens):
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
         cache = _gpu_cache(model, ctx, bs)
-        out[:, T] = cache.logits.argmax(-1)
+        out[:, T] = first(cache, T)
         T += 1
         n = min(end - T, bs - L)
         if n > 0:
-            out[:, T:T + n] = cache.greedy(out[:, T - 1:T], L, n)
-            T += n
-    return out
-
-
-def _generate_sample_gpu(model, idx, max_new_tokens, temperature, top_k, seed):
-    """Seeded sampling on the GPU, the host glue of ``_generate_greedy_gpu``: one prefill per context
-    window whose logits give the window's first token (the sample kernel), then the device-side
-    token loop (``_GpuCache.sample``) for every position the window still has room for.  The draw
-    counter of a token is its column in the returned sequence."""
-    bs = model.block_size
-    B, T0 = idx.shape
-    out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
-    out[:, :T0] = idx
-    T, end = T0, T0 + max_new_tokens
-    while T < end:
-        ctx = out[:, max(0, T - bs):T]
-        L = ctx.size(1)
-        cache = _gpu_cache(model, ctx, bs)
-        out[:, T] = cache.sample_prefill(_sample_words(seed, T, temperature, top_k))
-        T += 1
-        n = min(end - T, bs - L)
-        if n > 0:
-            out[:, T:T + n] = cache.sample(out[:, T - 1:T], L, n, _sample_words(seed, T, temperature, top_k))
+            out[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
             T += n
     return out
 

@@ -78,7 +78,7 @@ def _drive(model, prompts, n, greedy, bs=BS, seed=SEED):
         for _ in range(n):
             pos_in, tok_in = st["pos"].cpu().long(), st["tok"].view(-1).cpu()
             cache.ragged(1, words, greedy)
-            rec.append(dict(logits=cache._rgraph[greedy]["logits"].float().cpu(), pos_in=pos_in, tok_in=tok_in,
+            rec.append(dict(logits=cache._loops[("ragged", greedy)].logits.float().cpu(), pos_in=pos_in, tok_in=tok_in,
                             tok_out=st["tok"].view(-1).cpu()))
         final = {k: st[k].clone() for k in ("seq", "pos", "done")}
     return rec, final
@@ -151,6 +151,11 @@ def test_equal_lengths_reduce_to_generate(vocab, kw):
     assert torch.equal(tokens, want) and lengths.tolist() == [47] * 3
     tokens2, _ = generate_batch(model, (idx, torch.full((3,), 7)), 40, **kw)
     assert torch.equal(tokens2, want)
+    # ragged, then the rectangular loop, then ragged again with unchanged words: each loop has its
+    # own parameter block, and the ragged one is not uploaded again
+    assert torch.equal(model.generate(idx, 40, **kw), want)
+    tokens3, _ = model.generate_batch(list(idx), 40, **kw)
+    assert torch.equal(tokens3, want)
 
 
 # ------------------------------------------------------------------ 2. the pick follows the rule
@@ -208,7 +213,7 @@ def test_loop_equals_steps(driven, monkeypatch):
         cache, st, _ = _start(model, prompts, words, greedy, BS)
         cache.ragged(STEPS - 7, words, greedy)
         cache.ragged(7, words, greedy)
-        assert "graph" not in cache._rgraph[greedy]
+        assert cache._loops[("ragged", greedy)].graph is None
         for k in final:
             assert torch.equal(st[k], final[k]), f"eager: {k}"
 
@@ -311,20 +316,20 @@ def test_state_reuse_and_recapture():
     model, fresh = _model(1000), lambda: _model(1000)
     kw = dict(do_sample=True, top_k=20, temperature=0.8, seed=7)
     a = generate_batch(model, _prompts(LENS), 30, **kw)
-    graph = model._mg_decode_cache._rgraph[False]["graph"]
+    graph = model._mg_decode_cache._loops[("ragged", False)].graph
     for lens, kw2 in (([9, 2, 4, 11], kw), ([9, 2, 4, 11], dict(do_sample=True, top_k=3, temperature=1.7, seed=8)),
                       (LENS, kw)):
         got = generate_batch(model, _prompts(lens, seed=4), 30, **kw2)
         want = generate_batch(fresh(), _prompts(lens, seed=4), 30, **kw2)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-        assert model._mg_decode_cache._rgraph[False]["graph"] is graph
+        assert model._mg_decode_cache._loops[("ragged", False)].graph is graph
     assert torch.equal(generate_batch(model, _prompts(LENS), 30, **kw)[0], a[0])
     other = fresh()
     with torch.no_grad():
         for m in (model, other):
             m.transformer.wpe.weight.mul_(3.0)  # in place: the version changes, the pointer does not
     got = generate_batch(model, _prompts(LENS), 30, **kw)
-    assert model._mg_decode_cache._rgraph[False]["graph"] is not graph
+    assert model._mg_decode_cache._loops[("ragged", False)].graph is not graph
     assert torch.equal(got[0], generate_batch(other, _prompts(LENS), 30, **kw)[0])
     assert not torch.equal(got[0], a[0])
 

@@ -76,7 +76,7 @@ def test_repeat_and_recapture(setup):
     model, idx, V = setup
     kw = dict(do_sample=True, top_k=20, temperature=0.8)
     a = model.generate(idx, 40, seed=7, **kw)
-    graph = model._mg_decode_cache._sgraph["graph"]
+    graph = model._mg_decode_cache._loops["sample"].graph
     b = model.generate(idx, 40, seed=7, **kw)
     assert torch.equal(a, b)
     c = model.generate(idx, 40, seed=8, **kw)
@@ -85,7 +85,7 @@ def test_repeat_and_recapture(setup):
     e = model.generate(idx, 40, seed=7, do_sample=True, top_k=20, temperature=3.0)
     f = model.generate(idx, 40, seed=7, do_sample=True, top_k=None, temperature=0.8)
     assert not torch.equal(a, d) and not torch.equal(a, e) and not torch.equal(a, f)
-    assert model._mg_decode_cache._sgraph["graph"] is graph
+    assert model._mg_decode_cache._loops["sample"].graph is graph
     assert torch.equal(model.generate(idx, 40, seed=7, **kw), a)
 
 
@@ -117,11 +117,11 @@ def test_greedy_intact(setup):
     LM-head argmax keys are untouched by the sampled loop."""
     model, idx, V = setup
     g0 = model.generate(idx, 50, do_sample=False)
-    ggraph = model._mg_decode_cache._ggraph["graph"]
+    ggraph = model._mg_decode_cache._loops["greedy"].graph
     model.generate(idx, 50, do_sample=True, top_k=10, seed=1)
     g1 = model.generate(idx, 50, do_sample=False)
     assert torch.equal(g0, g1)
-    assert model._mg_decode_cache._ggraph["graph"] is ggraph
+    assert model._mg_decode_cache._loops["greedy"].graph is ggraph
     torch.manual_seed(3)
     u0 = model.generate(idx, 10, do_sample=True, top_k=10)  # the unseeded host loop still works
     torch.manual_seed(3)
