@@ -79,6 +79,7 @@ def main():
     ap.add_argument("--sample", action="store_true",
                     help="time do_sample=True instead (this framework only, no reference run)")
     ap.add_argument("--top-k", type=int, default=40)
+    ap.add_argument("--top-p", type=float, default=None, help="with --sample: nucleus filtering (default: off)")
     ap.add_argument("--seed", type=int, default=None,
                     help="with --sample: the on-device seeded sampler; omitted: torch's generator (host loop)")
     ap.add_argument("--ragged", action="store_true",
@@ -97,6 +98,8 @@ def main():
         return ragged(ours, a)
     if a.sample:
         kw = dict(do_sample=True, top_k=a.top_k or None)
+        if a.top_p is not None:
+            kw["top_p"] = a.top_p
         if a.seed is not None:
             kw["seed"] = a.seed
         for B in map(int, a.batches.split(",")):
@@ -106,7 +109,8 @@ def main():
                 out, t = timed(lambda: ours.generate(idx, a.new, **kw))
             assert out.shape == (B, a.prompt + a.new)
             print(json.dumps({"metric": "sampled decode tokens/s", "model": "gpt2 (random init)", "batch": B,
-                              "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "seed": a.seed,
+                              "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "top_p": a.top_p,
+                              "seed": a.seed,
                               "tok_s": round(B * a.new / t, 1), "ms_per_step": round(t / a.new * 1e3, 4)}),
                   flush=True)
         return

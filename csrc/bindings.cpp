@@ -609,7 +609,7 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
 
 // One sampled token per row of logits [B, ld] bf16 (columns >= V are padding, never read): exact
 // top-k + Gumbel-max (sample.hip, the rule in common.h).  params: int32 [8] on the device, {seed lo,
-// seed hi, draw, inv_t fp32 bits, top_k (0: off), 0, 0, 0}; the kernel advances params[2] and, when
+// seed hi, draw, inv_t fp32 bits, top_k (0: off), 0, top_p fp32 bits (0: off), 0}; the kernel advances params[2] and, when
 // given, pos_dev[0] by one.  tok (int64, B elements) is written when given, else allocated; seq
 // (int64 [B, L], needs pos_dev) gets seq[b, pos_dev[0] + 1].  Returns tok.
 at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& params,
@@ -650,6 +650,26 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
   mg::sample_logits(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()), pd,
                     t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream());
   return t;
+}
+
+// The kept set of the sampling rule per row of logits (as for sample_logits): int32 [B, 2], the bf16
+// bit pattern of the lowest kept value and the number of kept entries under the block's top_k /
+// top_p / temperature.  Runs the sampler's kernel up to its threshold; nothing but the result is
+// written.
+at::Tensor sample_kept(const at::Tensor& logits, int64_t V, const at::Tensor& params) {
+  CHECK_BF16(logits); CHECK_DEV(params);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "sample_kept: logits [B, ld], unit column stride");
+  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "sample_kept: 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_kept: rows must be 16-byte aligned (ld % 8 == 0)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
+              params.device() == logits.device(), "sample_kept: params int32 [8] on the logits' device");
+  DevGuard g(logits.device());
+  at::Tensor out = at::empty({B, 2}, logits.options().dtype(at::kInt));
+  mg::sample_kept(bp(logits), ld, (int)B, (int)V, reinterpret_cast<const uint32_t*>(params.data_ptr<int>()),
+                  out.data_ptr<int>(), cur_stream());
+  return out;
 }
 
 // Ragged batches: the end of a decode step for every row that is not finished (kernels.h,
@@ -827,6 +847,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
         py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none());
+  m.def("sample_kept", &sample_kept, py::arg("logits"), py::arg("V"), py::arg("params"));
   m.def("pick_ragged", &pick_ragged, py::arg("logits"), py::arg("V"), py::arg("params"), py::arg("pos"),
         py::arg("done"), py::arg("tok"), py::arg("seq"), py::arg("greedy"));
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {

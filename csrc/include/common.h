@@ -191,7 +191,49 @@ MG_DEVICE void rowdrop8(float (&v)[8], uint64_t seed, long m, int n, int N, uint
 // significant bits, so its complement y = ((2^24 - x) - 0.5) 2^-24 is formed instead (exact) and
 // -ln(u) = -log1p(-y).  Accurate logf / log1pf, not the fast intrinsics: g is good to ~1e-6, the
 // score of any contender within 25 of the top to ~1e-5.
+//
+// Nucleus (top-p) filtering, after the temperature and top-k, before the Gumbel pass.  K is the
+// set top-k keeps (every finite entry when top-k is off; -inf is never kept), and for i in K
+//   w_i = exp((l_i - m) * inv_t)      Z = sum_K w_i      A(v) = sum_{i in K, l_i > v} w_i
+// (A(v): the mass strictly above the value v).  Kept: every i in K with A(l_i) < top_p * Z.  Equal
+// logits have the same A, so they are kept or dropped together (ties at the threshold all kept, as
+// for top-k); A(m) = 0, so the row maximum is always kept; A grows as the value falls, so the kept
+// set is an upper set of the bf16 values -- a threshold on the 16-bit key, and the final threshold
+// is the larger of the top-k and the nucleus keys.  top_p is a float32 in (0, 1]; params word 6
+// holds its bits, and 0 or anything >= 1.0 means off (the stage is skipped by a uniform branch).
+// Device arithmetic, independent of the order of the additions: the mass of an element is the
+// integer q_i = floor(w^_i * 2^32), w^_i = exp2(((l_i - m) * inv_t) * float32(log2 e)) in fp32
+// (sample_mass: subtract, two multiplies, v_exp_f32, a scale by 2^32, truncation -- one fixed
+// sequence, nothing to contract or reassociate), added as a 64-bit integer into LDS histograms
+// over the key's high, then low byte (V * 2^32 fits 64 bits for any V the binding accepts).  With
+// top_p = f * 2^-s exactly (f its 24-bit significand), the target is the integer
+//   T = ceil(f * Z^ / 2^s),  Z^ = sum q_i   (a 128-bit product),
+// and A^ < top_p * Z^ over the reals is exactly A^ < T over the integers.  The threshold is the
+// lowest key whose mass strictly above is below T.
+// Error of A^/Z^ against the real A/Z: an element's weight is off by at most eps_w * w_i + 2^-32,
+//   eps_w = 22.2 * (3 * 2^-24 + 1.2e-8) + 2^-23 = 4.4e-6
+// (three fp32 roundings and the rounded constant on an exponent of at most 32 ln 2 = 22.2 in
+// magnitude -- smaller weights truncate to 0 and are covered by the 2^-32 -- and 1 ulp of
+// v_exp_f32).  Z >= 1 (the maximum weighs 1), so |A^/Z^ - A/Z| <= 2 eps_w * A/Z + V * 2^-32: at the
+// boundary A/Z ~ top_p this is a relative shift of top_p by at most 8.8e-6 + V * 2^-32 / top_p
+// (2.2e-5 at V = 50257, top_p = 0.9; 4.8e-5 at top_p = 0.3).  The tests bracket the kernel's
+// threshold between the fp64 rule at top_p (1 +- delta), delta = 4 x that bound.
 constexpr uint32_t kSampleSalt = 0x5a3b1e97u;
+
+// q_i of the nucleus rule above: floor(2^32 exp((l - m) * inv_t)) for l <= m, 0 for l = -inf
+MG_DEVICE unsigned long long sample_mass(uint32_t bits, float m, float inv_t) {
+  const float y = ((bf2f(bits) - m) * inv_t) * 1.44269504f;
+  return (unsigned long long)(__builtin_amdgcn_exp2f(y) * 0x1p32f);
+}
+
+// T of the nucleus rule: ceil(top_p * Z) for top_p in (0, 1) given as fp32 bits, exactly
+MG_DEVICE unsigned long long sample_nucleus_target(uint32_t top_p_bits, unsigned long long Z) {
+  const uint32_t e = top_p_bits >> 23, frac = top_p_bits & 0x7fffffu;
+  const uint32_t f = e ? (frac | 0x800000u) : frac, s = e ? 150u - e : 149u;  // top_p = f * 2^-s, s >= 24
+  const unsigned __int128 prod = (unsigned __int128)f * Z;                    // < 2^88
+  if (s >= 96u) return prod ? 1ull : 0ull;
+  return (unsigned long long)((prod + (((unsigned __int128)1 << s) - 1)) >> s);
+}
 
 MG_DEVICE float sample_gumbel(uint32_t r3, uint32_t i) {
   const uint32_t x = fmix32(r3 + i * 0x9E3779B1u) >> 8;

@@ -82,13 +82,18 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
 
 // sample.hip -- one sampled token per row of bf16 logits [B, ld] (columns >= V never read; ld % 8
 // == 0, rows 16-byte aligned): exact top-k + Gumbel-max, the rule in common.h.  params (device,
-// 8 x u32): {seed lo, seed hi, draw counter, inv_t as fp32 bits, top_k (<= 0: off), 0, 0, 0} -- read
-// by the kernel, so a captured launch replays with new values.  Writes tok[b] (optional) and, with
+// 8 x u32): {seed lo, seed hi, draw counter, inv_t as fp32 bits, top_k (<= 0: off), stop token (ragged
+// only), top_p as fp32 bits (0 or >= 1.0: off; the nucleus rule in common.h), 0} -- read by the
+// kernel, so a captured launch replays with new values; only the draw counter is ever written.  Writes tok[b] (optional) and, with
 // seq, seq[b * seq_ld + *pos_dev + 1]; then a trailing one-thread kernel advances params[2] and
 // *pos_dev (when given) by one.
 constexpr int kSampleParamWords = 8;
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
                    int64_t* seq, long seq_ld, hipStream_t stream);
+// The kept set of the same rule for the block's top_k / top_p / temperature, by the sampler's own
+// kernel with the Gumbel pass replaced: out[2 b] = the bf16 bit pattern of row b's lowest kept
+// value (-inf's when nothing is kept), out[2 b + 1] = the number of kept entries.  Writes only out.
+void sample_kept(const bf16_t* logits, long ld, int B, int V, const uint32_t* params, int* out, hipStream_t stream);
 // Ragged batches: per-row device state pos [B], done [B] (int32), tok [B], seq [B, seq_ld].  One
 // kernel, one workgroup per row: a row with done[b] set is left alone; otherwise the token t -- the
 // argmax of the row's V logits, first index on ties (greedy), or the Gumbel-max draw with counter

@@ -12,10 +12,15 @@
 //   pass A  row maximum, and (top-k on) a 256-bin histogram of the high byte of the 16-bit key;
 //   pass B  (top-k on) histogram of the low byte among the keys in the bin that holds the k-th;
 //           -> the exact k-th largest key, ties included, no sort and no tolerance;
+//   nucleus (top_p on) the same two-level select with 64-bit integer masses in place of counts,
+//           over the elements top-k kept: the lowest key whose mass strictly above is below
+//           ceil(top_p * Z); the final threshold is the larger of the two keys;
 //   pass C  score (l - max) * inv_t + gumbel of every kept element, argmax as one 64-bit key
 //           (ordered score << 32 | ~index: the lowest index wins an exact tie).
 // Histograms are kept 32 times over (one copy per lane mod 32, the copy picks the LDS bank):
-// logits of one row share a few exponents, and 64 lanes adding to one LDS word serialise.
+// logits of one row share a few exponents, and 64 lanes adding to one LDS word serialise.  The mass
+// histograms reuse the same 32 KiB as 256 x 16 copies of 64 bits; integer adds commute, so the
+// threshold is a function of the row's values alone.
 //
 // Everything that changes between generate() calls is read from a device parameter block (and the
 // position from pos_dev), so a captured launch replays with a new seed, temperature or k.  The
@@ -35,6 +40,7 @@ namespace {
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
 constexpr int kCopies = 32;
+constexpr int kMassCopies = kCopies / 2;  // 64-bit bins in the same array
 
 // order-preserving 16-bit key of a bf16 bit pattern (-0 counts as +0, as in a float compare)
 MG_DEVICE uint32_t key16(uint32_t bits) {
@@ -50,6 +56,11 @@ MG_DEVICE uint32_t ordered_f32(float s) {
 
 MG_DEVICE unsigned long long shfl_xor_u64(unsigned long long v, int o) {
   const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+MG_DEVICE unsigned long long shfl_up_u64(unsigned long long v, int o) {
+  const unsigned lo = __shfl_up((unsigned)v, o, 64), hi = __shfl_up((unsigned)(v >> 32), o, 64);
   return ((unsigned long long)hi << 32) | lo;
 }
 
@@ -129,6 +140,44 @@ MG_DEVICE void hist_select(const uint32_t* hist, uint32_t* scan, uint32_t want, 
   __syncthreads();  // scan and hist may be rewritten
 }
 
+// hist_select on masses.  hist: 256 x kMassCopies 64-bit sums; scan: 6 words.  The bin (counted
+// from the top) in which the cumulative mass reaches want = target(sum of all bins), and how much of
+// that bin's mass is still wanted; bin 0 and rest 0 when there is no such bin (want = 0 or above
+// the sum).  Result broadcast to the block.
+template <class T>
+MG_DEVICE void mass_select(const unsigned long long* hist, unsigned long long* scan, T target, uint32_t& bin,
+                           unsigned long long& rest) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __syncthreads();  // the histogram is complete
+  unsigned long long c = 0ull;
+  if (t < 256) {
+#pragma unroll 8
+    for (int j = 0; j < kMassCopies; ++j) c += hist[(255 - t) * kMassCopies + ((j + t) & (kMassCopies - 1))];
+  }
+  unsigned long long inc = c;  // inclusive scan over descending bins
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long v = shfl_up_u64(inc, o);
+    if (lane >= o) inc += v;
+  }
+  if (t < 256 && lane == 63) scan[w] = inc;
+  if (t == 0) scan[4] = scan[5] = 0ull;
+  __syncthreads();
+  if (t < 256) {
+    const unsigned long long want = target(scan[0] + scan[1] + scan[2] + scan[3]);
+    unsigned long long before = inc - c;
+    for (int i = 0; i < w; ++i) before += scan[i];
+    if (before < want && want <= before + c) {  // at most one thread
+      scan[4] = 255ull - (unsigned long long)t;
+      scan[5] = want - before;
+    }
+  }
+  __syncthreads();
+  bin = (uint32_t)scan[4];
+  rest = scan[5];
+  __syncthreads();  // scan and hist may be rewritten
+}
+
 // order-preserving key of a float with the index inverted in the low half: the max key is the
 // FIRST index among equal values (the amax_key of gemv.hip, whose fused argmax ranks the same
 // stored bf16 logits)
@@ -170,16 +219,21 @@ MG_DEVICE void ragged_finish(long t, int b, int p, int eos, int* pos, int* done,
   if (eos >= 0 && t == (long)eos) done[b] = 1;
 }
 
-// params: {seed_lo, seed_hi, draw, inv_t (fp32 bits), top_k (<= 0: off), eos (ragged), 0, 0}
+// params: {seed_lo, seed_hi, draw, inv_t (fp32 bits), top_k (<= 0: off), eos (ragged),
+//          top_p (fp32 bits; 0 or >= 1.0: off), 0}
 // RAGGED: per-row state -- the draw counter is pos_dev[b] + 1 (the column of the produced token in
 // the row's own sequence), a row whose done[b] is set is skipped, and ragged_finish ends the row.
-template <bool RAGGED>
+// KEPT (sample_kept): the same thresholds, then instead of the Gumbel pass the kept set itself --
+// kept_out[2 b] = the bf16 bits of the lowest kept value (-inf when nothing is kept),
+// kept_out[2 b + 1] = the number of kept entries; nothing else is written.
+template <bool RAGGED, bool KEPT>
 __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
                                                           const uint32_t* params, int* pos_dev, int* done,
                                                           int64_t* __restrict__ tok, int64_t* __restrict__ seq,
-                                                          long seq_ld) {
-  __shared__ uint32_t hist[256 * kCopies];
+                                                          long seq_ld, int* __restrict__ kept_out) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256 * kCopies];  // or 256 x kMassCopies x 64 bits
   __shared__ uint32_t scan[kWaves + 2];
+  __shared__ unsigned long long mscan[6];
   __shared__ float redf[kWaves];
   __shared__ unsigned long long redk[kWaves];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -193,6 +247,8 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
   const float inv_t = __uint_as_float(params[3]);
   const int top_k = (int)params[4];
   const bool select = top_k > 0 && top_k < V;  // k >= V keeps every element
+  const uint32_t top_p = params[6];
+  const bool nucleus = top_p - 1u < 0x3f7fffffu;  // fp32 bits of a value in (0, 1)
 
   // the row, in registers when it fits (for_regs)
   const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
@@ -242,6 +298,96 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     thr = (hi << 8) | lo;
   }
 
+  // A row in registers whose threshold keeps a few elements per thread: mark them in a sweep over
+  // the registers (bit 8 j + e = element e of register j), then visit the marked ones one by one
+  // -- one copy of an expensive body (the ~100 instructions of Gumbel noise) in the code, not one
+  // per register element.  The body checks the threshold itself (the tail is always visited).
+  auto mark = [&](uint32_t t) {
+    unsigned long long kept = 0ull;
+#pragma unroll
+    for (int j = 0; j < kRegVec; ++j) {
+      if ((int)threadIdx.x + j * kThreads < nv)
+        for_vec(regs[j], j * 8, [&](int e, uint32_t bits) { kept |= key16(bits) >= t ? 1ull << e : 0ull; });
+    }
+    return kept;
+  };
+  auto for_marked = [&](unsigned long long kept, auto f) {
+    while (kept) {
+      const int e = __builtin_ctzll(kept);
+      kept &= kept - 1ull;
+      const int i = (((int)threadIdx.x + (e >> 3) * kThreads) << 3) + (e & 7);
+      f(i, (uint32_t)row[i]);
+    }
+    if (threadIdx.x < 8 && ti < V) f(ti, tail);
+  };
+
+  // ---- nucleus: the lowest key whose mass strictly above is below ceil(top_p * Z), by the same
+  // two-level select on integer masses (common.h); only what top-k kept carries mass
+  if (nucleus) {
+    unsigned long long* mhist = reinterpret_cast<unsigned long long*>(hist);
+    unsigned long long* mine = mhist + (lane & (kMassCopies - 1));
+    const bool few = select && cached;
+    const unsigned long long kept = few ? mark(thr) : 0ull;
+    auto pass = [&](auto f) {
+      if (few) for_marked(kept, f);
+      else sweep(f);
+    };
+    uint32_t hi, lo;
+    unsigned long long rest, unused;
+    hist_clear(hist);
+    __syncthreads();
+    pass([&](int, uint32_t bits) {
+      const uint32_t k = key16(bits);
+      if (k < thr || bits == 0xff80u) return;
+      const unsigned long long q = sample_mass(bits, m, inv_t);
+      if (q) atomicAdd(mine + (k >> 8) * kMassCopies, q);
+    });
+    mass_select(mhist, mscan, [&](unsigned long long Z) { return sample_nucleus_target(top_p, Z); }, hi, rest);
+    hist_clear(hist);
+    __syncthreads();
+    pass([&](int, uint32_t bits) {
+      const uint32_t k = key16(bits);
+      if ((k >> 8) != hi || k < thr || bits == 0xff80u) return;
+      const unsigned long long q = sample_mass(bits, m, inv_t);
+      if (q) atomicAdd(mine + (k & 0xffu) * kMassCopies, q);
+    });
+    mass_select(mhist, mscan, [&](unsigned long long) { return rest; }, lo, unused);
+    const uint32_t pt = (hi << 8) | lo;
+    thr = pt > thr ? pt : thr;
+  }
+
+  if constexpr (KEPT) {  // the kept set itself: its lowest value and its size
+    uint32_t cnt = 0u, lowest = 0xffffffffu;
+    sweep([&](int, uint32_t bits) {
+      const uint32_t k = key16(bits);
+      if (k < thr || bits == 0xff80u) return;
+      ++cnt;
+      lowest = k < lowest ? k : lowest;
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      cnt += __shfl_xor(cnt, o, 64);
+      const uint32_t k = __shfl_xor(lowest, o, 64);
+      lowest = k < lowest ? k : lowest;
+    }
+    if (lane == 0) {
+      scan[w] = cnt;
+      redk[w] = lowest;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int i = 1; i < kWaves; ++i) {
+        cnt += scan[i];
+        lowest = (uint32_t)redk[i] < lowest ? (uint32_t)redk[i] : lowest;
+      }
+      const uint32_t bits = (lowest & 0x8000u) ? (lowest ^ 0x8000u) : (lowest ^ 0xffffu);  // key16 undone
+      kept_out[2 * b] = cnt ? (int)bits : 0xff80;
+      kept_out[2 * b + 1] = (int)cnt;
+    }
+    return;
+  }
+
   // ---- pass C: Gumbel-max over the kept set
   const uint32_t r0 = fmix32(seed_lo ^ kSampleSalt);
   const uint32_t r1 = fmix32(r0 + seed_hi);
@@ -254,23 +400,8 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     const unsigned long long k = ((unsigned long long)ordered_f32(s) << 32) | (0xffffffffu - (uint32_t)i);
     best = k > best ? k : best;
   };
-  if (select && cached) {
-    // top-k keeps a few elements per row: mark them in a sweep over the registers (bit 8 j + e =
-    // element e of register j), then score the marked ones one by one -- one copy of the ~100
-    // instructions of Gumbel noise in the code, not one per register element
-    unsigned long long kept = 0ull;
-#pragma unroll
-    for (int j = 0; j < kRegVec; ++j) {
-      if ((int)threadIdx.x + j * kThreads < nv)
-        for_vec(regs[j], j * 8, [&](int e, uint32_t bits) { kept |= key16(bits) >= thr ? 1ull << e : 0ull; });
-    }
-    while (kept) {
-      const int e = __builtin_ctzll(kept);
-      kept &= kept - 1ull;
-      const int i = (((int)threadIdx.x + (e >> 3) * kThreads) << 3) + (e & 7);
-      score(i, (uint32_t)row[i]);
-    }
-    if (threadIdx.x < 8 && ti < V) score(ti, tail);
+  if ((select || nucleus) && cached) {  // top-k and the nucleus keep a few elements per row
+    for_marked(mark(thr), score);
   } else {
     for_row(row, V, score);
   }
@@ -350,14 +481,21 @@ namespace mg {
 
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
                    int64_t* seq, long seq_ld, hipStream_t stream) {
-  sample_kernel<false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, nullptr, tok, seq, seq_ld);
+  sample_kernel<false, false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, nullptr, tok, seq, seq_ld,
+                                                          nullptr);
   sample_advance_kernel<<<1, 64, 0, stream>>>(params, pos_dev);
 }
 
 void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos, int* done, int64_t* tok,
                  int64_t* seq, long seq_ld, bool greedy, hipStream_t stream) {
   if (greedy) pick_greedy_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld);
-  else sample_kernel<true><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld);
+  else sample_kernel<true, false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld,
+                                                              nullptr);
+}
+
+void sample_kept(const bf16_t* logits, long ld, int B, int V, const uint32_t* params, int* out, hipStream_t stream) {
+  sample_kernel<false, true><<<B, kThreads, 0, stream>>>(logits, ld, V, params, nullptr, nullptr, nullptr, nullptr, 0,
+                                                         out);
 }
 
 }  // namespace mg

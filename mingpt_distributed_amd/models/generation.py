@@ -38,13 +38,16 @@ from ..ops import reference as R
 from ..ops.grads import before_use
 
 
-def _sample(logits, temperature, do_sample, top_k):
+def _sample(logits, temperature, do_sample, top_k, top_p=None):
     if not do_sample:  # greedy: top-1 of softmax(logits / t) is the argmax of the logits
         return logits.argmax(dim=-1, keepdim=True)
     logits = logits.float() / temperature
     if top_k is not None:
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
         logits[logits < v[:, [-1]]] = -float("Inf")
+    p = R.sample_top_p(top_p)
+    if p is not None:  # the nucleus of what is left, ties at its boundary all kept (common.h)
+        logits[~R.nucleus_keep(logits.double(), p)] = -float("Inf")
     probs = F.softmax(logits, dim=-1)
     return torch.multinomial(probs, num_samples=1)
 
@@ -382,7 +385,7 @@ class _GpuCache:
         """n sampled decode steps starting with token ``tok`` [B, 1] at position ``pos``: each step
         is the plain LM head followed by the sample kernel, which writes the next token into the
         buffer the next step's embedding reads and advances the device position and draw counter.
-        Seed, temperature and top-k live in the device parameter block (``words``), so the one
+        Seed, temperature, top-k and top-p live in the device parameter block (``words``), so the one
         captured step serves every call.  Returns the n new tokens [B, n] (positions pos + 1 ..
         pos + n)."""
         assert pos + n <= self.tmax
@@ -481,22 +484,24 @@ class _GpuCache:
 _I64_MIN = -(1 << 63)
 
 
-def _sample_words(seed, draw, temperature, top_k):
+def _sample_words(seed, draw, temperature, top_k, top_p=None):
     """The sample kernel's parameter block as 8 int32: seed low / high word, draw counter,
-    float32(1 / temperature) as bits, top_k (0: off)."""
+    float32(1 / temperature) as bits, top_k (0: off), 0, float32(top_p) as bits (0: off), 0."""
     s32 = lambda x: ((x & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
     inv_t = struct.unpack("<i", struct.pack("<f", 1.0 / temperature))[0]
-    return [s32(seed), s32(seed >> 32), s32(draw), inv_t, min(int(top_k or 0), 0x7FFFFFFF), 0, 0, 0]
+    p = R.sample_top_p(top_p)
+    p_bits = 0 if p is None else struct.unpack("<i", struct.pack("<f", p))[0]
+    return [s32(seed), s32(seed >> 32), s32(draw), inv_t, min(int(top_k or 0), 0x7FFFFFFF), 0, p_bits, 0]
 
 
 def _weight_stamp(model):
     return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
 
-def _ragged_words(seed, temperature, top_k, eos_token):
+def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
     """The parameter block of the ragged pick kernels: ``_sample_words`` (the draw counter is not
     used: it is the row's position + 1) with the stop token in word 5, -1 for none."""
-    w = _sample_words(seed, 0, temperature, top_k)
+    w = _sample_words(seed, 0, temperature, top_k, top_p)
     w[5] = -1 if eos_token is None else int(eos_token)
     return w
 
@@ -514,21 +519,28 @@ def _gpu_cache(model, idx, tmax, last=None):
 
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
-             top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None):
-    """``seed`` (with ``do_sample``): draw by the counter-based Gumbel-max rule (common.h,
+             top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
+             top_p: Optional[float] = None):
+    """``top_p`` (with ``do_sample``): nucleus filtering after the temperature and top-k -- keep the
+    tokens whose probability mass strictly above them is below ``top_p`` of the total, ties kept
+    together (the rule in common.h); None or 1.0 is off.  With a seed it is a word of the sample
+    kernel's parameter block, so the captured loop serves any value.
+
+    ``seed`` (with ``do_sample``): draw by the counter-based Gumbel-max rule (common.h,
     ``ops.reference.sample_gumbel``) instead of torch's global generator -- the tokens depend on
     (seed, column, batch row, logits) only, and on the GPU the whole token loop stays on the device
     (``_GpuCache.sample``).  ``seed=None`` leaves every path as it was."""
     bs = model.block_size
     seeded = do_sample and seed is not None
+    if seeded or (do_sample and top_p is not None):
+        R.check_sample_args(temperature, top_k, top_p)
     if seeded:
-        R.check_sample_args(temperature, top_k)
         seed = int(seed) & ((1 << 64) - 1)
 
     def pick(logits, col):
         if seeded:
-            return R.sample_gumbel(logits, temperature, top_k, seed, col)
-        return _sample(logits, temperature, do_sample, top_k)
+            return R.sample_gumbel(logits, temperature, top_k, seed, col, top_p=top_p)
+        return _sample(logits, temperature, do_sample, top_k, top_p)
 
     # ZeRO-1: the KV-cache path launches the kernels directly (never model.forward), so neither
     # the fused ops' per-bucket waits nor the engine's forward pre-hook run: wait here for every
@@ -544,7 +556,7 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.logits.argmax(-1),
                                       lambda c, tok, L, n, T: c.greedy(tok, L, n))
     if idx.is_cuda and seeded and max_new_tokens > 0:  # the draw counter of a token is its column T
-        words = lambda T: _sample_words(seed, T, temperature, top_k)
+        words = lambda T: _sample_words(seed, T, temperature, top_k, top_p)
         return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.sample_prefill(words(T)),
                                       lambda c, tok, L, n, T: c.sample(tok, L, n, words(T)))
     cache = None
@@ -619,7 +631,7 @@ def _ragged_prompts(prompts):
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                    top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
-                   pad_token: int = 0):
+                   pad_token: int = 0, top_p: Optional[float] = None):
     """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``.
 
     ``prompts``: a sequence of 1-D int64 tensors (1 or more tokens each), or a pair ``(idx [B, Tp]
@@ -632,7 +644,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     the row's last-position logits (first index on ties); sampling is the seeded Gumbel-max rule of
     ``generate(seed=...)`` with the draw counter = the column of the produced token in the row's
     own unpadded sequence and the batch row index b (``do_sample`` without a seed draws one seed
-    from torch's global generator first).  A row stops after ``eos_token`` or ``max_new_tokens``
+    from torch's global generator first), ``top_p`` included.  A row stops after ``eos_token`` or ``max_new_tokens``
     tokens.  There is no sliding window here: ``max(len) + max_new_tokens`` must fit ``block_size``
     (ValueError otherwise).
 
@@ -652,7 +664,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
         raise ValueError(f"generate_batch: pad_token {pad_token} is not a token id (vocab {V})")
     if eos_token is not None and not 0 <= int(eos_token) < V:
         raise ValueError(f"generate_batch: eos_token {eos_token} is not a token id (vocab {V})")
-    R.check_sample_args(temperature, top_k)
+    R.check_sample_args(temperature, top_k, top_p)
     if do_sample and seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
     seed = int(seed or 0) & ((1 << 64) - 1)
@@ -668,13 +680,13 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
         return tokens, lengths
     if device.type == "cuda":
         return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
-                                   do_sample, top_k, seed, eos_token, int(pad_token))
+                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p)
     for b, r in enumerate(rows):  # the executable definition of the semantics
         cache = _CpuCache(model, r.view(1, -1))
         logits, n = cache.logits, lens[b]
         for _ in range(max_new_tokens):
             if do_sample:
-                nxt = R.sample_gumbel(logits, temperature, top_k, seed, n, row0=b)
+                nxt = R.sample_gumbel(logits, temperature, top_k, seed, n, row0=b, top_p=top_p)
             else:
                 nxt = logits.argmax(dim=-1, keepdim=True)
             tokens[b, n] = nxt.view(())
@@ -688,7 +700,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
 
 def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
-                        pad_token):
+                        pad_token, top_p=None):
     """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
     causal attention makes every position before a row's length exact -- take row b's logits at
     column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
@@ -697,7 +709,7 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     they are."""
     B, Lmax = idx.shape
     cache = _gpu_cache(model, idx, model.block_size, last=lengths - 1)
-    words = _ragged_words(seed, temperature, top_k, eos_token)
+    words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
     st = cache.ragged_start(idx, lengths, words, greedy)
     n = max_new_tokens - 1

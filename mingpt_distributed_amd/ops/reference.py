@@ -79,11 +79,13 @@ def _fmix32(h: torch.Tensor) -> torch.Tensor:
     return h ^ (h >> 16)
 
 
-def check_sample_args(temperature: float, top_k) -> None:
+def check_sample_args(temperature: float, top_k, top_p=None) -> None:
     if not temperature > 0:
         raise ValueError(f"sampling needs temperature > 0, got {temperature}")
     if top_k is not None and top_k < 1:
         raise ValueError(f"sampling needs top_k >= 1 (or None), got {top_k}")
+    if top_p is not None and not 0 < float(top_p) <= 1:  # NaN fails both comparisons
+        raise ValueError(f"sampling needs 0 < top_p <= 1 (or None), got {top_p}")
 
 
 def sample_inv_t(temperature: float) -> float:
@@ -91,12 +93,38 @@ def sample_inv_t(temperature: float) -> float:
     return float(torch.tensor(1.0 / temperature, dtype=torch.float32).item())
 
 
-def sample_gumbel(logits: torch.Tensor, temperature: float, top_k, seed: int, draw: int, row0: int = 0):
+def sample_top_p(top_p):
+    """float32(top_p), the value the rule uses, or None when the nucleus is off (None or >= 1.0)."""
+    if top_p is None:
+        return None
+    p = float(torch.tensor(float(top_p), dtype=torch.float32).item())
+    return p if p < 1.0 else None
+
+
+def nucleus_keep(x: torch.Tensor, top_p: float) -> torch.Tensor:
+    """The nucleus of ``csrc/include/common.h`` on rows of log-weights ``x`` [B, V] (fp64; -inf =
+    not in the set top-k kept): True where the mass strictly above the entry's value is below
+    ``top_p`` times the row's mass.  Equal values share one answer; the row maximum is always kept."""
+    xs, order = torch.sort(x, dim=-1, descending=True)
+    w = torch.exp(xs - xs[:, :1])
+    w = torch.where(torch.isfinite(xs), w, torch.zeros_like(w))
+    cum = torch.cumsum(w, dim=-1)
+    # the mass strictly above a value is the exclusive prefix at the first entry of its tie group
+    first = torch.ones_like(xs, dtype=torch.bool)
+    first[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    above = torch.cummax(torch.where(first, cum - w, torch.zeros_like(w)), dim=-1).values
+    keep_sorted = (above < top_p * cum[:, -1:]) & torch.isfinite(xs)
+    return torch.zeros_like(keep_sorted).scatter_(-1, order, keep_sorted)
+
+
+def sample_gumbel(logits: torch.Tensor, temperature: float, top_k, seed: int, draw: int, row0: int = 0,
+                  top_p=None):
     """One token per row of ``logits`` [B, V] by the Gumbel-max rule of ``csrc/include/common.h``
     ('Gumbel-max sampling'; the kernel is ``csrc/kernels/sample.hip``), in integer ops and fp64 on
     the logits' device.  ``draw`` is the column of the produced token in the returned sequence,
-    row b of ``logits`` is batch row ``row0 + b``.  Returns [B, 1] int64."""
-    check_sample_args(temperature, top_k)
+    row b of ``logits`` is batch row ``row0 + b``.  ``top_p``: the nucleus filter of the same rule,
+    after the temperature and top-k (None or >= 1.0: off).  Returns [B, 1] int64."""
+    check_sample_args(temperature, top_k, top_p)
     B, V = logits.shape
     dev = logits.device
     seed &= (1 << 64) - 1
@@ -115,6 +143,11 @@ def sample_gumbel(logits: torch.Tensor, temperature: float, top_k, seed: int, dr
         kth = torch.topk(l, min(int(top_k), V), dim=-1).values[:, -1:]
         score = score.masked_fill(l < kth, float("-inf"))
     score = score.masked_fill(l == float("-inf"), float("-inf"))
+    p = sample_top_p(top_p)
+    if p is not None:
+        x = (l - l.max(dim=-1, keepdim=True).values) * sample_inv_t(temperature)
+        x = x.masked_fill(score == float("-inf"), float("-inf"))  # outside top-k, or -inf itself
+        score = score.masked_fill(~nucleus_keep(x, p), float("-inf"))
     return score.argmax(dim=-1, keepdim=True)
 
 

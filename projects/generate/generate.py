@@ -41,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--num-samples", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--top-k", type=int, default=40)
+    ap.add_argument("--top-p", type=float, default=None,
+                    help="nucleus filtering after the temperature and top-k (default: off)")
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--device", default="auto")
@@ -75,7 +77,7 @@ def main(argv=None):
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
     x = x.expand(a.num_samples, -1).contiguous()
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
-                       top_k=a.top_k, seed=a.seed)
+                       top_k=a.top_k, seed=a.seed, top_p=a.top_p)
     outs = []
     for i in range(a.num_samples):
         out = tok.decode(y[i].cpu().squeeze()) if tok is not None else y[i].tolist()
@@ -97,7 +99,7 @@ def generate_many(model, tok, texts, a, dev):
         eos = None
     rows = [r.to(dev) for r in rows for _ in range(a.num_samples)]
     y, n = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
-                                top_k=a.top_k, seed=a.seed, eos_token=eos)
+                                top_k=a.top_k, seed=a.seed, eos_token=eos, top_p=a.top_p)
     outs = []
     for i in range(len(rows)):
         ids = y[i, :int(n[i])].cpu()
