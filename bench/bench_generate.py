@@ -71,6 +71,52 @@ def ragged(model, a):
         print(json.dumps(res), flush=True)
 
 
+def logprobs(model, a):
+    """Tokens/s of the same call without and with ``return_logprobs=True`` per batch size B:
+    ``generate`` on B prompts of --prompt tokens (greedy, or with --sample [--seed] sampled), and
+    with --ragged ``generate_batch`` on B prompts spread over --min-len .. --max-len instead.  Both
+    cases are warmed up (each has its own captured loop), checked to give the same tokens, then
+    timed --reps times in turn; the median is reported with the spread."""
+    import statistics
+
+    kw = {}
+    if a.sample:
+        kw = dict(do_sample=True, top_k=a.top_k or None, top_p=a.top_p, seed=a.seed)
+    for B in map(int, a.batches.split(",")):
+        g = torch.Generator().manual_seed(B)
+        if a.ragged:
+            lens = [round(a.min_len + (a.max_len - a.min_len) * i / max(B - 1, 1)) for i in range(B)]
+            prompts = [torch.randint(0, 50257, (n,), generator=g).cuda() for n in lens]
+            plain = lambda: model.generate_batch(prompts, a.new, **kw)[0]
+            with_lp = lambda: model.generate_batch(prompts, a.new, return_logprobs=True, **kw)[0]
+        else:
+            lens = [a.prompt] * B
+            idx = torch.randint(0, 50257, (B, a.prompt), generator=g).cuda()
+            plain = lambda: model.generate(idx, a.new, **kw)
+            with_lp = lambda: model.generate(idx, a.new, return_logprobs=True, **kw)[0]
+        cases = {"plain": plain, "logprobs": with_lp}  # each returns the tokens
+        with torch.no_grad():
+            for fn in cases.values():  # warm-up at the timed shapes (kernels, states, graph capture)
+                fn()
+            if a.seed is not None or not a.sample:  # torch's global generator does not repeat
+                assert torch.equal(cases["plain"](), cases["logprobs"]())
+            times = {k: [] for k in cases}
+            for _ in range(a.reps):
+                for k, fn in cases.items():
+                    times[k].append(timed(fn)[1])
+        res = {"metric": "decode tokens/s without / with return_logprobs", "model": "gpt2 (random init)",
+               "batch": B, "entry": "generate_batch" if a.ragged else "generate", "prompt_lengths": lens,
+               "new_tokens": a.new, "sample": bool(a.sample), "top_k": a.top_k if a.sample else None,
+               "top_p": a.top_p if a.sample else None, "seed": a.seed, "reps": a.reps}
+        for k, ts in times.items():
+            res[k + "_tok_s"] = round(B * a.new / statistics.median(ts), 1)
+            res[k + "_tok_s_range"] = [round(B * a.new / max(ts), 1), round(B * a.new / min(ts), 1)]
+            res[k + "_ms_per_step"] = round(statistics.median(ts) / a.new * 1e3, 4)
+        res["logprobs_over_plain_time"] = round(statistics.median(times["logprobs"]) /
+                                                statistics.median(times["plain"]), 4)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prompt", type=int, default=32)
@@ -87,13 +133,19 @@ def main():
                          "mixed prompts as sequential B = 1 generate calls")
     ap.add_argument("--min-len", type=int, default=16, help="--ragged: shortest mixed prompt")
     ap.add_argument("--max-len", type=int, default=256, help="--ragged: longest mixed prompt")
-    ap.add_argument("--reps", type=int, default=5, help="--ragged: timed repetitions per case (alternating)")
+    ap.add_argument("--reps", type=int, default=5,
+                    help="--ragged / --logprobs: timed repetitions per case (alternating)")
+    ap.add_argument("--logprobs", action="store_true",
+                    help="time the same call without and with return_logprobs=True (this framework only): "
+                         "generate, greedy or with --sample [--seed]; with --ragged generate_batch")
     a = ap.parse_args()
     from mingpt_distributed_amd.models import GPT, GPTConfig
 
     torch.manual_seed(0)
     ours = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
+    if a.logprobs:
+        return logprobs(ours, a)
     if a.ragged:
         return ragged(ours, a)
     if a.sample:

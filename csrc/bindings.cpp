@@ -607,14 +607,33 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// The optional log-probability arguments of the pick kernels (kernels.h): lse fp32 with 2 B
+// elements ({m, lnz} per row, from logits_lse on the same logits) and lp fp32 of seq's shape; both
+// or neither.  Sets the two pointers (null without them).
+void logprob_args(const char* op, const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp,
+                  const at::Tensor& logits, const at::Tensor* seq, const float*& lsep, float*& lpp) {
+  lsep = nullptr;
+  lpp = nullptr;
+  const bool has_lse = lse.has_value() && lse->defined(), has_lp = lp.has_value() && lp->defined();
+  if (!has_lse && !has_lp) return;
+  TORCH_CHECK(has_lse && has_lp && seq, op, ": lse and lp go together, with seq");
+  CHECK_F32(*lse); CHECK_CONTIG(*lse); CHECK_F32(*lp); CHECK_CONTIG(*lp);
+  TORCH_CHECK(lse->numel() == 2 * logits.size(0) && lse->device() == logits.device(), op, ": lse fp32 [B, 2]");
+  TORCH_CHECK(lp->sizes() == seq->sizes() && lp->device() == logits.device(), op, ": lp fp32 of seq's shape");
+  lsep = lse->data_ptr<float>();
+  lpp = lp->data_ptr<float>();
+}
+
 // One sampled token per row of logits [B, ld] bf16 (columns >= V are padding, never read): exact
 // top-k + Gumbel-max (sample.hip, the rule in common.h).  params: int32 [8] on the device, {seed lo,
 // seed hi, draw, inv_t fp32 bits, top_k (0: off), 0, top_p fp32 bits (0: off), 0}; the kernel advances params[2] and, when
 // given, pos_dev[0] by one.  tok (int64, B elements) is written when given, else allocated; seq
-// (int64 [B, L], needs pos_dev) gets seq[b, pos_dev[0] + 1].  Returns tok.
+// (int64 [B, L], needs pos_dev) gets seq[b, pos_dev[0] + 1].  lse / lp (optional, with seq): the
+// drawn token's log-probability goes to lp[b, pos_dev[0] + 1] (logprob_args).  Returns tok.
 at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& params,
                          const c10::optional<at::Tensor>& pos_dev, const c10::optional<at::Tensor>& tok,
-                         const c10::optional<at::Tensor>& seq) {
+                         const c10::optional<at::Tensor>& seq, const c10::optional<at::Tensor>& lse,
+                         const c10::optional<at::Tensor>& lp) {
   CHECK_BF16(logits); CHECK_DEV(params);
   TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "sample_logits: logits [B, ld], unit column stride");
   const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
@@ -647,8 +666,11 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
     seqp = seq->data_ptr<int64_t>();
     seq_ld = seq->size(1);
   }
+  const float* lsep;
+  float* lpp;
+  logprob_args("sample_logits", lse, lp, logits, seq.has_value() ? &*seq : nullptr, lsep, lpp);
   mg::sample_logits(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()), pd,
-                    t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream());
+                    t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream(), lsep, lpp);
   return t;
 }
 
@@ -675,9 +697,11 @@ at::Tensor sample_kept(const at::Tensor& logits, int64_t V, const at::Tensor& pa
 // Ragged batches: the end of a decode step for every row that is not finished (kernels.h,
 // pick_ragged).  logits [B, ld] bf16 as for sample_logits; params int32 [8] (word 5: the stop token,
 // negative for none); pos, done int32 [B]; tok int64 with B elements; seq int64 [B, L].  All
-// updated in place.
+// updated in place.  lse / lp (optional): the picked token's log-probability goes to
+// lp[b, pos[b] + 1] of every row that advances (logprob_args).
 void pick_ragged(const at::Tensor& logits, int64_t V, const at::Tensor& params, const at::Tensor& pos,
-                 const at::Tensor& done, const at::Tensor& tok, const at::Tensor& seq, bool greedy) {
+                 const at::Tensor& done, const at::Tensor& tok, const at::Tensor& seq, bool greedy,
+                 const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp) {
   CHECK_BF16(logits); CHECK_DEV(params);
   TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "pick_ragged: logits [B, ld], unit column stride");
   const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
@@ -693,10 +717,57 @@ void pick_ragged(const at::Tensor& logits, int64_t V, const at::Tensor& params, 
   TORCH_CHECK(tok.numel() == B && tok.device() == logits.device(), "pick_ragged: tok int64 with B elements");
   TORCH_CHECK(seq.dim() == 2 && seq.size(0) == B && seq.size(1) >= 2 && seq.device() == logits.device(),
               "pick_ragged: seq int64 [B, L]");
+  const float* lsep;
+  float* lpp;
+  logprob_args("pick_ragged", lse, lp, logits, &seq, lsep, lpp);
   DevGuard g(logits.device());
   mg::pick_ragged(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()),
                   pos.data_ptr<int>(), done.data_ptr<int>(), tok.data_ptr<int64_t>(), seq.data_ptr<int64_t>(),
-                  seq.size(1), greedy, cur_stream());
+                  seq.size(1), greedy, cur_stream(), lsep, lpp);
+}
+
+// Per-token log-probabilities of the rule in common.h for every row of logits [M, ld] bf16 (as for
+// sample_logits: columns >= V never read).  Returns lse fp32 [M, 2] = {row maximum, lnz}; with
+// targets (int64 [M] on the device) returns (lse, lp): lp fp32 [M], lp[r] = the log-probability of
+// token targets[r] -- a negative target (or one >= V) leaves lp[r] as it is (0 in a buffer allocated
+// here).  lse / lp: write into these instead of allocating.
+py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<at::Tensor>& targets,
+                      const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp) {
+  CHECK_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "logits_lse: logits [M, ld], unit column stride");
+  const int64_t M = logits.size(0), ld = M > 1 ? logits.stride(0) : 0;  // one row: no stride
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (M == 1 || ld >= logits.size(1)), "logits_lse: 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "logits_lse: rows must be 16-byte aligned (ld % 8 == 0)");
+  TORCH_CHECK(M <= 0x7fffffff, "logits_lse: too many rows");
+  DevGuard g(logits.device());
+  at::Tensor l, p;
+  if (lse.has_value() && lse->defined()) {
+    CHECK_F32(*lse); CHECK_CONTIG(*lse);
+    TORCH_CHECK(lse->numel() == 2 * M && lse->device() == logits.device(), "logits_lse: lse fp32 [M, 2]");
+    l = *lse;
+  } else {
+    l = at::empty({M, 2}, logits.options().dtype(at::kFloat));
+  }
+  const bool has_t = targets.has_value() && targets->defined();
+  const int64_t* tp = nullptr;
+  if (has_t) {
+    CHECK_I64(*targets); CHECK_CONTIG(*targets);
+    TORCH_CHECK(targets->numel() == M && targets->device() == logits.device(), "logits_lse: targets int64 [M]");
+    tp = targets->data_ptr<int64_t>();
+    if (lp.has_value() && lp->defined()) {
+      CHECK_F32(*lp); CHECK_CONTIG(*lp);
+      TORCH_CHECK(lp->numel() == M && lp->device() == logits.device(), "logits_lse: lp fp32 [M]");
+      p = *lp;
+    } else {
+      p = at::zeros({M}, logits.options().dtype(at::kFloat));
+    }
+  } else {
+    TORCH_CHECK(!(lp.has_value() && lp->defined()), "logits_lse: lp needs targets");
+  }
+  mg::logits_lse(bp(logits), ld, (int)M, (int)V, tp, fp(l), has_t ? fp(p) : nullptr, cur_stream());
+  if (has_t) return py::make_tuple(l, p);
+  return py::cast(l);
 }
 
 // ------------------------------------------------------------------------------- native RCCL
@@ -846,10 +917,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
-        py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none());
+        py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none(),
+        py::arg("lse") = py::none(), py::arg("lp") = py::none());
   m.def("sample_kept", &sample_kept, py::arg("logits"), py::arg("V"), py::arg("params"));
   m.def("pick_ragged", &pick_ragged, py::arg("logits"), py::arg("V"), py::arg("params"), py::arg("pos"),
-        py::arg("done"), py::arg("tok"), py::arg("seq"), py::arg("greedy"));
+        py::arg("done"), py::arg("tok"), py::arg("seq"), py::arg("greedy"), py::arg("lse") = py::none(),
+        py::arg("lp") = py::none());
+  m.def("logits_lse", &logits_lse, py::arg("logits"), py::arg("V"), py::arg("targets") = py::none(),
+        py::arg("lse") = py::none(), py::arg("lp") = py::none());
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });

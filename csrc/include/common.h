@@ -242,6 +242,30 @@ MG_DEVICE float sample_gumbel(uint32_t r3, uint32_t i) {
   return -logf(t);
 }
 
+// ---------------------------------------------------------------- Per-token log-probabilities
+// The log-probability of token t for a row of bf16 logits l_0 .. l_{V-1} is the MODEL's
+// log-softmax: temperature 1, before top-k and top-p, natural log -- so greedy, sampled, ragged and
+// scored paths give one number for one (row, token), and the numbers of a sequence add up to its
+// log-likelihood.  With m the row maximum:
+//   q_i   = sample_mass(bits_i, m, 1.0f)      (the nucleus rule's fixed fp32 sequence; -inf weighs 0)
+//   Z^    = sum q_i                           (a 64-bit integer: the adds commute, V * 2^32 fits)
+//   lnz   = logf((float)Z^ * 2^-32)
+//   lp(t) = (float(l_t) - m) - lnz            (a greedy token has l_t = m: lp = -lnz)
+// {m, lnz} is a function of the row's values alone -- not of a reduction order, a workgroup size or
+// graph / eager launch -- and so is lp.  A target whose logit is -inf gets -inf.  A row without a
+// finite maximum is outside the rule (any value may come out, nothing faults).
+// Error against the real log-softmax of the same bf16 logits: Z^ / 2^32 is off from Z by at most
+// eps_w * Z + V * 2^-32 (above), and Z >= 1, so ln is off by at most eps_w + V * 2^-32 = 4.4e-6 +
+// V * 2^-32; the integer-to-float conversion (2^-24 relative) and an accurate logf (1 ulp of a
+// result in [0, ln V]) add at most 2^-23 * (ln V + 1); l_t - m is exact while the two bf16 exponents
+// are within 16 of each other and rounds to 2^-24 * |l_t - m| otherwise; the last subtraction adds
+// half an ulp, 2^-24 * |lp|.  |l_t - m| <= |lp|, so in all
+//   |lp^ - lp| <= 4.4e-6 + V * 2^-32 + 2^-23 * (ln V + 1) + 2^-23 * |lp|
+// (2.5e-5 at V = 50257, |lp| <= 64).  The tests take four times this, as the nucleus tests do.
+MG_DEVICE float logprob_lnz(unsigned long long Z) { return logf((float)Z * 0x1p-32f); }
+
+MG_DEVICE float token_logprob(uint32_t bits, float m, float lnz) { return (bf2f(bits) - m) - lnz; }
+
 // ---------------------------------------------------------------- GELU (tanh approximation)
 constexpr float kGeluK0 = 0.7978845608028654f;  // sqrt(2/pi)
 constexpr float kGeluK1 = 0.044715f;

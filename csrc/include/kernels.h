@@ -88,8 +88,11 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
 // seq, seq[b * seq_ld + *pos_dev + 1]; then a trailing one-thread kernel advances params[2] and
 // *pos_dev (when given) by one.
 constexpr int kSampleParamWords = 8;
+// lse, lp (optional, together, with seq): lse = the rows' {m, lnz} from logits_lse on the same logits,
+// lp fp32 laid out as seq; lp[b * seq_ld + *pos_dev + 1] = the drawn token's log-probability,
+// written exactly where and when the token is written to seq.
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
-                   int64_t* seq, long seq_ld, hipStream_t stream);
+                   int64_t* seq, long seq_ld, hipStream_t stream, const float* lse = nullptr, float* lp = nullptr);
 // The kept set of the same rule for the block's top_k / top_p / temperature, by the sampler's own
 // kernel with the Gumbel pass replaced: out[2 b] = the bf16 bit pattern of row b's lowest kept
 // value (-inf's when nothing is kept), out[2 b + 1] = the number of kept entries.  Writes only out.
@@ -100,9 +103,17 @@ void sample_kept(const bf16_t* logits, long ld, int B, int V, const uint32_t* pa
 // pos[b] + 1 and batch row b -- is written to tok[b] and seq[b, pos[b] + 1], pos[b] advances by one
 // and done[b] is set when t == (int)params[5] (the stop token; negative: none).  params[2] is not
 // used and nothing is advanced after the launch.  A row whose pos[b] + 1 would reach seq_ld - 1 is
-// left alone too.
+// left alone too.  lse, lp (optional, together): as for sample_logits -- lp[b, pos[b] + 1] is written
+// with seq[b, pos[b] + 1], so a finished row or a row at capacity writes neither.
 void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos, int* done, int64_t* tok,
-                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream);
+                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream, const float* lse = nullptr,
+                 float* lp = nullptr);
+// Per-token log-probabilities (the rule in common.h): lse[2 r] = the maximum m and lse[2 r + 1] =
+// lnz of row r of logits [M, ld] (layout as for sample_logits; one workgroup per row, integer mass
+// sum, no float atomics).  targets (optional, int64 [M]): lp[r] = the log-probability of token
+// targets[r]; a negative target (or one >= V) leaves lp[r] as it is.
+void logits_lse(const bf16_t* logits, long ld, int M, int V, const int64_t* targets, float* lse, float* lp,
+                hipStream_t stream);
 
 // elementwise.hip
 void bias_act_fwd(const bf16_t* x, const bf16_t* b, bf16_t* pre, bf16_t* y, long M, int N, int act,

@@ -30,6 +30,13 @@
 // Ragged batches (pick_ragged): every row has its own position, draw counter (position + 1) and
 // finished flag in device memory, read and written by the row's own workgroup only -- the sampler
 // in its RAGGED form or the greedy pick kernel, both ending in ragged_finish.  No advance kernel.
+//
+// Log-probabilities (logits_lse; the rule in common.h, 'Per-token log-probabilities'): one more
+// one-workgroup-per-row kernel over the same row in registers -- the maximum, then the 64-bit
+// integer sum of the sampler's own masses at temperature 1 by wave shuffle and LDS -- leaves
+// {m, lnz} per row, and with targets the log-probability of one given token per row (score).  The
+// pick kernels take that pair and write the picked token's log-probability beside the token, under
+// the conditions of the token's own store.
 #include "common.h"
 #include "kernels.h"
 
@@ -204,17 +211,33 @@ MG_DEVICE unsigned long long block_max_key(unsigned long long best, unsigned lon
   return best;
 }
 
+// sum of one 64-bit integer per thread over the workgroup, broadcast (integer adds: any order)
+MG_DEVICE unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += shfl_xor_u64(v, o);
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  unsigned long long t = 0ull;
+#pragma unroll
+  for (int i = 0; i < kWaves; ++i) t += red[i];
+  return t;
+}
+
 // Ragged decode: the end of row b's step, by one thread of the row's own workgroup.  p is the
 // row's position as the workgroup read it (pos[b]); the picked token t goes to tok[b] and
 // seq[b, p + 1], the position moves on, and the row is finished once t is the stop token
 // (params[5], negative: none).  Nobody else reads or writes pos[b], done[b], tok[b] or row b of
 // seq in this launch, so there is no hand-off and no trailing advance kernel.  The position never
 // reaches seq_ld - 1 = Tmax (the cache's and wpe's row count): a row that would is left as it is.
+// lp (optional, laid out as seq) gets the token's log-probability where seq gets the token: lse =
+// {m, lnz} of every row (logits_lse), row = the logits of row b.
 MG_DEVICE void ragged_finish(long t, int b, int p, int eos, int* pos, int* done, int64_t* tok, int64_t* seq,
-                             long seq_ld) {
+                             long seq_ld, const bf16_t* row, const float* lse, float* lp) {
   if (p < 0 || (long)p + 1 >= seq_ld - 1) return;
   tok[b] = t;
   seq[(long)b * seq_ld + p + 1] = t;
+  if (lp) lp[(long)b * seq_ld + p + 1] = token_logprob(row[t], lse[2 * b], lse[2 * b + 1]);
   pos[b] = p + 1;
   if (eos >= 0 && t == (long)eos) done[b] = 1;
 }
@@ -226,11 +249,14 @@ MG_DEVICE void ragged_finish(long t, int b, int p, int eos, int* pos, int* done,
 // KEPT (sample_kept): the same thresholds, then instead of the Gumbel pass the kept set itself --
 // kept_out[2 b] = the bf16 bits of the lowest kept value (-inf when nothing is kept),
 // kept_out[2 b + 1] = the number of kept entries; nothing else is written.
+// lse, lp (optional, together; lp needs seq): the drawn token's log-probability goes to lp where the
+// token goes to seq.
 template <bool RAGGED, bool KEPT>
 __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
                                                           const uint32_t* params, int* pos_dev, int* done,
                                                           int64_t* __restrict__ tok, int64_t* __restrict__ seq,
-                                                          long seq_ld, int* __restrict__ kept_out) {
+                                                          long seq_ld, int* __restrict__ kept_out,
+                                                          const float* __restrict__ lse, float* __restrict__ lp) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[256 * kCopies];  // or 256 x kMassCopies x 64 bits
   __shared__ uint32_t scan[kWaves + 2];
   __shared__ unsigned long long mscan[6];
@@ -418,23 +444,28 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     long t = (long)(0xffffffffu - (uint32_t)best);
     if (t >= V) t = V - 1;  // no candidate (a row without a finite maximum): still a valid id
     if constexpr (RAGGED) {
-      ragged_finish(t, b, rpos, (int)params[5], pos_dev, done, tok, seq, seq_ld);
+      ragged_finish(t, b, rpos, (int)params[5], pos_dev, done, tok, seq, seq_ld, row, lse, lp);
     } else {
       if (tok) tok[b] = t;
       if (seq) {
         const long p = (long)pos_dev[0] + 1;
-        if (p >= 0 && p < seq_ld) seq[(long)b * seq_ld + p] = t;
+        if (p >= 0 && p < seq_ld) {
+          seq[(long)b * seq_ld + p] = t;
+          if (lp) lp[(long)b * seq_ld + p] = token_logprob(row[t], lse[2 * b], lse[2 * b + 1]);
+        }
       }
     }
   }
 }
 
 // Ragged greedy pick: one workgroup per logits row, the argmax over the first V bf16 columns
-// (16-byte loads, first index on ties), then ragged_finish.
+// (16-byte loads, first index on ties), then ragged_finish (lse, lp: as for the sampler).
 __global__ __launch_bounds__(kThreads) void pick_greedy_kernel(const bf16_t* __restrict__ logits, long ld, int V,
                                                                const uint32_t* params, int* pos, int* done,
                                                                int64_t* __restrict__ tok,
-                                                               int64_t* __restrict__ seq, long seq_ld) {
+                                                               int64_t* __restrict__ seq, long seq_ld,
+                                                               const float* __restrict__ lse,
+                                                               float* __restrict__ lp) {
   __shared__ unsigned long long redk[kWaves];
   const int b = blockIdx.x;
   if (done[b]) return;  // the whole workgroup: a finished row changes nothing
@@ -463,7 +494,50 @@ __global__ __launch_bounds__(kThreads) void pick_greedy_kernel(const bf16_t* __r
   if (threadIdx.x == 0) {
     long t = (long)(0xffffffffu - (uint32_t)best);
     if (t >= V) t = V - 1;
-    ragged_finish(t, b, p, (int)params[5], pos, done, tok, seq, seq_ld);
+    ragged_finish(t, b, p, (int)params[5], pos, done, tok, seq, seq_ld, row, lse, lp);
+  }
+}
+
+// {m, lnz} of the log-probability rule (common.h) for every row of logits [M, ld], and with targets
+// (int64 [M]; negative or >= V: the row's lp is not written) lp[r] of the target.  The row is loaded
+// once into registers when it fits, as in the sampler; both passes stream a longer one.
+__global__ __launch_bounds__(kThreads) void lse_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                       const int64_t* __restrict__ targets,
+                                                       float* __restrict__ lse, float* __restrict__ lp) {
+  __shared__ float redf[kWaves];
+  __shared__ unsigned long long redq[kWaves];
+  const long r = blockIdx.x;
+  const bf16_t* row = logits + r * ld;
+  const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
+  const bool cached = nv <= kRegVec * kThreads;
+  uint4 regs[kRegVec];
+  uint32_t tail = 0u;
+  if (cached) {
+#pragma unroll
+    for (int j = 0; j < kRegVec; ++j) {
+      const int v = (int)threadIdx.x + j * kThreads;
+      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (threadIdx.x < 8 && ti < V) tail = row[ti];
+  }
+  auto sweep = [&](auto f) {
+    if (cached) for_regs(regs, tail, V, f);
+    else for_row(row, V, f);
+  };
+  float m = -INFINITY;
+  sweep([&](int, uint32_t bits) { m = fmaxf(m, bf2f(bits)); });
+  m = block_max<kWaves>(m, redf);
+  unsigned long long z = 0ull;
+  sweep([&](int, uint32_t bits) { z += sample_mass(bits, m, 1.0f); });
+  z = block_sum_u64(z, redq);
+  if (threadIdx.x == 0) {
+    const float lnz = logprob_lnz(z);
+    lse[2 * r] = m;
+    lse[2 * r + 1] = lnz;
+    if (targets) {
+      const long t = targets[r];
+      if (t >= 0 && t < V) lp[r] = token_logprob(row[t], m, lnz);
+    }
   }
 }
 
@@ -480,22 +554,28 @@ __global__ __launch_bounds__(64) void sample_advance_kernel(uint32_t* params, in
 namespace mg {
 
 void sample_logits(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos_dev, int64_t* tok,
-                   int64_t* seq, long seq_ld, hipStream_t stream) {
+                   int64_t* seq, long seq_ld, hipStream_t stream, const float* lse, float* lp) {
   sample_kernel<false, false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos_dev, nullptr, tok, seq, seq_ld,
-                                                          nullptr);
+                                                          nullptr, lse, lp);
   sample_advance_kernel<<<1, 64, 0, stream>>>(params, pos_dev);
 }
 
 void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, int* pos, int* done, int64_t* tok,
-                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream) {
-  if (greedy) pick_greedy_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld);
+                 int64_t* seq, long seq_ld, bool greedy, hipStream_t stream, const float* lse, float* lp) {
+  if (greedy)
+    pick_greedy_kernel<<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld, lse, lp);
   else sample_kernel<true, false><<<B, kThreads, 0, stream>>>(logits, ld, V, params, pos, done, tok, seq, seq_ld,
-                                                              nullptr);
+                                                              nullptr, lse, lp);
+}
+
+void logits_lse(const bf16_t* logits, long ld, int M, int V, const int64_t* targets, float* lse, float* lp,
+                hipStream_t stream) {
+  lse_kernel<<<M, kThreads, 0, stream>>>(logits, ld, V, targets, lse, lp);
 }
 
 void sample_kept(const bf16_t* logits, long ld, int B, int V, const uint32_t* params, int* out, hipStream_t stream) {
   sample_kernel<false, true><<<B, kThreads, 0, stream>>>(logits, ld, V, params, nullptr, nullptr, nullptr, nullptr, 0,
-                                                         out);
+                                                         out, nullptr, nullptr);
 }
 
 }  // namespace mg

@@ -24,6 +24,17 @@ kernel inside a device-side token loop, ``_GpuCache.sample``): reproducible per 
 Ragged batches (``generate_batch``): prompts of different lengths, right-padded, decoded together;
 each row has its own position and finished flag in device memory (``_GpuCache.ragged``), stops at
 its own stop token, and computes what the single-prompt path computes for that row alone.
+
+Log-probabilities (``return_logprobs=True``, ``score``): the model's log-softmax of a token given
+its prefix (temperature 1, before top-k / top-p; the rule in common.h).  The device loops compute it
+inside the captured step -- the plain LM head, the lse kernel (``logits_lse``), then the pick kernel
+writing the number beside the token -- in loops of their own (``"greedy_lp"``, ``"sample_lp"``,
+``("ragged_lp", greedy)``), so the plain loops launch what they always did.  Greedy with
+log-probabilities does not go through the LM head's fused argmax: carrying the number through the
+argmax keys would need the previous step's {m, lnz} in the next step's embedding kernel and a host
+epilogue for the last token; its step is the ragged greedy step on equal positions instead, which
+ranks the same stored bf16 logits with the first index on ties.  Host loops use
+``ops.reference.token_logprob``.
 """
 from __future__ import annotations
 
@@ -195,6 +206,18 @@ class _GpuCache:
         self._loops = {}  # the device-side token loops (_Loop) by name, built on first use
         self.prefill(idx, last)
 
+    @classmethod
+    def body_only(cls, model):
+        """The step bodies' plumbing (``_prompt``, ``_blocks``, ``_head``) without KV caches,
+        workspaces or loops: ``score`` runs one forward and never decodes."""
+        from ..ops._ext import ext
+        from ..ops import gemm as G
+
+        model.config.check_gpu_support()
+        self = cls.__new__(cls)
+        self.C, self.G, self.bf, self.model = ext(), G, bf16_weights(model), model
+        return self
+
     def _lin(self, skinny, inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
         """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first (fused into
         the skinny GEMM's staging at decode time)."""
@@ -235,10 +258,9 @@ class _GpuCache:
         return self._lin(skinny, x_last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8,
                          ln=m.transformer.ln_f, am=am)
 
-    def prefill(self, idx, last=None):
-        """Run the prompt idx [B, T] on the MFMA GEMM path, keep every layer's qkv rows as the
-        cache and set ``logits`` [B, V] to the last position's -- or, for a right-padded batch, to
-        those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
+    def _prompt(self, idx, keep=True):
+        """The blocks' output [B, T, D] for the prompt idx [B, T] on the MFMA GEMM path; ``keep``:
+        every layer's qkv rows go into the cache."""
         C, bf = self.C, self.bf
         tr, cfg = self.model.transformer, self.model.config
         B, T = idx.shape
@@ -246,10 +268,19 @@ class _GpuCache:
         x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0).view(B * T, D)
 
         def attend(i, qkv):
-            self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
+            if keep:
+                self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
             return C.attention_fwd(qkv, B, T, H, 0.0, 0)[0]
 
-        x = self._blocks(x, attend, False).view(B, T, D)
+        return self._blocks(x, attend, False).view(B, T, D)
+
+    def prefill(self, idx, last=None):
+        """Run the prompt idx [B, T] on the MFMA GEMM path, keep every layer's qkv rows as the
+        cache and set ``logits`` [B, V] to the last position's -- or, for a right-padded batch, to
+        those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
+        cfg = self.model.config
+        B = idx.size(0)
+        x = self._prompt(idx)
         if last is not None:  # right-padded prefill: row b's hidden state at its own last token
             x = x[torch.arange(B, device=x.device), last]
         else:
@@ -317,12 +348,57 @@ class _GpuCache:
         lp.run(1)
         return lp.logits
 
-    def greedy(self, tok, pos, n):
+    def with_logprob(self, tok):
+        """(tok, lp): token ``tok`` [B] picked from the prefill logits, with its log-probability
+        [B] from the lse kernel."""
+        return tok, self.C.logits_lse(self.logits, self.model.config.vocab_size, tok.contiguous())[1]
+
+    def _greedy_lp(self, tok, pos, n):
+        """``greedy`` with log-probabilities: (tokens [B, n], lp [B, n]).  A loop of its own
+        (``"greedy_lp"``) on the plain LM head, the lse kernel and the ragged greedy pick kernel,
+        with every row at the same position and no stop token -- not the fused argmax of the LM
+        head, whose keys have no room for the number.  Both rank the stored bf16 logits with the
+        first index on ties.  ``seq`` / ``lp`` are one column longer than the ragged state's: the
+        pick kernel keeps the position below the last column, and a window's last token sits at
+        column tmax."""
+        B = tok.shape[0]
+        V = self.model.config.vocab_size
+
+        def seed(st):
+            st["tok"].copy_(tok)
+            st["pos"].fill_(pos)
+
+        def make():
+            dev = tok.device
+            st = {"tok": tok.clone(), "pos": torch.full((B,), pos, dtype=torch.int32, device=dev),
+                  "done": torch.zeros(B, dtype=torch.int32, device=dev),
+                  "seq": torch.zeros(B, self.tmax + 2, dtype=torch.long, device=dev),
+                  "lp": torch.zeros(B, self.tmax + 2, dtype=torch.float32, device=dev),
+                  "params": torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=dev)}
+
+            def step():
+                logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
+                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], True,
+                                   self.C.logits_lse(logits, V), st["lp"])
+                return logits[:, :V]
+
+            return _Loop(step, st)
+
+        lp = self._loop("greedy_lp", make)
+        st = lp.state
+        seed(st)  # after the loop is built: its warm-up step moved the state
+        lp.run(n)
+        return st["seq"][:, pos + 1:pos + 1 + n], st["lp"][:, pos + 1:pos + 1 + n]
+
+    def greedy(self, tok, pos, n, logprobs=False):
         """n greedy decode steps starting with token ``tok`` [B, 1] at position ``pos``: the step
         takes its input token and position from device buffers that its own kernels advance (the
         fused argmax of ``_decode``; for a small vocabulary the argmax in torch).  Returns the n
-        new tokens [B, n] (positions pos + 1 .. pos + n)."""
+        new tokens [B, n] (positions pos + 1 .. pos + n); with ``logprobs`` also their
+        log-probabilities [B, n] (``_greedy_lp``)."""
         assert pos + n <= self.tmax
+        if logprobs:
+            return self._greedy_lp(tok, pos, n)
         B = tok.shape[0]
         cfg = self.model.config
         V = cfg.vocab_size
@@ -381,13 +457,15 @@ class _GpuCache:
         """The token [B] drawn from the prefill logits (the first token of a context window)."""
         return self.C.sample_logits(self.logits, self.model.config.vocab_size, self._sample_params(words))
 
-    def sample(self, tok, pos, n, words):
+    def sample(self, tok, pos, n, words, logprobs=False):
         """n sampled decode steps starting with token ``tok`` [B, 1] at position ``pos``: each step
         is the plain LM head followed by the sample kernel, which writes the next token into the
         buffer the next step's embedding reads and advances the device position and draw counter.
         Seed, temperature, top-k and top-p live in the device parameter block (``words``), so the one
         captured step serves every call.  Returns the n new tokens [B, n] (positions pos + 1 ..
-        pos + n)."""
+        pos + n).  ``logprobs``: a loop of its own (``"sample_lp"``) with the lse kernel between the
+        LM head and the sampler, which writes each token's log-probability beside it; returns
+        (tokens, lp [B, n])."""
         assert pos + n <= self.tmax
         B = tok.shape[0]
         V = self.model.config.vocab_size
@@ -396,20 +474,27 @@ class _GpuCache:
             dev = tok.device
             st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
                   "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev), "hpos": max(pos, 1)}
+            if logprobs:
+                st["lp"] = torch.zeros(B, self.tmax + 1, dtype=torch.float32, device=dev)
             params = self._sample_params(words)
 
             def step():
                 logits = self._decode(st["tok"], st["pos"], st["hpos"])
-                self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"])
+                if logprobs:
+                    self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"],
+                                         self.C.logits_lse(logits, V), st["lp"])
+                else:
+                    self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"])
                 return logits[:, :V]
 
             return _Loop(step, st)
 
-        lp = self._loop("sample", make)
+        lp = self._loop("sample_lp" if logprobs else "sample", make)
         self._seed(lp.state, tok, pos)
         self._sample_params(words)
         lp.run(n)
-        return lp.state["seq"][:, pos + 1:pos + 1 + n]
+        toks = lp.state["seq"][:, pos + 1:pos + 1 + n]
+        return (toks, lp.state["lp"][:, pos + 1:pos + 1 + n]) if logprobs else toks
 
     # ----------------------------------------------------------------- ragged batches
     def ragged_state(self):
@@ -437,22 +522,32 @@ class _GpuCache:
             st["params"].copy_(torch.tensor(words, dtype=torch.int32))
             self._rwords = list(words)
 
-    def ragged_start(self, idx, lengths, words, greedy):
+    def ragged_start(self, idx, lengths, words, greedy, logprobs=False):
         """Point the ragged state at a prefilled right-padded batch ``idx`` [B, Tp] with ``lengths``
         [B] (``self.logits`` = row b's logits at column lengths[b] - 1) and pick every row's first
-        token with the loop's own pick kernel: pos = lengths - 1 and done = 0 going in."""
+        token with the loop's own pick kernel: pos = lengths - 1 and done = 0 going in.
+        ``logprobs``: the state's ``lp`` buffer (float32, the shape of ``seq``; allocated on first
+        use) is zeroed with ``seq`` and gets the first tokens' log-probabilities."""
         st = self.ragged_state()
+        if logprobs:
+            if "lp" not in st:
+                st["lp"] = torch.zeros(st["seq"].shape, dtype=torch.float32, device=st["seq"].device)
+            st["lp"].zero_()
         st["seq"].zero_()
         st["seq"][:, :idx.size(1)].copy_(idx)
         st["pos"].copy_(lengths - 1)
         st["done"].zero_()
         self._ragged_params(st, words)
         logits = self.logits  # [B, V] view of the padded [B, ld] buffer the LM head wrote
-        self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
-                           greedy)
+        if logprobs:
+            self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
+                               greedy, self.C.logits_lse(logits, logits.size(1)), st["lp"])
+        else:
+            self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
+                               greedy)
         return st
 
-    def ragged(self, n, words, greedy):
+    def ragged(self, n, words, greedy, logprobs=False):
         """n decode steps of a ragged batch on the current device state (``ragged_state``): embed
         ``tok[b]`` at ``pos[b]``, the blocks with per-row decode attention, the plain LM head, then
         the pick kernel -- greedy argmax or the seeded draw with counter ``pos[b] + 1`` -- which
@@ -461,14 +556,20 @@ class _GpuCache:
         the same token and rewrites the same cache row), so the launch shapes never change: one
         loop per mode (``_loops[("ragged", greedy)]``).  Resumable: n calls of one step equal one
         call of n steps.  ``words``: the parameter block (``_ragged_words``).  Returns the state;
-        the last step's logits are the loop's ``logits``."""
+        the last step's logits are the loop's ``logits``.  ``logprobs`` (after a ``ragged_start``
+        with it): loops of their own (``("ragged_lp", greedy)``) with the lse kernel before the pick
+        kernel, which writes ``lp[b, pos[b] + 1]`` with the token."""
         st = self.ragged_state()
         self._ragged_params(st, words)
         V = self.model.config.vocab_size
 
         def step():
             logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
-            self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy)
+            if logprobs:
+                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy,
+                                   self.C.logits_lse(logits, V), st["lp"])
+            else:
+                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy)
             return logits[:, :V]
 
         def warm():  # with every row marked finished the step is idempotent: the state the caller
@@ -477,7 +578,7 @@ class _GpuCache:
             step()
             st["done"].copy_(done)
 
-        self._loop(("ragged", greedy), lambda: _Loop(step, st, warm)).run(n)
+        self._loop(("ragged_lp" if logprobs else "ragged", greedy), lambda: _Loop(step, st, warm)).run(n)
         return st
 
 
@@ -520,8 +621,15 @@ def _gpu_cache(model, idx, tmax, last=None):
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
-             top_p: Optional[float] = None):
-    """``top_p`` (with ``do_sample``): nucleus filtering after the temperature and top-k -- keep the
+             top_p: Optional[float] = None, return_logprobs: bool = False):
+    """``return_logprobs``: return ``(idx, logprobs)``, ``logprobs`` float32 of ``idx``'s shape --
+    entry [b, j] is the model's log-probability of ``idx[b, j]`` given ``idx[b, :j]`` (the cropped
+    window past ``block_size``, as for the token itself) at every generated position and 0.0 at the
+    prompt's.  It is the log-softmax of the model's logits at temperature 1, before top-k and
+    top-p, whatever the sampling settings (the rule in common.h): on the device loops from the lse
+    kernel inside the captured step, on the host loops from ``ops.reference.token_logprob``.
+
+    ``top_p`` (with ``do_sample``): nucleus filtering after the temperature and top-k -- keep the
     tokens whose probability mass strictly above them is below ``top_p`` of the total, ties kept
     together (the rule in common.h); None or 1.0 is off.  With a seed it is a word of the sample
     kernel's parameter block, so the captured loop serves any value.
@@ -542,6 +650,16 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             return R.sample_gumbel(logits, temperature, top_k, seed, col, top_p=top_p)
         return _sample(logits, temperature, do_sample, top_k, top_p)
 
+    lps = []  # host loops: one [B] per generated token
+
+    def done(idx):
+        if not return_logprobs:
+            return idx
+        lp = torch.zeros(idx.shape, dtype=torch.float32, device=idx.device)
+        if lps:
+            lp[:, idx.size(1) - len(lps):] = torch.stack(lps, dim=1)
+        return idx, lp
+
     # ZeRO-1: the KV-cache path launches the kernels directly (never model.forward), so neither
     # the fused ops' per-bucket waits nor the engine's forward pre-hook run: wait here for every
     # in-flight parameter all-gather (stream-ordered) before any decode kernel reads the weights
@@ -550,13 +668,25 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         for _ in range(max_new_tokens):
             idx_cond = idx if idx.size(1) <= bs else idx[:, -bs:]
             logits, _ = model(idx_cond)
-            idx = torch.cat((idx, pick(logits[:, -1, :], idx.size(1))), dim=1)
-        return idx
+            nxt = pick(logits[:, -1, :], idx.size(1))
+            if return_logprobs:
+                lps.append(R.token_logprob(logits[:, -1, :], nxt))
+            idx = torch.cat((idx, nxt), dim=1)
+        return done(idx)
     if idx.is_cuda and not do_sample and max_new_tokens > 0:
+        if return_logprobs:
+            return _generate_windowed_gpu(model, idx, max_new_tokens,
+                                          lambda c, T: c.with_logprob(c.logits.argmax(-1)),
+                                          lambda c, tok, L, n, T: c.greedy(tok, L, n, logprobs=True), True)
         return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.logits.argmax(-1),
                                       lambda c, tok, L, n, T: c.greedy(tok, L, n))
     if idx.is_cuda and seeded and max_new_tokens > 0:  # the draw counter of a token is its column T
         words = lambda T: _sample_words(seed, T, temperature, top_k, top_p)
+        if return_logprobs:
+            return _generate_windowed_gpu(model, idx, max_new_tokens,
+                                          lambda c, T: c.with_logprob(c.sample_prefill(words(T))),
+                                          lambda c, tok, L, n, T: c.sample(tok, L, n, words(T), logprobs=True),
+                                          True)
         return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.sample_prefill(words(T)),
                                       lambda c, tok, L, n, T: c.sample(tok, L, n, words(T)))
     cache = None
@@ -568,39 +698,49 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             cache.pos = idx_cond.size(1)
             logits = cache.logits
         idx_next = pick(logits, T)
+        if return_logprobs:
+            lps.append(R.token_logprob(logits, idx_next))
         idx = torch.cat((idx, idx_next), dim=1)
         if idx.size(1) > bs:
             cache = None  # window slides: rebuild from the cropped context next step
             continue
         logits = cache.step(idx_next, cache.pos)
         cache.pos += 1
-    return idx
+    return done(idx)
 
 
-def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop):
+def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False):
     """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
     window's first token ``first(cache, T)`` [B], then the device-side token loop ``loop(cache,
     tok, L, n, T)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
     position ``L``) for every position the window still has room for.  ``T`` is the column of the
     call's first token in the returned sequence.  Once the sequence outgrows block_size, each token
     is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
-    (``/root/reference/mingpt/model.py:333``)."""
+    (``/root/reference/mingpt/model.py:333``).  ``logprobs``: ``first`` and ``loop`` return (tokens,
+    log-probabilities) pairs, and so does this."""
     bs = model.block_size
     B, T0 = idx.shape
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
     out[:, :T0] = idx
+    lp = torch.zeros(out.shape, dtype=torch.float32, device=idx.device) if logprobs else None
     T, end = T0, T0 + max_new_tokens
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
         cache = _gpu_cache(model, ctx, bs)
-        out[:, T] = first(cache, T)
+        if logprobs:
+            out[:, T], lp[:, T] = first(cache, T)
+        else:
+            out[:, T] = first(cache, T)
         T += 1
         n = min(end - T, bs - L)
         if n > 0:
-            out[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
+            if logprobs:
+                out[:, T:T + n], lp[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
+            else:
+                out[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
             T += n
-    return out
+    return (out, lp) if logprobs else out
 
 
 # --------------------------------------------------------------------------- ragged batches
@@ -608,22 +748,22 @@ _EARLY_EXIT = True  # set False to replay every step even after every row has st
 _EXIT_EVERY = 16    # replays between two reads of the finished flags
 
 
-def _ragged_prompts(prompts):
+def _ragged_prompts(prompts, who="generate_batch"):
     """(rows, device): the unpadded int64 prompts of either input form, on the first one's device."""
     if isinstance(prompts, tuple) and len(prompts) == 2 and torch.is_tensor(prompts[0]) and prompts[0].dim() == 2:
         idx, lengths = prompts
         lengths = torch.as_tensor(lengths).to("cpu", torch.long).view(-1)
         if lengths.numel() != idx.size(0):
-            raise ValueError(f"generate_batch: {idx.size(0)} rows, {lengths.numel()} lengths")
+            raise ValueError(f"{who}: {idx.size(0)} rows, {lengths.numel()} lengths")
         if lengths.numel() and (int(lengths.min()) < 1 or int(lengths.max()) > idx.size(1)):
-            raise ValueError(f"generate_batch: every length must be in 1..{idx.size(1)}, got {lengths.tolist()}")
+            raise ValueError(f"{who}: every length must be in 1..{idx.size(1)}, got {lengths.tolist()}")
         rows = [idx[b, :int(n)] for b, n in enumerate(lengths.tolist())]
     else:
         rows = [torch.as_tensor(p) for p in prompts]
         if any(r.dim() != 1 or r.numel() < 1 for r in rows):
-            raise ValueError("generate_batch: every prompt must be a 1-D tensor of 1 or more tokens")
+            raise ValueError(f"{who}: every prompt must be a 1-D tensor of 1 or more tokens")
     if not rows:
-        raise ValueError("generate_batch: no prompts")
+        raise ValueError(f"{who}: no prompts")
     device = rows[0].device
     return [r.to(device=device, dtype=torch.long) for r in rows], device
 
@@ -631,8 +771,12 @@ def _ragged_prompts(prompts):
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                    top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
-                   pad_token: int = 0, top_p: Optional[float] = None):
-    """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``.
+                   pad_token: int = 0, top_p: Optional[float] = None, return_logprobs: bool = False):
+    """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``, or
+    with ``return_logprobs`` ``(tokens, lengths, logprobs)``: float32 of ``tokens``' shape, entry
+    [b, j] the model's log-probability of ``tokens[b, j]`` given ``tokens[b, :j]`` at every generated
+    position (the stop token included) and 0.0 at prompt and padding positions -- the number
+    ``generate(return_logprobs=True)`` gives for the row alone.
 
     ``prompts``: a sequence of 1-D int64 tensors (1 or more tokens each), or a pair ``(idx [B, Tp]
     right-padded, lengths [B])`` -- positions at or past a row's length are ignored, whatever they
@@ -676,11 +820,12 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     lo, hi = tokens.aminmax()  # the padding is pad_token, a valid id
     if int(lo) < 0 or int(hi) >= V:
         raise ValueError(f"generate_batch: prompt token outside [0, {V})")
+    logprobs = torch.zeros(tokens.shape, dtype=torch.float32, device=device) if return_logprobs else None
     if max_new_tokens == 0:
-        return tokens, lengths
+        return (tokens, lengths, logprobs) if return_logprobs else (tokens, lengths)
     if device.type == "cuda":
         return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
-                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p)
+                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs)
     for b, r in enumerate(rows):  # the executable definition of the semantics
         cache = _CpuCache(model, r.view(1, -1))
         logits, n = cache.logits, lens[b]
@@ -690,33 +835,36 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
             else:
                 nxt = logits.argmax(dim=-1, keepdim=True)
             tokens[b, n] = nxt.view(())
+            if return_logprobs:
+                logprobs[b, n] = R.token_logprob(logits, nxt).view(())
             n += 1
             if eos_token is not None and int(nxt) == int(eos_token):
                 break
             if n < lens[b] + max_new_tokens:
                 logits = cache.step(nxt, n - 1)
         lengths[b] = n
-    return tokens, lengths
+    return (tokens, lengths, logprobs) if return_logprobs else (tokens, lengths)
 
 
 def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
-                        pad_token, top_p=None):
+                        pad_token, top_p=None, logprobs=False):
     """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
     causal attention makes every position before a row's length exact -- take row b's logits at
     column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
     ragged step max_new_tokens - 1 times.  With a stop token the finished flags are read every
     ``_EXIT_EVERY`` replays; stopping early changes nothing, since a step leaves finished rows as
-    they are."""
+    they are.  ``logprobs``: the loops with the lse kernel, and the state's ``lp`` buffer (zero but
+    at the generated positions) as a third result."""
     B, Lmax = idx.shape
     cache = _gpu_cache(model, idx, model.block_size, last=lengths - 1)
     words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
-    st = cache.ragged_start(idx, lengths, words, greedy)
+    st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs)
     n = max_new_tokens - 1
     check = _EARLY_EXIT and eos_token is not None  # without a stop token no row finishes early
     while n > 0:
         k = min(n, _EXIT_EVERY) if check else n
-        cache.ragged(k, words, greedy)
+        cache.ragged(k, words, greedy, logprobs=logprobs)
         n -= k
         if check and n > 0 and bool(st["done"].all()):
             break
@@ -724,4 +872,79 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     W = Lmax + max_new_tokens
     cols = torch.arange(W, device=idx.device).view(1, W)
     tokens = torch.where(cols < out_len.view(B, 1), st["seq"][:, :W], torch.full_like(cols, pad_token))
+    if logprobs:
+        return tokens, out_len, st["lp"][:, :W].clone()
     return tokens, out_len
+
+
+# --------------------------------------------------------------------------- scoring
+_SCORE_LOGITS_BYTES = 256 << 20  # cap on the transient bf16 logits of one LM-head chunk in score()
+
+
+@torch.no_grad()
+def score(model, idx, lengths=None):
+    """Log-probabilities of given sequences: float32 [B, T], ``out[b, j]`` = the model's
+    log-probability of ``idx[b, j]`` given ``idx[b, :j]`` (the rule in common.h: log-softmax at
+    temperature 1) for 1 <= j < lengths[b], and 0.0 elsewhere, column 0 included.  A row's sum is
+    its log-likelihood given its first token.
+
+    ``idx``: a sequence of 1-D int64 tensors, or a right-padded [B, T] tensor with ``lengths`` [B]
+    (None: every row is full) -- the input forms of ``generate_batch``; a pair ``(idx, lengths)`` is
+    accepted too.  T must fit ``block_size`` and every token be in [0, V) (ValueError).  Runs in
+    eval mode (no dropout) whatever ``model.training`` says, and leaves that flag as it was.
+
+    GPU: one forward of the blocks on the MFMA path (the prefill's body), then the LM head in row
+    chunks whose transient bf16 logits stay under ``_SCORE_LOGITS_BYTES`` (256 MiB; at least one
+    row), each through the lse kernel with the next tokens as targets (``logits_lse``) -- the
+    [B, T, V] logits never exist at once and nothing is read back in fp32.  CPU: the model's
+    forward and ``ops.reference.token_logprob``."""
+    if isinstance(idx, tuple) and lengths is None:
+        prompts = idx
+    elif torch.is_tensor(idx) and idx.dim() == 2:
+        prompts = (idx, torch.full((idx.size(0),), idx.size(1)) if lengths is None else lengths)
+    elif lengths is not None:
+        raise ValueError("score: lengths go with a 2-D idx")
+    else:
+        prompts = idx
+    rows, device = _ragged_prompts(prompts, "score")
+    V, bs = model.config.vocab_size, model.block_size
+    lens = [r.numel() for r in rows]
+    B = len(rows)
+    T = prompts[0].size(1) if isinstance(prompts, tuple) else max(lens)
+    if T > bs:
+        raise ValueError(f"score: sequence length {T} exceeds block_size ({bs})")
+    tokens = torch.zeros((B, T), dtype=torch.long, device=device)
+    for b, r in enumerate(rows):
+        tokens[b, :lens[b]] = r
+    lo, hi = tokens.aminmax()  # the padding is 0, a valid id
+    if int(lo) < 0 or int(hi) >= V:
+        raise ValueError(f"score: token outside [0, {V})")
+    before_use(*model.parameters())
+    out = torch.zeros((B, T), dtype=torch.float32, device=device)
+    if T == 1:
+        return out
+    cols = torch.arange(1, T, device=device).view(1, T - 1)
+    valid = cols < torch.tensor(lens, device=device).view(B, 1)  # [B, T - 1]: column j has a target
+    if device.type != "cuda":
+        was = model.training
+        model.eval()
+        try:
+            logits, _ = model(tokens)
+        finally:
+            model.train(was)
+        lp = R.token_logprob(logits[:, :-1], tokens[:, 1:])
+        out[:, 1:] = torch.where(valid, lp, torch.zeros_like(lp))
+        return out
+    c = _GpuCache.body_only(model)
+    D = model.config.n_embed
+    x = c._prompt(tokens, keep=False).view(B * T, D)
+    targets = torch.full((B, T), -1, dtype=torch.long, device=device)  # row (b, t) predicts column t + 1
+    targets[:, :-1] = torch.where(valid, tokens[:, 1:], targets[:, 1:])
+    targets = targets.view(B * T)
+    lp = torch.zeros(B * T, dtype=torch.float32, device=device)
+    step = max(1, _SCORE_LOGITS_BYTES // (2 * ((V + 7) // 8 * 8)))
+    for r0 in range(0, B * T, step):
+        r1 = min(B * T, r0 + step)
+        c.C.logits_lse(c._head(x[r0:r1], False), V, targets[r0:r1], None, lp[r0:r1])
+    out[:, 1:] = lp.view(B, T)[:, :-1]
+    return out

@@ -219,28 +219,43 @@ class GPT(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                  top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
-                 top_p: Optional[float] = None):
+                 top_p: Optional[float] = None, return_logprobs: bool = False):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
         prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
         ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
         (``generation.generate``); None draws from torch's global generator as before.  ``top_p``:
-        nucleus filtering after the temperature and top-k (None or 1.0: off)."""
+        nucleus filtering after the temperature and top-k (None or 1.0: off).  ``return_logprobs``:
+        returns ``(idx, logprobs)``, the model's log-probability of every generated token (0.0 at
+        the prompt)."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
-                        top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p)
+                        top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                        top_k: Optional[int] = None, seed: Optional[int] = None,
-                       eos_token: Optional[int] = None, pad_token: int = 0, top_p: Optional[float] = None):
+                       eos_token: Optional[int] = None, pad_token: int = 0, top_p: Optional[float] = None,
+                       return_logprobs: bool = False):
         """Decode prompts of different lengths in one batch, each row stopping at ``eos_token`` or
         after ``max_new_tokens``; returns ``(tokens, lengths)`` (``generation.generate_batch``).  No
-        sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``."""
+        sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``.
+        ``return_logprobs``: returns ``(tokens, lengths, logprobs)``."""
         from .generation import generate_batch
 
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, do_sample=do_sample,
-                              top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token, top_p=top_p)
+                              top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token, top_p=top_p,
+                              return_logprobs=return_logprobs)
+
+    @torch.no_grad()
+    def score(self, idx, lengths=None):
+        """Per-token log-probabilities of given sequences, float32 [B, T]: ``out[b, j]`` is the
+        log-probability of ``idx[b, j]`` given ``idx[b, :j]`` for 1 <= j < lengths[b], 0.0 elsewhere
+        (``generation.score``).  ``idx``: a list of 1-D prompts, or [B, T] right-padded with
+        ``lengths``."""
+        from .generation import score
+
+        return score(self, idx, lengths)
 
     # -------------------------------------------------------------------------------- optimizer
     def configure_optimizers(self, train_config):

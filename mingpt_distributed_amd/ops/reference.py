@@ -151,6 +151,17 @@ def sample_gumbel(logits: torch.Tensor, temperature: float, top_k, seed: int, dr
     return score.argmax(dim=-1, keepdim=True)
 
 
+def token_logprob(logits: torch.Tensor, tok: torch.Tensor) -> torch.Tensor:
+    """Log-probability of token ``tok[..., r]`` under row r of ``logits`` [..., V]: the rule of
+    ``csrc/include/common.h`` ('Per-token log-probabilities') over the reals -- the model's
+    log-softmax (temperature 1, before top-k / top-p), in fp64 on the logits as stored (bf16 values
+    for a bf16 model), cast to float32.  ``tok``: int64 of the logits' leading shape (a trailing
+    dimension of 1 is accepted).  Returns float32 of the leading shape."""
+    lead = logits.shape[:-1]
+    lp = F.log_softmax(logits.double(), dim=-1)
+    return lp.gather(-1, tok.reshape(*lead, 1)).reshape(lead).float()
+
+
 def cross_entropy(logits, targets, ignore_index: int = -1):
     return F.cross_entropy(logits.reshape(-1, logits.size(-1)).float(), targets.reshape(-1),
                            ignore_index=ignore_index)

@@ -17,8 +17,12 @@ decoded together in one ragged batch (``GPT.generate_batch``): every prompt keep
 
     python projects/generate/generate.py --weights /path/to/gpt2 --prompt "The capital of France" \
         --prompt "Once upon a time, in a land far away," --num-samples 2 --steps 40 --device cuda
+
+``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
+the model (temperature 1, before top-k / top-p) and their per-token perplexity.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -45,6 +49,8 @@ def main(argv=None):
                     help="nucleus filtering after the temperature and top-k (default: off)")
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--greedy", action="store_true")
+    ap.add_argument("--logprobs", action="store_true",
+                    help="print each sample's summed log-probability and per-token perplexity")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -76,15 +82,26 @@ def main(argv=None):
     else:
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
     x = x.expand(a.num_samples, -1).contiguous()
+    kw = {"return_logprobs": True} if a.logprobs else {}
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
-                       top_k=a.top_k, seed=a.seed, top_p=a.top_p)
+                       top_k=a.top_k, seed=a.seed, top_p=a.top_p, **kw)
+    y, lp = y if a.logprobs else (y, None)
     outs = []
     for i in range(a.num_samples):
         out = tok.decode(y[i].cpu().squeeze()) if tok is not None else y[i].tolist()
         outs.append(out)
         print("-" * 80)
         print(out)
+        if lp is not None:
+            print_logprob(lp[i, x.size(1):])
     return outs
+
+
+def print_logprob(lp):
+    """The summed log-probability of a sample's generated tokens ``lp`` (1-D) and their perplexity."""
+    total, n = float(lp.double().sum()), lp.numel()
+    ppl = math.exp(-total / n) if n else float("nan")
+    print(f"[logprob {total:.4f} over {n} tokens, perplexity {ppl:.4f}]")
 
 
 def generate_many(model, tok, texts, a, dev):
@@ -98,8 +115,10 @@ def generate_many(model, tok, texts, a, dev):
         rows = [torch.tensor([int(w) for w in t.split()] or [0], dtype=torch.long) for t in texts]
         eos = None
     rows = [r.to(dev) for r in rows for _ in range(a.num_samples)]
-    y, n = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
-                                top_k=a.top_k, seed=a.seed, eos_token=eos, top_p=a.top_p)
+    kw = {"return_logprobs": True} if a.logprobs else {}
+    y, n, *lp = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature,
+                                     do_sample=not a.greedy, top_k=a.top_k, seed=a.seed, eos_token=eos,
+                                     top_p=a.top_p, **kw)
     outs = []
     for i in range(len(rows)):
         ids = y[i, :int(n[i])].cpu()
@@ -107,6 +126,8 @@ def generate_many(model, tok, texts, a, dev):
         outs.append(out)
         print("-" * 80)
         print(out)
+        if lp:
+            print_logprob(lp[0][i, rows[i].numel():int(n[i])])
     return outs
 
 
