@@ -117,8 +117,47 @@ def logprobs(model, a):
         print(json.dumps(res), flush=True)
 
 
+def beams(model, a):
+    """Beam search per beam count W of --beams: ``generate_beam`` on one prompt of --prompt tokens,
+    next to the same row count through ``generate_batch(return_logprobs=True)`` greedy (W copies of
+    the prompt: the same decode step and lse kernel without the search).  Tokens/s of the best
+    beam (--new tokens per call) and microseconds per step, median of --reps alternating runs with
+    the spread.  --per-layer launches the cache reorder once per layer instead of once."""
+    import statistics
+
+    from mingpt_distributed_amd.models import generation as gen
+
+    gen._BEAM_REORDER_PER_LAYER = bool(a.per_layer)
+    idx = torch.randint(0, 50257, (1, a.prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    for W in map(int, a.beams.split(",")):
+        rows = [idx[0]] * W
+        cases = {"beam": lambda: model.generate_beam(idx, a.new, W)[0],
+                 "rows_logprobs": lambda: model.generate_batch(rows, a.new, return_logprobs=True)[0]}
+        with torch.no_grad():
+            for fn in cases.values():  # warm-up at the timed shapes (kernels, states, graph capture)
+                fn()
+            times = {k: [] for k in cases}
+            for _ in range(a.reps):
+                for k, fn in cases.items():
+                    times[k].append(timed(fn)[1])
+        res = {"metric": "beam search: best-beam tokens/s and us per step", "model": "gpt2 (random init)",
+               "beams": W, "prompt": a.prompt, "new_tokens": a.new, "reps": a.reps,
+               "reorder": "per layer" if a.per_layer else "one launch"}
+        for k, ts in times.items():
+            res[k + "_tok_s"] = round(a.new / statistics.median(ts), 1)
+            res[k + "_tok_s_range"] = [round(a.new / max(ts), 1), round(a.new / min(ts), 1)]
+            res[k + "_us_per_step"] = round(statistics.median(ts) / a.new * 1e6, 1)
+        res["beam_over_rows_time"] = round(statistics.median(times["beam"]) /
+                                           statistics.median(times["rows_logprobs"]), 4)
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--beams", default=None,
+                    help="time generate_beam at these beam counts (e.g. 1,4,8) on one prompt, beside the same "
+                         "row count through generate_batch(return_logprobs=True)")
+    ap.add_argument("--per-layer", action="store_true", help="--beams: one cache-reorder launch per layer")
     ap.add_argument("--prompt", type=int, default=32)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--batches", default="1,8")
@@ -144,6 +183,8 @@ def main():
     torch.manual_seed(0)
     ours = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
+    if a.beams:
+        return beams(ours, a)
     if a.logprobs:
         return logprobs(ours, a)
     if a.ragged:

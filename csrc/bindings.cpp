@@ -770,8 +770,106 @@ py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<a
   return py::cast(l);
 }
 
+// ------------------------------------------------------------------------------- beam search
+// beam.hip (kernels.h).  Every per-beam buffer has R = B * W elements, row b * W + w = beam w of
+// prompt b; all of them live on the logits' / the cache's device and are updated in place.
+void beam_i32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
+              op, ": ", name, " must be int32 with ", n, " elements on the operands' device");
+}
+
+void beam_f32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
+              op, ": ", name, " must be float32 with ", n, " elements on the operands' device");
+}
+
+// The row kernel on logits [R, ld] bf16 (columns >= V never read): writes cand_tok int32 [R, W],
+// cand_c fp32 [R, W] and lse fp32 [R, 2] from score fp32 [R], fin int32 [R] and ctl int32 [4].
+void beam_rows(const at::Tensor& logits, int64_t V, int64_t W, const at::Tensor& score, const at::Tensor& fin,
+               const at::Tensor& ctl, const at::Tensor& cand_tok, const at::Tensor& cand_c, const at::Tensor& lse) {
+  CHECK_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "beam_rows: logits [R, ld], unit column stride");
+  const int64_t R = logits.size(0), ld = R > 1 ? logits.stride(0) : 0;  // one row: no stride
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (R == 1 || ld >= logits.size(1)), "beam_rows: 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "beam_rows: rows must be 16-byte aligned (ld % 8 == 0)");
+  TORCH_CHECK(W >= 1 && W <= mg::kBeamMax && W <= V && R % W == 0 && R <= 0x7fffffff,
+              "beam_rows: 1 <= W <= 8, W <= V, R a multiple of W");
+  TORCH_CHECK(V <= (1 << 25), "beam_rows: V above 2^25 (a thread counts its elements in 16 bits)");
+  const at::Device dev = logits.device();
+  beam_f32("beam_rows", "score", score, R, dev);
+  beam_i32("beam_rows", "fin", fin, R, dev);
+  beam_i32("beam_rows", "ctl", ctl, mg::kBeamCtlWords, dev);
+  beam_i32("beam_rows", "cand_tok", cand_tok, R * W, dev);
+  beam_f32("beam_rows", "cand_c", cand_c, R * W, dev);
+  beam_f32("beam_rows", "lse", lse, 2 * R, dev);
+  DevGuard g(dev);
+  mg::beam_rows(bp(logits), ld, (int)R, (int)V, (int)W, fp(score), fin.data_ptr<int>(), ctl.data_ptr<int>(),
+                cand_tok.data_ptr<int>(), fp(cand_c), fp(lse), cur_stream());
+}
+
+// The merge kernel: cand_tok / cand_c [R, W] -> score, fin, len, tok (int64 [R]), parent and column
+// ctl[0] of hist_parent / hist_tok (int32 [R, Lh]) / hist_score (fp32 [R, Lh]); pos int32 [1] advances.
+void beam_merge(int64_t W, int64_t V, const at::Tensor& cand_tok, const at::Tensor& cand_c, const at::Tensor& score,
+                const at::Tensor& fin, const at::Tensor& len, const at::Tensor& tok, const at::Tensor& parent,
+                const at::Tensor& hist_parent, const at::Tensor& hist_tok, const at::Tensor& hist_score,
+                const at::Tensor& pos, const at::Tensor& ctl) {
+  CHECK_DEV(score);
+  TORCH_CHECK(W >= 1 && W <= mg::kBeamMax && W <= V && V <= 0x7fffffff, "beam_merge: 1 <= W <= 8, W <= V");
+  const int64_t R = score.numel();
+  TORCH_CHECK(R >= W && R % W == 0 && R <= 0x7fffffff, "beam_merge: score with B * W elements");
+  const at::Device dev = score.device();
+  beam_f32("beam_merge", "score", score, R, dev);
+  beam_i32("beam_merge", "cand_tok", cand_tok, R * W, dev);
+  beam_f32("beam_merge", "cand_c", cand_c, R * W, dev);
+  beam_i32("beam_merge", "fin", fin, R, dev);
+  beam_i32("beam_merge", "len", len, R, dev);
+  beam_i32("beam_merge", "parent", parent, R, dev);
+  CHECK_I64(tok); CHECK_CONTIG(tok);
+  TORCH_CHECK(tok.numel() == R && tok.device() == dev, "beam_merge: tok int64 with B * W elements");
+  TORCH_CHECK(hist_parent.dim() >= 2 && hist_parent.size(-1) >= 1, "beam_merge: histories [B, W, Lh]");
+  const int64_t Lh = hist_parent.size(-1);
+  beam_i32("beam_merge", "hist_parent", hist_parent, R * Lh, dev);
+  beam_i32("beam_merge", "hist_tok", hist_tok, R * Lh, dev);
+  beam_f32("beam_merge", "hist_score", hist_score, R * Lh, dev);
+  beam_i32("beam_merge", "pos", pos, 1, dev);
+  beam_i32("beam_merge", "ctl", ctl, mg::kBeamCtlWords, dev);
+  DevGuard g(dev);
+  mg::beam_merge((int)(R / W), (int)W, (int)V, cand_tok.data_ptr<int>(), fp(cand_c), fp(score), fin.data_ptr<int>(),
+                 len.data_ptr<int>(), tok.data_ptr<int64_t>(), parent.data_ptr<int>(), hist_parent.data_ptr<int>(),
+                 hist_tok.data_ptr<int>(), fp(hist_score), Lh, pos.data_ptr<int>(), ctl.data_ptr<int>(), cur_stream());
+}
+
+// The cache reorder on kv [L, R, Tmax, 3 D] bf16 (one layer: [1, R, Tmax, 3 D]; layers may be a
+// strided stack of contiguous [R, Tmax, 3 D] blocks), parent int32 [R], pos int32 [1]: rows t < pos.
+// ctl (optional): its history column advances.
+void beam_reorder(const at::Tensor& kv, int64_t W, const at::Tensor& parent, const at::Tensor& pos,
+                  const c10::optional<at::Tensor>& ctl) {
+  CHECK_BF16(kv);
+  TORCH_CHECK(kv.dim() == 4 && kv.size(0) >= 1 && kv[0].is_contiguous() && kv.size(3) % 3 == 0,
+              "beam_reorder: kv [L, R, Tmax, 3 D], every layer contiguous");
+  const int64_t L = kv.size(0), R = kv.size(1), Tmax = kv.size(2), D = kv.size(3) / 3;
+  const int64_t ls = L > 1 ? kv.stride(0) : 0;
+  TORCH_CHECK(W >= 1 && W <= mg::kBeamMax && R >= W && R % W == 0, "beam_reorder: 1 <= W <= 8, R a multiple of W");
+  TORCH_CHECK(D >= 8 && D % 8 == 0 && reinterpret_cast<uintptr_t>(kv.data_ptr()) % 16 == 0 && ls % 8 == 0 && ls >= 0,
+              "beam_reorder: D % 8 == 0 and 16-byte aligned layers");
+  TORCH_CHECK(Tmax >= 1 && Tmax * (D / 4) <= 0x7fffffff - 256 && R / W <= 65535 && L <= 65535,
+              "beam_reorder: cache too large for one launch");
+  const at::Device dev = kv.device();
+  beam_i32("beam_reorder", "parent", parent, R, dev);
+  beam_i32("beam_reorder", "pos", pos, 1, dev);
+  int* cp = nullptr;
+  if (ctl.has_value() && ctl->defined()) {
+    beam_i32("beam_reorder", "ctl", *ctl, mg::kBeamCtlWords, dev);
+    cp = ctl->data_ptr<int>();
+  }
+  DevGuard g(dev);
+  mg::beam_reorder(bp(kv), (int)L, ls, (int)(R / W), (int)W, (int)Tmax, (int)D, parent.data_ptr<int>(),
+                   pos.data_ptr<int>(), cp, cur_stream());
+}
+
 // ------------------------------------------------------------------------------- native RCCL
-// csrc/comm/rccl_comm.cpp.  Every collective runs on the communicator's comm stream after the
+// csrc/comm/rccl_comm.cpp. Every collective runs on the communicator's comm stream after the
 // tensor's device's CURRENT stream (the producers); comm_wait makes that stream wait again.
 mg::comm::DType comm_dtype(const at::Tensor& t) {
   switch (t.scalar_type()) {
@@ -925,6 +1023,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lp") = py::none());
   m.def("logits_lse", &logits_lse, py::arg("logits"), py::arg("V"), py::arg("targets") = py::none(),
         py::arg("lse") = py::none(), py::arg("lp") = py::none());
+  m.def("beam_rows", &beam_rows, py::arg("logits"), py::arg("V"), py::arg("W"), py::arg("score"), py::arg("fin"),
+        py::arg("ctl"), py::arg("cand_tok"), py::arg("cand_c"), py::arg("lse"));
+  m.def("beam_merge", &beam_merge, py::arg("W"), py::arg("V"), py::arg("cand_tok"), py::arg("cand_c"),
+        py::arg("score"), py::arg("fin"), py::arg("len"), py::arg("tok"), py::arg("parent"), py::arg("hist_parent"),
+        py::arg("hist_tok"), py::arg("hist_score"), py::arg("pos"), py::arg("ctl"));
+  m.def("beam_reorder", &beam_reorder, py::arg("kv"), py::arg("W"), py::arg("parent"), py::arg("pos"),
+        py::arg("ctl") = py::none());
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });

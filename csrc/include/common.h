@@ -266,6 +266,29 @@ MG_DEVICE float logprob_lnz(unsigned long long Z) { return logf((float)Z * 0x1p-
 
 MG_DEVICE float token_logprob(uint32_t bits, float m, float lnz) { return (bf2f(bits) - m) - lnz; }
 
+// ---------------------------------------------------------------- Beam search
+// W <= 8 beams per prompt over the log-probabilities above.  State per prompt b and beam w: a score
+// s[b, w] in fp32 (the running sum of the beam's lp numbers) and a finished flag.  Start: s[b, 0] = 0,
+// s[b, w > 0] = -inf, nothing finished; the W rows of a prompt hold the same prompt.
+// One step, from the bf16 logits row of each (b, w):
+//   a live beam offers the candidates (w, i), i < V, with  c = s[b, w] + lp_i,  lp_i =
+//     token_logprob(bits_i, m, lnz) on the row's own {m, lnz} -- one fp32 add; a -inf logit gives -inf;
+//   a finished beam offers the single candidate (w, pad_token) with c = s[b, w]: it stays finished
+//     and its length does not grow.
+// The new beams are the W best candidates of the prompt: c descending (a float compare: -0 equals
+// +0), among equal c the lower w first, then the row's own order -- logit descending, index
+// ascending (amax_key's order; for equal logits of one row that is the lower i).  -inf candidates
+// rank last by the same tie-break.  New beam r is the rank-r candidate with parent w, token i and
+// score c; it is finished if its parent was or if i is the stop token.  fp32 adds and subtractions
+// are monotone, so within a row c never rises along the row's order: a row can only contribute its
+// first W entries, and W * W candidates per prompt suffice.
+// Error against the rule over the reals (the fp64 step of ops/reference.py) given the same scores
+// going in: |c^ - c| <= (the lp bound above) + 2^-24 * |c| for the one add; the tests allow
+// d = 4 x the lp bound + 2^-23 * |c| and check that no unchosen candidate beats a chosen one by more
+// than the two candidates' d.
+// {m, lnz} is the lse kernel's, bit for bit (row_common.h holds the shared row code); the result
+// depends on the rows' values and the scores alone, not on a reduction order or graph / eager launch.
+
 // ---------------------------------------------------------------- GELU (tanh approximation)
 constexpr float kGeluK0 = 0.7978845608028654f;  // sqrt(2/pi)
 constexpr float kGeluK1 = 0.044715f;

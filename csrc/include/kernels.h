@@ -115,6 +115,31 @@ void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, 
 void logits_lse(const bf16_t* logits, long ld, int M, int V, const int64_t* targets, float* lse, float* lp,
                 hipStream_t stream);
 
+// beam.hip -- the tail of a beam decode step (the rule in common.h, 'Beam search'): B prompts, W <= 8
+// beams each, R = B * W rows, row b * W + w = beam w of prompt b.  ctl (device, 4 x int32): {history
+// column, stop token (negative: none), pad token, 0}.
+constexpr int kBeamMax = 8;
+constexpr int kBeamCtlWords = 4;
+// Per row of logits [R, ld] (layout as for sample_logits, W <= V): lse[2 r], lse[2 r + 1] = {m, lnz}
+// exactly as logits_lse writes them, and W candidates (cand_tok[r, k], cand_c[r, k]), k = the rank in
+// the row's (logit descending, index ascending) order, c = score[r] + lp.  A row with fin[r] set
+// writes (ctl[2], score[r]) and W - 1 empty candidates (token -1), which rank below everything.
+void beam_rows(const bf16_t* logits, long ld, int R, int V, int W, const float* score, const int* fin, const int* ctl,
+               int* cand_tok, float* cand_c, float* lse, hipStream_t stream);
+// Per prompt: the W best of its W * W candidates become the new beams, best first.  Rewrites score,
+// fin, len (int32 [R]; a finished parent's length does not grow), tok (int64 [R], the next step's
+// input) and parent (int32 [R]), and writes column ctl[0] of hist_parent / hist_tok (int32 [R,
+// hist_ld]) and hist_score (fp32, same shape).  Then *pos advances by one.
+void beam_merge(int B, int W, int V, const int* cand_tok, const float* cand_c, float* score, int* fin, int* len,
+                int64_t* tok, int* parent, int* hist_parent, int* hist_tok, float* hist_score, long hist_ld, int* pos,
+                const int* ctl, hipStream_t stream);
+// In place, for each of L layers of kv [L, R, Tmax, 3 D] (layer_stride elements apart): rows t <
+// min(*pos, Tmax) of the K and V columns of beam r of every prompt become those of beam parent[r] of
+// the same prompt.  Q columns, later rows and prompts whose parents are the identity are not
+// touched.  ctl (optional): ctl[0] advances by one.  D % 8 == 0.
+void beam_reorder(bf16_t* kv, int L, long layer_stride, int B, int W, int Tmax, int D, const int* parent,
+                  const int* pos, int* ctl, hipStream_t stream);
+
 // elementwise.hip
 void bias_act_fwd(const bf16_t* x, const bf16_t* b, bf16_t* pre, bf16_t* y, long M, int N, int act,
                   hipStream_t stream);

@@ -35,6 +35,14 @@ argmax keys would need the previous step's {m, lnz} in the next step's embedding
 epilogue for the last token; its step is the ragged greedy step on equal positions instead, which
 ranks the same stored bf16 logits with the first index on ties.  Host loops use
 ``ops.reference.token_logprob``.
+
+Beam search (``generate_beam``; the rule in common.h): W beams per prompt, scored by the running fp32
+sum of those log-probabilities.  The decode state has B * W rows and lives beside the plain one
+(``_beam_cache``), the prompt is prefilled once per prompt and broadcast, and the step -- ``_decode``
+at one batch-wide position, the row kernel, the merge, the in-place reorder of every layer's KV
+cache by parent beam -- is the loop ``("beam", W)`` (``_GpuCache.beam``).  The token history is never
+permuted: the sequences are rebuilt from the per-step parent / token histories at the end.  The CPU
+path runs ``ops.reference.beam_step`` on ``_CpuCache``.
 """
 from __future__ import annotations
 
@@ -182,7 +190,10 @@ class _GpuCache:
     with the same batch re-prefills into the same buffers and replays the same hipGraphs, unless
     a weight changed storage or version since the capture (then the graphs are re-captured)."""
 
-    def __init__(self, model, idx, tmax, last=None):
+    def __init__(self, model, idx, tmax, last=None, rows=None):
+        """``rows`` (beam search): a state of that many decode rows whose layers' caches are one
+        stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks every layer in one
+        launch), not prefilled here -- ``idx`` only names the device."""
         from ..ops._ext import ext
         from ..ops import gemm as G
 
@@ -190,12 +201,16 @@ class _GpuCache:
         self.C, self.G, self.bf = ext(), G, bf16_weights(model)
         self.model = model
         self.tmax = tmax
-        B, T = idx.shape
+        B = idx.size(0) if rows is None else rows
         cfg = model.config
         D = cfg.n_embed
         self.B = B
-        self.caches = [torch.empty(B, tmax, 3 * D, device=idx.device, dtype=torch.bfloat16)
-                       for _ in range(cfg.n_layer)]
+        if rows is None:
+            self.caches = [torch.empty(B, tmax, 3 * D, device=idx.device, dtype=torch.bfloat16)
+                           for _ in range(cfg.n_layer)]
+        else:
+            self.kv = torch.empty(cfg.n_layer, B, tmax, 3 * D, device=idx.device, dtype=torch.bfloat16)
+            self.caches = list(self.kv.unbind(0))
         # decode-attention workspace owned by this state (split partials + per-(b, h) counters
         # that the kernel leaves zero): the captured graphs bake these pointers in
         H = cfg.n_head
@@ -204,7 +219,8 @@ class _GpuCache:
         self.dec_cnt = torch.zeros(B * H, device=idx.device, dtype=torch.int32)
         self.stamp = _weight_stamp(model)
         self._loops = {}  # the device-side token loops (_Loop) by name, built on first use
-        self.prefill(idx, last)
+        if rows is None:
+            self.prefill(idx, last)
 
     @classmethod
     def body_only(cls, model):
@@ -268,8 +284,10 @@ class _GpuCache:
         x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0).view(B * T, D)
 
         def attend(i, qkv):
-            if keep:
+            if keep and self.caches[i].size(0) == B:
                 self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
+            elif keep:  # a beam state: the prompt's rows go to each of its beams
+                self.caches[i].view(B, -1, self.tmax, 3 * D)[:, :, :T].copy_(qkv.view(B, 1, T, 3 * D))
             return C.attention_fwd(qkv, B, T, H, 0.0, 0)[0]
 
         return self._blocks(x, attend, False).view(B, T, D)
@@ -581,6 +599,83 @@ class _GpuCache:
         self._loop(("ragged_lp" if logprobs else "ragged", greedy), lambda: _Loop(step, st, warm)).run(n)
         return st
 
+    # ----------------------------------------------------------------- beam search
+    def beam_state(self, W):
+        """The device state of the beam loop with W beams per prompt on this state's B * W rows
+        (row b * W + w = beam w of prompt b), allocated once (the captured step bakes the pointers
+        in): ``tok`` int64 [R, 1] (the next step's input), ``pos`` int32 [1] (one position for the
+        batch), ``ctl`` int32 [4] = {history column, stop token or -1, pad token, 0}, per beam
+        ``score`` fp32, ``fin`` / ``len`` / ``parent`` int32 [R], the row kernel's candidates and
+        ``lse``, and the per-step histories ``hparent`` / ``htok`` (int32 [B, W, tmax + 1]) and
+        ``hscore`` (fp32), indexed by the column of the step's token in the sequence."""
+        states = self.__dict__.setdefault("_bstate", {})
+        if W not in states:
+            dev, R = self.caches[0].device, self.B
+            assert R % W == 0
+            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+            f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+            start = torch.full((R // W, W), float("-inf"), dtype=torch.float32)
+            start[:, 0] = 0.0  # only beam 0 is live going into the first step
+            states[W] = {"tok": torch.zeros(R, 1, dtype=torch.long, device=dev), "pos": i32(1), "ctl": i32(4),
+                         "score": f32(R), "fin": i32(R), "len": i32(R), "parent": i32(R),
+                         "cand_tok": i32(R, W), "cand_c": f32(R, W), "lse": f32(R, 2),
+                         "hparent": i32(R // W, W, self.tmax + 1), "htok": i32(R // W, W, self.tmax + 1),
+                         "hscore": f32(R // W, W, self.tmax + 1), "score0": start.view(R).to(dev)}
+        return states[W]
+
+    def _beam_tail(self, st, W, logits):
+        """The end of a beam step on the padded logits [R, ld]: the row kernel ({m, lnz} and W
+        candidates per row), the merge (the prompt's W best become its beams; the position
+        advances) and the in-place reorder of every layer's K / V rows by parent beam (the history
+        column advances)."""
+        C, V = self.C, self.model.config.vocab_size
+        C.beam_rows(logits, V, W, st["score"], st["fin"], st["ctl"], st["cand_tok"], st["cand_c"], st["lse"])
+        C.beam_merge(W, V, st["cand_tok"], st["cand_c"], st["score"], st["fin"], st["len"], st["tok"], st["parent"],
+                     st["hparent"], st["htok"], st["hscore"], st["pos"], st["ctl"])
+        if _BEAM_REORDER_PER_LAYER:
+            for i in range(self.kv.size(0)):
+                C.beam_reorder(self.kv[i:i + 1], W, st["parent"], st["pos"], st["ctl"] if i == 0 else None)
+        else:
+            C.beam_reorder(self.kv, W, st["parent"], st["pos"], st["ctl"])
+
+    def beam(self, W):
+        """The beam loop of this state (``_loops[("beam", W)]``): ``_decode`` at one batch-wide
+        position, then ``_beam_tail``.  A finished beam keeps flowing through the step with the pad
+        token as its input and what it computes is ignored, so the launch shapes never change.
+        Build it BEFORE the prefill: the warm-up step runs on whatever the state holds (all zeros
+        the first time: position 0, token 0) and moves it."""
+        st = self.beam_state(W)
+        V = self.model.config.vocab_size
+
+        def step():
+            logits = self._decode(st["tok"], st["pos"], 1)
+            self._beam_tail(st, W, logits)
+            return logits[:, :V]
+
+        return self._loop(("beam", W), lambda: _Loop(step, st))
+
+    def beam_prefill(self, idx, W):
+        """Prefill the B prompts idx [B, T] once: every layer's qkv rows go to the W beams of their
+        prompt (``_prompt``), and the last position's padded logits [B, ld] come back W times over,
+        [B * W, ld] -- the input of the first beam step."""
+        x = self._prompt(idx)[:, -1]
+        full = self._head(x.contiguous(), False)
+        self.logits = full[:, :self.model.config.vocab_size]
+        return full.repeat_interleave(W, dim=0)
+
+    def beam_start(self, W, T, logits, eos_token, pad_token):
+        """Point the beam state at prompts of T tokens whose (broadcast) last-position logits are
+        ``logits`` and take the first step: the row and merge kernels with only beam 0 live."""
+        st = self.beam_state(W)
+        st["pos"].fill_(T - 1)
+        st["ctl"].copy_(torch.tensor([T, -1 if eos_token is None else int(eos_token), int(pad_token), 0],
+                                     dtype=torch.int32))
+        st["score"].copy_(st["score0"])
+        st["fin"].zero_()
+        st["len"].fill_(T)
+        self._beam_tail(st, W, logits)
+        return st
+
 
 _I64_MIN = -(1 << 63)
 
@@ -875,6 +970,162 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     if logprobs:
         return tokens, out_len, st["lp"][:, :W].clone()
     return tokens, out_len
+
+
+# --------------------------------------------------------------------------- beam search
+_BEAM_MAX = 8                     # beams per prompt the kernels take (kernels.h kBeamMax)
+_BEAM_REORDER_PER_LAYER = False   # set True (before a state's first beam call) to launch the cache
+#                                   reorder once per layer instead of once over all layers (PERF.md)
+
+
+def _beam_backtrack(hparent, htok, pad_token, total):
+    """The beams' generated tokens [B, W, total] from the per-step histories ``hparent`` / ``htok``
+    [B, W, steps] (host tensors; column j: new beam r of step j came from old beam hparent[b, r, j]
+    with token htok[b, r, j]), walked backwards from the last step's order.  Columns from ``steps``
+    on -- every beam had finished and the loop stopped -- are ``pad_token``: more steps would have
+    kept the order and offered only that."""
+    B, W, steps = htok.shape
+    out = torch.full((B, W, total), int(pad_token), dtype=torch.long)
+    cur = torch.arange(W).expand(B, W)
+    for j in range(steps - 1, -1, -1):
+        out[:, :, j] = htok[:, :, j].long().gather(1, cur)
+        cur = hparent[:, :, j].long().gather(1, cur)
+    return out
+
+
+@torch.no_grad()
+def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,
+                  pad_token: int = 0, length_penalty: float = 0.0):
+    """Beam search over the model's log-probabilities (the rule in common.h, 'Beam search'): keep
+    the ``num_beams`` continuations of every prompt with the largest summed log-probability, step
+    by step.  Returns ``(tokens, lengths, scores)``, best beam first per prompt: ``tokens`` int64
+    [B, W, T + max_new_tokens] -- the prompt, the beam's tokens (``eos_token``, if produced, is the
+    beam's last) and ``pad_token`` in the rest; ``lengths`` int64 [B, W] counts the valid tokens,
+    prompt included; ``scores`` float32 [B, W] is the beam's summed log-probability (the numbers of
+    ``generate(return_logprobs=True)``, added in fp32 on the device).
+
+    ``idx``: int64 [B, T], rectangular.  ``1 <= num_beams <= 8`` and at most the vocabulary size;
+    ``T + max_new_tokens`` must fit ``block_size`` (no sliding window here); ValueError otherwise.
+    A beam that produced ``eos_token`` is finished: it keeps its score, competes with the live
+    beams' continuations for its place and is padded.  ``length_penalty = a`` re-ranks the final W
+    beams by ``score / max(n_generated, 1) ** a`` (a stable sort: ties keep the search's order);
+    ``scores`` stays the raw sum, and a = 0 returns the search's order untouched.
+
+    On the GPU the prompt is prefilled once per prompt and the whole step -- decode, the row
+    kernel, the merge, the in-place reorder of every layer's KV cache by parent beam -- is one
+    captured graph replayed back to back on B * W rows (``_GpuCache.beam``); the sequences are
+    rebuilt at the end from the per-step parent / token histories.  On the CPU the same loop runs
+    ``ops.reference.beam_step`` on ``_CpuCache``."""
+    who = "generate_beam"
+    if not (torch.is_tensor(idx) and idx.dim() == 2 and idx.dtype == torch.long and idx.size(0) >= 1
+            and idx.size(1) >= 1):
+        raise ValueError(f"{who}: idx must be an int64 [B, T] tensor with B, T >= 1")
+    V, bs = model.config.vocab_size, model.block_size
+    B, T = idx.shape
+    W, n = int(num_beams), int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"{who}: max_new_tokens must be >= 0, got {max_new_tokens}")
+    if not 1 <= W <= _BEAM_MAX:
+        raise ValueError(f"{who}: num_beams must be in 1..{_BEAM_MAX}, got {num_beams}")
+    if W > V:
+        raise ValueError(f"{who}: num_beams ({W}) exceeds the vocabulary size ({V})")
+    if T + n > bs:
+        raise ValueError(f"{who}: prompt ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
+                         f"point has no sliding window")
+    if not 0 <= int(pad_token) < V:
+        raise ValueError(f"{who}: pad_token {pad_token} is not a token id (vocab {V})")
+    if eos_token is not None and not 0 <= int(eos_token) < V:
+        raise ValueError(f"{who}: eos_token {eos_token} is not a token id (vocab {V})")
+    lo, hi = idx.aminmax()
+    if int(lo) < 0 or int(hi) >= V:
+        raise ValueError(f"{who}: prompt token outside [0, {V})")
+    a = float(length_penalty)
+    device = idx.device
+    before_use(*model.parameters())
+    tokens = torch.full((B, W, T + n), int(pad_token), dtype=torch.long, device=device)
+    tokens[:, :, :T] = idx.view(B, 1, T)
+    lengths = torch.full((B, W), T, dtype=torch.long, device=device)
+    scores = torch.zeros((B, W), dtype=torch.float32, device=device)
+    if n == 0:
+        return tokens, lengths, scores
+    if device.type == "cuda":
+        hparent, htok, lengths, scores = _generate_beam_gpu(model, idx.contiguous(), n, W, eos_token, int(pad_token))
+    else:
+        hparent, htok, lengths, scores = _generate_beam_cpu(model, idx, n, W, eos_token, int(pad_token))
+    tokens[:, :, T:] = _beam_backtrack(hparent, htok, pad_token, n).to(device)
+    if a != 0.0:
+        key = scores.double() / (lengths - T).clamp(min=1).double() ** a
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        tokens = tokens.gather(1, order.view(B, W, 1).expand(B, W, T + n))
+        lengths, scores = lengths.gather(1, order), scores.gather(1, order)
+    return tokens, lengths, scores
+
+
+def _generate_beam_cpu(model, idx, n, W, eos_token, pad_token):
+    """The CPU half of ``generate_beam``, the executable definition of the semantics: one
+    ``_CpuCache`` of B * W rows (the prompt prefilled once per prompt and broadcast), a step of
+    ``ops.reference.beam_step`` per token, the caches' rows re-gathered by parent beam.  Returns the
+    histories (``_beam_backtrack``), the lengths and the scores."""
+    B, T = idx.shape
+    V = model.config.vocab_size
+    cache = _CpuCache(model, idx)
+    cache.k = [k.repeat_interleave(W, dim=0) for k in cache.k]
+    cache.v = [v.repeat_interleave(W, dim=0) for v in cache.v]
+    logits = cache.logits.repeat_interleave(W, dim=0)
+    s = torch.full((B, W), float("-inf"), dtype=torch.float64)
+    s[:, 0] = 0.0
+    fin = torch.zeros((B, W), dtype=torch.bool)
+    lens = torch.full((B, W), T, dtype=torch.long)
+    base = torch.arange(B).view(B, 1) * W
+    hparent, htok = [], []
+    for j in range(n):
+        par, tok, s, done = R.beam_step(s, fin, logits.view(B, W, V), eos_token, pad_token)
+        lens = lens.gather(1, par) + (~fin.gather(1, par)).long()
+        fin = done
+        hparent.append(par)
+        htok.append(tok)
+        if j + 1 == n or bool(fin.all()):
+            break
+        rows = (base + par).view(-1)
+        cache.k = [k.index_select(0, rows) for k in cache.k]
+        cache.v = [v.index_select(0, rows) for v in cache.v]
+        logits = cache.step(tok.view(B * W, 1), T + j)
+    return torch.stack(hparent, dim=2), torch.stack(htok, dim=2), lens, s.float()
+
+
+def _beam_cache(model, idx, W, tmax):
+    """The model's beam decode state of B * W rows, kept beside (not in place of) the plain decode
+    state: beam calls leave the plain loops and their graphs alone."""
+    rows = idx.size(0) * W
+    c = model.__dict__.get("_mg_beam_cache")
+    if c is None or c.B != rows or c.tmax != tmax or c.caches[0].device != idx.device:
+        c = _GpuCache(model, idx, tmax, rows=rows)
+        model.__dict__["_mg_beam_cache"] = c
+    return c
+
+
+def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token):
+    """The GPU half of ``generate_beam``: build (once) the beam loop of the B * W-row state, prefill
+    the B prompts, take the first beam step on the prefill's logits, then replay the captured step
+    n - 1 times.  With a stop token the finished flags are read every ``_EXIT_EVERY`` replays and
+    the loop ends once every beam has finished -- further steps would keep the order and append
+    padding (``_beam_backtrack``), so stopping changes no result.  Returns the host histories of
+    the steps taken, the lengths [B, W] and the scores [B, W]."""
+    B, T = idx.shape
+    cache = _beam_cache(model, idx, W, model.block_size)
+    loop = cache.beam(W)  # before the prefill: building it runs a warm-up step
+    st = cache.beam_start(W, T, cache.beam_prefill(idx, W), eos_token, pad_token)
+    left, steps = n - 1, 1
+    check = _EARLY_EXIT and eos_token is not None
+    while left > 0:
+        k = min(left, _EXIT_EVERY) if check else left
+        loop.run(k)
+        left -= k
+        steps += k
+        if check and left > 0 and bool(st["fin"].all()):
+            break
+    hparent, htok = st["hparent"][:, :, T:T + steps].cpu(), st["htok"][:, :, T:T + steps].cpu()
+    return hparent, htok, st["len"].view(B, W).long(), st["score"].view(B, W).clone()
 
 
 # --------------------------------------------------------------------------- scoring

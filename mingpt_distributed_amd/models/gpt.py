@@ -248,6 +248,18 @@ class GPT(nn.Module):
                               return_logprobs=return_logprobs)
 
     @torch.no_grad()
+    def generate_beam(self, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,
+                      pad_token: int = 0, length_penalty: float = 0.0):
+        """Beam search with ``num_beams`` (1..8) beams per prompt of ``idx`` [B, T]; returns ``(tokens
+        [B, W, T + max_new_tokens], lengths [B, W], scores [B, W])``, best beam first, ``scores`` the
+        summed log-probabilities (``generation.generate_beam``).  No sliding window: ``T +
+        max_new_tokens`` must fit ``block_size``."""
+        from .generation import generate_beam
+
+        return generate_beam(self, idx, max_new_tokens, num_beams, eos_token=eos_token, pad_token=pad_token,
+                             length_penalty=length_penalty)
+
+    @torch.no_grad()
     def score(self, idx, lengths=None):
         """Per-token log-probabilities of given sequences, float32 [B, T]: ``out[b, j]`` is the
         log-probability of ``idx[b, j]`` given ``idx[b, :j]`` for 1 <= j < lengths[b], 0.0 elsewhere

@@ -39,7 +39,9 @@ def _load():
 
 _ERR_BITS = {1: "embedding_fwd: token id outside [0, vocab)",
              2: "embedding_bwd: token id outside [0, vocab)",
-             4: "cross-entropy: target >= vocab"}
+             4: "cross-entropy: target >= vocab",
+             8: "beam_merge: chosen token outside [0, vocab)",
+             16: "beam_reorder: parent outside [0, beams)"}
 
 
 class DeviceCheckError(RuntimeError):

@@ -162,6 +162,45 @@ def token_logprob(logits: torch.Tensor, tok: torch.Tensor) -> torch.Tensor:
     return lp.gather(-1, tok.reshape(*lead, 1)).reshape(lead).float()
 
 
+def beam_step(scores: torch.Tensor, finished: torch.Tensor, logits: torch.Tensor, eos_token=None,
+              pad_token: int = 0):
+    """One step of the beam-search rule of ``csrc/include/common.h`` ('Beam search'; the kernels are
+    ``csrc/kernels/beam.hip``) over the reals, in fp64.  ``scores`` [B, W] (the running sums; -inf
+    for a beam that does not exist yet), ``finished`` bool [B, W], ``logits`` [B, W, V] (the row of
+    beam w of prompt b), W <= V.  A live beam offers (w, i) with c = s + log_softmax(logits)[i]; a
+    finished one only (w, pad_token) with c = s.  The new beams are the W best candidates of the
+    prompt: c descending, then the lower w, then the row's own order (logit descending, index
+    ascending).  Returns ``(parents, tokens, scores, finished)``: int64, int64, fp64, bool, all
+    [B, W], best first."""
+    B, W, V = logits.shape
+    if W > V:
+        raise ValueError(f"beam_step: {W} beams need a vocabulary of at least {W}, got {V}")
+    s = scores.double()
+    l = logits.double()
+    # a row can only contribute its first W entries in its own order (stable: the first index on ties)
+    top, tok = torch.sort(l, dim=-1, descending=True, stable=True)
+    top, tok = top[..., :W], tok[..., :W]
+    lp = top - torch.logsumexp(l, dim=-1, keepdim=True)
+    c = s.unsqueeze(-1) + lp  # [B, W, W]: beam w, rank k in its row
+    fin = finished.bool().unsqueeze(-1)
+    first = torch.arange(W, device=logits.device).view(1, 1, W) == 0
+    c = torch.where(fin, torch.where(first, s.unsqueeze(-1), torch.full_like(c, float("-inf"))), c)
+    tok = torch.where(fin, torch.full_like(tok, int(pad_token)), tok)
+    offered = (~fin | first).reshape(B, W * W)
+    c, tok = c.reshape(B, W * W), tok.reshape(B, W * W)
+    # stable sorts, the last one the most significant: offered first, then c descending; what is left
+    # of the flat (w, k) order breaks the ties
+    order = torch.sort(c, dim=-1, descending=True, stable=True).indices
+    order = order.gather(-1, torch.sort((~offered).gather(-1, order).long(), dim=-1, stable=True).indices)
+    order = order[:, :W]
+    parents = order // W
+    tokens, new = tok.gather(-1, order), c.gather(-1, order)
+    done = finished.bool().gather(-1, parents)
+    if eos_token is not None:
+        done = done | (tokens == int(eos_token))
+    return parents, tokens, new, done
+
+
 def cross_entropy(logits, targets, ignore_index: int = -1):
     return F.cross_entropy(logits.reshape(-1, logits.size(-1)).float(), targets.reshape(-1),
                            ignore_index=ignore_index)

@@ -18,6 +18,10 @@ decoded together in one ragged batch (``GPT.generate_batch``): every prompt keep
     python projects/generate/generate.py --weights /path/to/gpt2 --prompt "The capital of France" \
         --prompt "Once upon a time, in a land far away," --num-samples 2 --steps 40 --device cuda
 
+``--beams N`` (1..8) runs beam search on the one prompt instead of sampling (``GPT.generate_beam``) and
+prints the N beams best first with their summed log-probability; ``--length-penalty a`` re-ranks them
+by ``score / n_generated ** a``.
+
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
 """
@@ -51,6 +55,10 @@ def main(argv=None):
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--logprobs", action="store_true",
                     help="print each sample's summed log-probability and per-token perplexity")
+    ap.add_argument("--beams", type=int, default=0,
+                    help="beam search with this many beams (1..8) on one prompt instead of sampling")
+    ap.add_argument("--length-penalty", type=float, default=0.0,
+                    help="with --beams: re-rank the final beams by score / n_generated ** penalty")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -74,6 +82,8 @@ def main(argv=None):
     if a.prompt_file:
         with open(a.prompt_file, "r", encoding="utf-8") as f:
             texts += [ln.rstrip("\n") for ln in f if ln.strip()]
+    if a.beams and len(texts) > 1:
+        ap.error("--beams takes one prompt")
     if len(texts) > 1:
         return generate_many(model, tok, texts, a, dev)
     prompt = texts[0] if texts else ""
@@ -81,6 +91,8 @@ def main(argv=None):
         x = tok(prompt).to(dev)
     else:
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
+    if a.beams:
+        return generate_beams(model, tok, x, a)
     x = x.expand(a.num_samples, -1).contiguous()
     kw = {"return_logprobs": True} if a.logprobs else {}
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
@@ -102,6 +114,23 @@ def print_logprob(lp):
     total, n = float(lp.double().sum()), lp.numel()
     ppl = math.exp(-total / n) if n else float("nan")
     print(f"[logprob {total:.4f} over {n} tokens, perplexity {ppl:.4f}]")
+
+
+def generate_beams(model, tok, x, a):
+    """``--beams``: beam search on the one prompt x [1, T] (``GPT.generate_beam``), the beams printed
+    best first with their summed log-probability; a beam stops at ``<|endoftext|>`` when the
+    tokenizer has one."""
+    eos = tok.encoder.encoder.get("<|endoftext|>") if tok is not None else None
+    y, n, scores = model.generate_beam(x, a.steps, a.beams, eos_token=eos, length_penalty=a.length_penalty)
+    outs = []
+    for w in range(a.beams):
+        ids = y[0, w, :int(n[0, w])].cpu()
+        out = tok.decode(ids) if tok is not None else ids.tolist()
+        outs.append(out)
+        print("-" * 80)
+        print(out)
+        print(f"[beam {w}: logprob {float(scores[0, w]):.4f} over {int(n[0, w]) - x.size(1)} tokens]")
+    return outs
 
 
 def generate_many(model, tok, texts, a, dev):
