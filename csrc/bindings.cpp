@@ -607,19 +607,60 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// ------------------------------------------------------------------------------- logits-row ops
+// The checks the one-workgroup-per-row ops (sample.hip, beam.hip) share, one per kind of argument.
+
+// A contiguous int32 / fp32 device buffer of n elements on device dev, argument `name` of op `op`.
+void dev_i32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
+              op, ": ", name, " must be int32 with ", n, " elements on the operands' device");
+}
+
+void dev_f32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
+              op, ": ", name, " must be float32 with ", n, " elements on the operands' device");
+}
+
+// The logits of op `op`: [rows, ld] bf16 with unit column stride, of which the kernel reads the
+// first V columns of every row in 16-byte loads (columns >= V are padding, never read).  ld is the
+// row stride in elements -- 0 for a single row, which has none to check.
+struct LogitsRows {
+  int64_t rows, ld;
+  at::Device dev;
+};
+
+LogitsRows logits_rows(const char* op, const at::Tensor& logits, int64_t V) {
+  CHECK_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, op,
+              ": logits [rows, ld], unit column stride");
+  const int64_t rows = logits.size(0), ld = rows > 1 ? logits.stride(0) : 0;
+  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (rows == 1 || ld >= logits.size(1)), op, ": 1 <= V <= ld");
+  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, op,
+              ": rows must be 16-byte aligned (ld % 8 == 0)");
+  return {rows, ld, logits.device()};
+}
+
+// The pick kernels' parameter block (kernels.h): int32 [8] on the logits' device.
+uint32_t* sample_params(const char* op, const at::Tensor& params, const at::Device& dev) {
+  CHECK_DEV(params);
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
+              params.device() == dev, op, ": params int32 [8] on the logits' device");
+  return reinterpret_cast<uint32_t*>(params.data_ptr<int>());
+}
+
 // The optional log-probability arguments of the pick kernels (kernels.h): lse fp32 with 2 B
 // elements ({m, lnz} per row, from logits_lse on the same logits) and lp fp32 of seq's shape; both
 // or neither.  Sets the two pointers (null without them).
 void logprob_args(const char* op, const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp,
-                  const at::Tensor& logits, const at::Tensor* seq, const float*& lsep, float*& lpp) {
+                  const LogitsRows& lr, const at::Tensor* seq, const float*& lsep, float*& lpp) {
   lsep = nullptr;
   lpp = nullptr;
   const bool has_lse = lse.has_value() && lse->defined(), has_lp = lp.has_value() && lp->defined();
   if (!has_lse && !has_lp) return;
   TORCH_CHECK(has_lse && has_lp && seq, op, ": lse and lp go together, with seq");
-  CHECK_F32(*lse); CHECK_CONTIG(*lse); CHECK_F32(*lp); CHECK_CONTIG(*lp);
-  TORCH_CHECK(lse->numel() == 2 * logits.size(0) && lse->device() == logits.device(), op, ": lse fp32 [B, 2]");
-  TORCH_CHECK(lp->sizes() == seq->sizes() && lp->device() == logits.device(), op, ": lp fp32 of seq's shape");
+  dev_f32(op, "lse", *lse, 2 * lr.rows, lr.dev);
+  dev_f32(op, "lp", *lp, seq->numel(), lr.dev);
+  TORCH_CHECK(lp->sizes() == seq->sizes(), op, ": lp fp32 of seq's shape");
   lsep = lse->data_ptr<float>();
   lpp = lp->data_ptr<float>();
 }
@@ -634,25 +675,20 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
                          const c10::optional<at::Tensor>& pos_dev, const c10::optional<at::Tensor>& tok,
                          const c10::optional<at::Tensor>& seq, const c10::optional<at::Tensor>& lse,
                          const c10::optional<at::Tensor>& lp) {
-  CHECK_BF16(logits); CHECK_DEV(params);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "sample_logits: logits [B, ld], unit column stride");
-  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
-  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "sample_logits: 1 <= V <= ld");
-  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "sample_logits: rows must be 16-byte aligned (ld % 8 == 0)");
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
-              params.device() == logits.device(), "sample_logits: params int32 [8] on the logits' device");
+  const char* op = "sample_logits";
+  const LogitsRows lr = logits_rows(op, logits, V);
+  const int64_t B = lr.rows;
+  uint32_t* pp = sample_params(op, params, lr.dev);
   int* pd = nullptr;
   if (pos_dev.has_value()) {
-    TORCH_CHECK(pos_dev->scalar_type() == at::kInt && pos_dev->is_cuda() && pos_dev->numel() == 1 &&
-                pos_dev->device() == logits.device(), "sample_logits: pos_dev int32 [1] on the logits' device");
+    dev_i32(op, "pos_dev", *pos_dev, 1, lr.dev);
     pd = pos_dev->data_ptr<int>();
   }
-  DevGuard g(logits.device());
+  DevGuard g(lr.dev);
   at::Tensor t;
   if (tok.has_value()) {
     CHECK_I64(*tok); CHECK_CONTIG(*tok);
-    TORCH_CHECK(tok->numel() == B && tok->device() == logits.device(), "sample_logits: tok int64 with B elements");
+    TORCH_CHECK(tok->numel() == B && tok->device() == lr.dev, "sample_logits: tok int64 with B elements");
     t = *tok;
   } else {
     t = at::empty({B}, logits.options().dtype(at::kLong));
@@ -661,16 +697,16 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
   long seq_ld = 0;
   if (seq.has_value()) {
     CHECK_I64(*seq); CHECK_CONTIG(*seq);
-    TORCH_CHECK(pd && seq->dim() == 2 && seq->size(0) == B && seq->device() == logits.device(),
+    TORCH_CHECK(pd && seq->dim() == 2 && seq->size(0) == B && seq->device() == lr.dev,
                 "sample_logits: seq int64 [B, L] with pos_dev");
     seqp = seq->data_ptr<int64_t>();
     seq_ld = seq->size(1);
   }
   const float* lsep;
   float* lpp;
-  logprob_args("sample_logits", lse, lp, logits, seq.has_value() ? &*seq : nullptr, lsep, lpp);
-  mg::sample_logits(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()), pd,
-                    t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream(), lsep, lpp);
+  logprob_args(op, lse, lp, lr, seq.has_value() ? &*seq : nullptr, lsep, lpp);
+  mg::sample_logits(bp(logits), lr.ld, (int)B, (int)V, pp, pd, t.data_ptr<int64_t>(), seqp, seq_ld, cur_stream(),
+                    lsep, lpp);
   return t;
 }
 
@@ -679,18 +715,11 @@ at::Tensor sample_logits(const at::Tensor& logits, int64_t V, const at::Tensor& 
 // top_p / temperature.  Runs the sampler's kernel up to its threshold; nothing but the result is
 // written.
 at::Tensor sample_kept(const at::Tensor& logits, int64_t V, const at::Tensor& params) {
-  CHECK_BF16(logits); CHECK_DEV(params);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "sample_kept: logits [B, ld], unit column stride");
-  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
-  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "sample_kept: 1 <= V <= ld");
-  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "sample_kept: rows must be 16-byte aligned (ld % 8 == 0)");
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
-              params.device() == logits.device(), "sample_kept: params int32 [8] on the logits' device");
-  DevGuard g(logits.device());
-  at::Tensor out = at::empty({B, 2}, logits.options().dtype(at::kInt));
-  mg::sample_kept(bp(logits), ld, (int)B, (int)V, reinterpret_cast<const uint32_t*>(params.data_ptr<int>()),
-                  out.data_ptr<int>(), cur_stream());
+  const LogitsRows lr = logits_rows("sample_kept", logits, V);
+  const uint32_t* pp = sample_params("sample_kept", params, lr.dev);
+  DevGuard g(lr.dev);
+  at::Tensor out = at::empty({lr.rows, 2}, logits.options().dtype(at::kInt));
+  mg::sample_kept(bp(logits), lr.ld, (int)lr.rows, (int)V, pp, out.data_ptr<int>(), cur_stream());
   return out;
 }
 
@@ -702,28 +731,22 @@ at::Tensor sample_kept(const at::Tensor& logits, int64_t V, const at::Tensor& pa
 void pick_ragged(const at::Tensor& logits, int64_t V, const at::Tensor& params, const at::Tensor& pos,
                  const at::Tensor& done, const at::Tensor& tok, const at::Tensor& seq, bool greedy,
                  const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp) {
-  CHECK_BF16(logits); CHECK_DEV(params);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "pick_ragged: logits [B, ld], unit column stride");
-  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : 0;  // one row: no stride
-  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (B == 1 || ld >= logits.size(1)), "pick_ragged: 1 <= V <= ld");
-  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "pick_ragged: rows must be 16-byte aligned (ld % 8 == 0)");
-  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kSampleParamWords &&
-              params.device() == logits.device(), "pick_ragged: params int32 [8] on the logits' device");
-  for (const at::Tensor* t : {&pos, &done})
-    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() == B &&
-                t->device() == logits.device(), "pick_ragged: pos and done int32 [B] on the logits' device");
+  const char* op = "pick_ragged";
+  const LogitsRows lr = logits_rows(op, logits, V);
+  const int64_t B = lr.rows;
+  uint32_t* pp = sample_params(op, params, lr.dev);
+  dev_i32(op, "pos", pos, B, lr.dev);
+  dev_i32(op, "done", done, B, lr.dev);
   CHECK_I64(tok); CHECK_CONTIG(tok); CHECK_I64(seq); CHECK_CONTIG(seq);
-  TORCH_CHECK(tok.numel() == B && tok.device() == logits.device(), "pick_ragged: tok int64 with B elements");
-  TORCH_CHECK(seq.dim() == 2 && seq.size(0) == B && seq.size(1) >= 2 && seq.device() == logits.device(),
+  TORCH_CHECK(tok.numel() == B && tok.device() == lr.dev, "pick_ragged: tok int64 with B elements");
+  TORCH_CHECK(seq.dim() == 2 && seq.size(0) == B && seq.size(1) >= 2 && seq.device() == lr.dev,
               "pick_ragged: seq int64 [B, L]");
   const float* lsep;
   float* lpp;
-  logprob_args("pick_ragged", lse, lp, logits, &seq, lsep, lpp);
-  DevGuard g(logits.device());
-  mg::pick_ragged(bp(logits), ld, (int)B, (int)V, reinterpret_cast<uint32_t*>(params.data_ptr<int>()),
-                  pos.data_ptr<int>(), done.data_ptr<int>(), tok.data_ptr<int64_t>(), seq.data_ptr<int64_t>(),
-                  seq.size(1), greedy, cur_stream(), lsep, lpp);
+  logprob_args(op, lse, lp, lr, &seq, lsep, lpp);
+  DevGuard g(lr.dev);
+  mg::pick_ragged(bp(logits), lr.ld, (int)B, (int)V, pp, pos.data_ptr<int>(), done.data_ptr<int>(),
+                  tok.data_ptr<int64_t>(), seq.data_ptr<int64_t>(), seq.size(1), greedy, cur_stream(), lsep, lpp);
 }
 
 // Per-token log-probabilities of the rule in common.h for every row of logits [M, ld] bf16 (as for
@@ -733,18 +756,14 @@ void pick_ragged(const at::Tensor& logits, int64_t V, const at::Tensor& params, 
 // here).  lse / lp: write into these instead of allocating.
 py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<at::Tensor>& targets,
                       const c10::optional<at::Tensor>& lse, const c10::optional<at::Tensor>& lp) {
-  CHECK_BF16(logits);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "logits_lse: logits [M, ld], unit column stride");
-  const int64_t M = logits.size(0), ld = M > 1 ? logits.stride(0) : 0;  // one row: no stride
-  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (M == 1 || ld >= logits.size(1)), "logits_lse: 1 <= V <= ld");
-  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "logits_lse: rows must be 16-byte aligned (ld % 8 == 0)");
+  const char* op = "logits_lse";
+  const LogitsRows lr = logits_rows(op, logits, V);
+  const int64_t M = lr.rows;
   TORCH_CHECK(M <= 0x7fffffff, "logits_lse: too many rows");
-  DevGuard g(logits.device());
+  DevGuard g(lr.dev);
   at::Tensor l, p;
   if (lse.has_value() && lse->defined()) {
-    CHECK_F32(*lse); CHECK_CONTIG(*lse);
-    TORCH_CHECK(lse->numel() == 2 * M && lse->device() == logits.device(), "logits_lse: lse fp32 [M, 2]");
+    dev_f32(op, "lse", *lse, 2 * M, lr.dev);
     l = *lse;
   } else {
     l = at::empty({M, 2}, logits.options().dtype(at::kFloat));
@@ -753,11 +772,10 @@ py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<a
   const int64_t* tp = nullptr;
   if (has_t) {
     CHECK_I64(*targets); CHECK_CONTIG(*targets);
-    TORCH_CHECK(targets->numel() == M && targets->device() == logits.device(), "logits_lse: targets int64 [M]");
+    TORCH_CHECK(targets->numel() == M && targets->device() == lr.dev, "logits_lse: targets int64 [M]");
     tp = targets->data_ptr<int64_t>();
     if (lp.has_value() && lp->defined()) {
-      CHECK_F32(*lp); CHECK_CONTIG(*lp);
-      TORCH_CHECK(lp->numel() == M && lp->device() == logits.device(), "logits_lse: lp fp32 [M]");
+      dev_f32(op, "lp", *lp, M, lr.dev);
       p = *lp;
     } else {
       p = at::zeros({M}, logits.options().dtype(at::kFloat));
@@ -765,7 +783,7 @@ py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<a
   } else {
     TORCH_CHECK(!(lp.has_value() && lp->defined()), "logits_lse: lp needs targets");
   }
-  mg::logits_lse(bp(logits), ld, (int)M, (int)V, tp, fp(l), has_t ? fp(p) : nullptr, cur_stream());
+  mg::logits_lse(bp(logits), lr.ld, (int)M, (int)V, tp, fp(l), has_t ? fp(p) : nullptr, cur_stream());
   if (has_t) return py::make_tuple(l, p);
   return py::cast(l);
 }
@@ -773,38 +791,25 @@ py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<a
 // ------------------------------------------------------------------------------- beam search
 // beam.hip (kernels.h).  Every per-beam buffer has R = B * W elements, row b * W + w = beam w of
 // prompt b; all of them live on the logits' / the cache's device and are updated in place.
-void beam_i32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
-  TORCH_CHECK(t.scalar_type() == at::kInt && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
-              op, ": ", name, " must be int32 with ", n, " elements on the operands' device");
-}
-
-void beam_f32(const char* op, const char* name, const at::Tensor& t, int64_t n, const at::Device& dev) {
-  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_cuda() && t.is_contiguous() && t.numel() == n && t.device() == dev,
-              op, ": ", name, " must be float32 with ", n, " elements on the operands' device");
-}
 
 // The row kernel on logits [R, ld] bf16 (columns >= V never read): writes cand_tok int32 [R, W],
 // cand_c fp32 [R, W] and lse fp32 [R, 2] from score fp32 [R], fin int32 [R] and ctl int32 [4].
 void beam_rows(const at::Tensor& logits, int64_t V, int64_t W, const at::Tensor& score, const at::Tensor& fin,
                const at::Tensor& ctl, const at::Tensor& cand_tok, const at::Tensor& cand_c, const at::Tensor& lse) {
-  CHECK_BF16(logits);
-  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.stride(1) == 1, "beam_rows: logits [R, ld], unit column stride");
-  const int64_t R = logits.size(0), ld = R > 1 ? logits.stride(0) : 0;  // one row: no stride
-  TORCH_CHECK(V >= 1 && V <= logits.size(1) && (R == 1 || ld >= logits.size(1)), "beam_rows: 1 <= V <= ld");
-  TORCH_CHECK(ld % 8 == 0 && reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
-              "beam_rows: rows must be 16-byte aligned (ld % 8 == 0)");
+  const LogitsRows lr = logits_rows("beam_rows", logits, V);
+  const int64_t R = lr.rows;
   TORCH_CHECK(W >= 1 && W <= mg::kBeamMax && W <= V && R % W == 0 && R <= 0x7fffffff,
               "beam_rows: 1 <= W <= 8, W <= V, R a multiple of W");
   TORCH_CHECK(V <= (1 << 25), "beam_rows: V above 2^25 (a thread counts its elements in 16 bits)");
-  const at::Device dev = logits.device();
-  beam_f32("beam_rows", "score", score, R, dev);
-  beam_i32("beam_rows", "fin", fin, R, dev);
-  beam_i32("beam_rows", "ctl", ctl, mg::kBeamCtlWords, dev);
-  beam_i32("beam_rows", "cand_tok", cand_tok, R * W, dev);
-  beam_f32("beam_rows", "cand_c", cand_c, R * W, dev);
-  beam_f32("beam_rows", "lse", lse, 2 * R, dev);
+  const at::Device dev = lr.dev;
+  dev_f32("beam_rows", "score", score, R, dev);
+  dev_i32("beam_rows", "fin", fin, R, dev);
+  dev_i32("beam_rows", "ctl", ctl, mg::kBeamCtlWords, dev);
+  dev_i32("beam_rows", "cand_tok", cand_tok, R * W, dev);
+  dev_f32("beam_rows", "cand_c", cand_c, R * W, dev);
+  dev_f32("beam_rows", "lse", lse, 2 * R, dev);
   DevGuard g(dev);
-  mg::beam_rows(bp(logits), ld, (int)R, (int)V, (int)W, fp(score), fin.data_ptr<int>(), ctl.data_ptr<int>(),
+  mg::beam_rows(bp(logits), lr.ld, (int)R, (int)V, (int)W, fp(score), fin.data_ptr<int>(), ctl.data_ptr<int>(),
                 cand_tok.data_ptr<int>(), fp(cand_c), fp(lse), cur_stream());
 }
 
@@ -819,21 +824,21 @@ void beam_merge(int64_t W, int64_t V, const at::Tensor& cand_tok, const at::Tens
   const int64_t R = score.numel();
   TORCH_CHECK(R >= W && R % W == 0 && R <= 0x7fffffff, "beam_merge: score with B * W elements");
   const at::Device dev = score.device();
-  beam_f32("beam_merge", "score", score, R, dev);
-  beam_i32("beam_merge", "cand_tok", cand_tok, R * W, dev);
-  beam_f32("beam_merge", "cand_c", cand_c, R * W, dev);
-  beam_i32("beam_merge", "fin", fin, R, dev);
-  beam_i32("beam_merge", "len", len, R, dev);
-  beam_i32("beam_merge", "parent", parent, R, dev);
+  dev_f32("beam_merge", "score", score, R, dev);
+  dev_i32("beam_merge", "cand_tok", cand_tok, R * W, dev);
+  dev_f32("beam_merge", "cand_c", cand_c, R * W, dev);
+  dev_i32("beam_merge", "fin", fin, R, dev);
+  dev_i32("beam_merge", "len", len, R, dev);
+  dev_i32("beam_merge", "parent", parent, R, dev);
   CHECK_I64(tok); CHECK_CONTIG(tok);
   TORCH_CHECK(tok.numel() == R && tok.device() == dev, "beam_merge: tok int64 with B * W elements");
   TORCH_CHECK(hist_parent.dim() >= 2 && hist_parent.size(-1) >= 1, "beam_merge: histories [B, W, Lh]");
   const int64_t Lh = hist_parent.size(-1);
-  beam_i32("beam_merge", "hist_parent", hist_parent, R * Lh, dev);
-  beam_i32("beam_merge", "hist_tok", hist_tok, R * Lh, dev);
-  beam_f32("beam_merge", "hist_score", hist_score, R * Lh, dev);
-  beam_i32("beam_merge", "pos", pos, 1, dev);
-  beam_i32("beam_merge", "ctl", ctl, mg::kBeamCtlWords, dev);
+  dev_i32("beam_merge", "hist_parent", hist_parent, R * Lh, dev);
+  dev_i32("beam_merge", "hist_tok", hist_tok, R * Lh, dev);
+  dev_f32("beam_merge", "hist_score", hist_score, R * Lh, dev);
+  dev_i32("beam_merge", "pos", pos, 1, dev);
+  dev_i32("beam_merge", "ctl", ctl, mg::kBeamCtlWords, dev);
   DevGuard g(dev);
   mg::beam_merge((int)(R / W), (int)W, (int)V, cand_tok.data_ptr<int>(), fp(cand_c), fp(score), fin.data_ptr<int>(),
                  len.data_ptr<int>(), tok.data_ptr<int64_t>(), parent.data_ptr<int>(), hist_parent.data_ptr<int>(),
@@ -856,11 +861,11 @@ void beam_reorder(const at::Tensor& kv, int64_t W, const at::Tensor& parent, con
   TORCH_CHECK(Tmax >= 1 && Tmax * (D / 4) <= 0x7fffffff - 256 && R / W <= 65535 && L <= 65535,
               "beam_reorder: cache too large for one launch");
   const at::Device dev = kv.device();
-  beam_i32("beam_reorder", "parent", parent, R, dev);
-  beam_i32("beam_reorder", "pos", pos, 1, dev);
+  dev_i32("beam_reorder", "parent", parent, R, dev);
+  dev_i32("beam_reorder", "pos", pos, 1, dev);
   int* cp = nullptr;
   if (ctl.has_value() && ctl->defined()) {
-    beam_i32("beam_reorder", "ctl", *ctl, mg::kBeamCtlWords, dev);
+    dev_i32("beam_reorder", "ctl", *ctl, mg::kBeamCtlWords, dev);
     cp = ctl->data_ptr<int>();
   }
   DevGuard g(dev);

@@ -116,6 +116,19 @@ MG_DEVICE float block_max(float v, float* red) {
   return t;
 }
 
+// ---------------------------------------------------------------- argmax keys
+// order-preserving key of a float (larger float -> larger key) with the index inverted in the low
+// half: the max key is the FIRST index among equal values (torch.argmax).  One definition for the
+// LM head's fused argmax (gemv.hip), the embedding kernel that reduces its keys, and the row kernels
+// (row_common.h), which all rank the same stored bf16 logits.
+MG_DEVICE unsigned long long amax_key(float v, int n) {
+  const uint32_t u = __float_as_uint(v);
+  const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)k << 32) | (uint32_t)(0xffffffffu - (uint32_t)n);
+}
+// the index in a key (key 0, "no candidate", gives 0xffffffff)
+MG_DEVICE long amax_index(unsigned long long key) { return (long)(0xffffffffu - (uint32_t)key); }
+
 // ---------------------------------------------------------------- residual-stream dropout mask
 // Exact nn.Dropout(p) decisions to 1/65536: keep iff a 16-bit uniform >= thr16 = round(65536 p),
 // scale 65536 / (65536 - thr16) (p = 0.1 -> 0.100006; the 8-bit decisions of rounds 1-3 ran

@@ -1,8 +1,8 @@
 // Beam search on the device for gfx950: the three kernels that follow the LM head in a beam decode
 // step (the rule in common.h, 'Beam search').  B prompts, W <= 8 beams each, R = B * W decode rows.
 //
-//   rows     one workgroup of 1024 threads per row, the row in registers as in sample.hip
-//            (row_common.h): {m, lnz} by the lse kernel's own sequence, then the row's first W
+//   rows     one workgroup of 1024 threads per row, the row in registers as in sample.hip (Row,
+//            row_common.h): {m, lnz} by the lse kernel's own row_max_mass, then the row's first W
 //            entries in amax_key order -- every thread keeps its best key below the previous
 //            winner, and only the thread that held the winner looks for its next one, so a round
 //            costs one workgroup reduction -- written as W (token, c = s + lp) candidates.  A
@@ -40,27 +40,13 @@ __global__ __launch_bounds__(kThreads) void beam_row_kernel(const bf16_t* __rest
   __shared__ unsigned long long redk[2][kWaves];
   const long r = blockIdx.x;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const bf16_t* row = logits + r * ld;
+  const Row rw(logits + r * ld, V);
   const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
-  const bool cached = nv <= kRegVec * kThreads;
-  uint4 regs[kRegVec];
-  uint32_t tail = 0u;
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < kRegVec; ++j) {
-      const int v = (int)threadIdx.x + j * kThreads;
-      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (threadIdx.x < 8 && ti < V) tail = row[ti];
-  }
-  auto sweep = [&](auto f) {
-    if (cached) for_regs(regs, tail, V, f);
-    else for_row(row, V, f);
-  };
-  // A thread ranks its own elements by a 32-bit key: the bf16 bits in amax_key's order above the
-  // inverted count e of the element within the thread (e grows with the column: 8 j + c for column c
-  // of the thread's j-th vector, 0xffff for the tail element), so the thread's maximum is its entry
-  // that comes first in amax_key order.  Only a thread's best is widened to the 64-bit key.
+  // A thread ranks its own elements by a 32-bit key: the bf16 bits in amax_key's order (key16's, but
+  // -0 stays below +0) above the inverted count e of the element within the thread (e grows with the
+  // column: 8 j + c for column c of the thread's j-th vector, 0xffff for the tail element), so the
+  // thread's maximum is its entry that comes first in amax_key order.  Only a thread's best is
+  // widened to the 64-bit key.
   static_assert(kThreads == 1024, "the element count below takes the vector stride as 1 << 10");
   auto lkey = [&](int i, uint32_t bits) -> uint32_t {
     const uint32_t o = (bits & 0x8000u) ? (bits ^ 0xffffu) : (bits | 0x8000u);
@@ -69,24 +55,19 @@ __global__ __launch_bounds__(kThreads) void beam_row_kernel(const bf16_t* __rest
   };
   auto gkey = [&](uint32_t lk) -> unsigned long long {
     if (!lk) return 0ull;
-    const uint32_t o = lk >> 16, e = 0xffffu - (lk & 0xffffu);
-    const uint32_t bits = (o & 0x8000u) ? (o ^ 0x8000u) : (o ^ 0xffffu);
+    const uint32_t e = 0xffffu - (lk & 0xffffu);
     const int i = e == 0xffffu ? ti : ((((int)threadIdx.x + (int)(e >> 3) * kThreads) << 3) | (int)(e & 7u));
-    return amax_key(bf2f(bits), i);
+    return amax_key(bf2f(key16_bits(lk >> 16)), i);
   };
-  // {m, lnz}: the lse kernel's sequence (the thread's best key rides along in the first sweep)
-  float m = -INFINITY;
+  // {m, lnz}: the lse kernel's (the thread's best key rides along in the first sweep)
+  float m;
+  unsigned long long z;
   uint32_t mine_l = 0u;
-  sweep([&](int i, uint32_t bits) {
-    m = fmaxf(m, bf2f(bits));
+  row_max_mass(rw, redf, redq, m, z, [&](int i, uint32_t bits) {
     const uint32_t k = lkey(i, bits);
     mine_l = k > mine_l ? k : mine_l;
   });
   unsigned long long mine = gkey(mine_l);
-  m = block_max<kWaves>(m, redf);
-  unsigned long long z = 0ull;
-  sweep([&](int, uint32_t bits) { z += sample_mass(bits, m, 1.0f); });
-  z = block_sum_u64(z, redq);
   float lnz = 0.f;  // thread 0's: it writes the candidates
   if (threadIdx.x == 0) {
     lnz = logprob_lnz(z);
@@ -107,19 +88,14 @@ __global__ __launch_bounds__(kThreads) void beam_row_kernel(const bf16_t* __rest
   for (int k = 0; k < W; ++k) {
     if (k > 0 && mine == prev) {
       uint32_t nxt = 0u;
-      sweep([&](int i, uint32_t bits) {
+      rw.sweep([&](int i, uint32_t bits) {
         const uint32_t key = lkey(i, bits);
         nxt = (key < mine_l && key > nxt) ? key : nxt;
       });
       mine_l = nxt;
       mine = gkey(nxt);
     }
-    unsigned long long best = mine;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long q = shfl_xor_u64(best, o);
-      best = q > best ? q : best;
-    }
+    unsigned long long best = wave_max_key(mine);
     // two buffers: a wave writes round k + 2 only after every wave has passed round k + 1's barrier,
     // i.e. has read round k
     if (lane == 0) redk[k & 1][wv] = best;
@@ -128,13 +104,10 @@ __global__ __launch_bounds__(kThreads) void beam_row_kernel(const bf16_t* __rest
     for (int i = 0; i < kWaves; ++i) best = redk[k & 1][i] > best ? redk[k & 1][i] : best;
     prev = best;
     if (threadIdx.x == 0) {
-      long t = (long)(0xffffffffu - (uint32_t)best);
-      if (t >= V) t = V - 1;  // no entry left (never with W <= V): still a valid id
-      // the entry's bf16 bits are in the key (amax_key undone): no dependent load of row[t]
-      const uint32_t kf = (uint32_t)(best >> 32);
-      const uint32_t u = (kf & 0x80000000u) ? (kf ^ 0x80000000u) : ~kf;
-      cand_tok[r * W + k] = (int)t;
-      cand_c[r * W + k] = s + token_logprob(u >> 16, m, lnz);
+      // no entry left (never with W <= V) is still a valid id; the entry's bf16 bits are the top 16
+      // of the key (amax_key undone): no dependent load of row[t]
+      cand_tok[r * W + k] = (int)key_token(best, V);
+      cand_c[r * W + k] = s + token_logprob(key16_bits((uint32_t)(best >> 48)), m, lnz);
     }
   }
 }

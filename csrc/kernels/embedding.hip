@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict_
   long tok;
   if (am_part) {
     // greedy decode: this row's token is the argmax the previous step's LM-head GEMV left as one
-    // key per workgroup (gemv.hip): a wave max over the keys, first index on ties
+    // amax_key per workgroup (gemv.hip): a wave max over the keys, first index on ties
     unsigned long long best = 0;
     for (int i = lane; i < am_groups; i += 64) {
       const unsigned long long k = am_part[m * am_groups + i];
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const int64_t* __restrict_
       const unsigned long long k = ((unsigned long long)hi << 32) | lo;
       best = k > best ? k : best;
     }
-    tok = (long)(0xffffffffu - (uint32_t)best);
+    tok = amax_index(best);
     if (lane == 0) {
       if (tok_out) tok_out[m] = tok;
       if (seq) seq[m * seq_ld + *pos_dev] = tok;

@@ -30,13 +30,6 @@ namespace {
 constexpr int kGemvMaxB = 8;
 constexpr int kGemvMaxK = 4096;  // B x K bf16 of x must fit the LDS staging buffer
 
-// order-preserving key of a float (larger float -> larger key), index in the low half inverted
-// so that the max key is the FIRST index among equal values (torch.argmax)
-MG_DEVICE unsigned long long amax_key(float v, int n) {
-  const uint32_t u = __float_as_uint(v);
-  const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)k << 32) | (uint32_t)(0xffffffffu - (uint32_t)n);
-}
 MG_DEVICE unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 // Fused greedy argmax, first half: every workgroup publishes its best (value, index) key per row

@@ -8,7 +8,7 @@
 // order, or whether the launch is replayed from a hipGraph.
 //
 // One workgroup of 1024 threads per row; the row (100 KB at V = 50257) is loaded once into
-// registers (for_regs; rows past 65536 columns are streamed by every pass instead):
+// registers (Row, row_common.h; rows past 65536 columns are streamed by every pass instead):
 //   pass A  row maximum, and (top-k on) a 256-bin histogram of the high byte of the 16-bit key;
 //   pass B  (top-k on) histogram of the low byte among the keys in the bin that holds the k-th;
 //           -> the exact k-th largest key, ties included, no sort and no tolerance;
@@ -33,13 +33,13 @@
 //
 // Log-probabilities (logits_lse; the rule in common.h, 'Per-token log-probabilities'): one more
 // one-workgroup-per-row kernel over the same row in registers -- the maximum, then the 64-bit
-// integer sum of the sampler's own masses at temperature 1 by wave shuffle and LDS -- leaves
-// {m, lnz} per row, and with targets the log-probability of one given token per row (score).  The
-// pick kernels take that pair and write the picked token's log-probability beside the token, under
-// the conditions of the token's own store.
+// integer sum of the sampler's own masses at temperature 1 by wave shuffle and LDS (row_max_mass)
+// -- leaves {m, lnz} per row, and with targets the log-probability of one given token per row
+// (score).  The pick kernels take that pair and write the picked token's log-probability beside the
+// token, under the conditions of the token's own store.
 //
-// The row helpers (for_row / for_regs, amax_key, the workgroup reductions) live in row_common.h,
-// shared with beam.hip.
+// The row itself (Row and its sweeps), key16 and its inverse, key_token, the workgroup reductions
+// and row_max_mass live in row_common.h, shared with beam.hip; amax_key in common.h.
 #include "common.h"
 #include "kernels.h"
 #include "row_common.h"
@@ -51,12 +51,6 @@ namespace {
 
 constexpr int kCopies = 32;
 constexpr int kMassCopies = kCopies / 2;  // 64-bit bins in the same array
-
-// order-preserving 16-bit key of a bf16 bit pattern (-0 counts as +0, as in a float compare)
-MG_DEVICE uint32_t key16(uint32_t bits) {
-  if (bits == 0x8000u) bits = 0u;
-  return (bits & 0x8000u) ? (bits ^ 0xffffu) : (bits | 0x8000u);
-}
 
 MG_DEVICE uint32_t ordered_f32(float s) {
   if (s == 0.f) s = 0.f;  // -0 -> +0
@@ -196,23 +190,8 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
   const uint32_t top_p = params[6];
   const bool nucleus = top_p - 1u < 0x3f7fffffu;  // fp32 bits of a value in (0, 1)
 
-  // the row, in registers when it fits (for_regs)
+  const Row rw(row, V);  // in registers when it fits
   const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
-  const bool cached = nv <= kRegVec * kThreads;
-  uint4 regs[kRegVec];
-  uint32_t tail = 0u;
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < kRegVec; ++j) {
-      const int v = (int)threadIdx.x + j * kThreads;
-      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (threadIdx.x < 8 && ti < V) tail = row[ti];
-  }
-  auto sweep = [&](auto f) {
-    if (cached) for_regs(regs, tail, V, f);
-    else for_row(row, V, f);
-  };
 
   // ---- pass A: row maximum (+ high-byte histogram)
   uint32_t* my = hist + (lane & (kCopies - 1));
@@ -220,12 +199,12 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
   __syncthreads();
   float m = -INFINITY;
   if (select) {
-    sweep([&](int, uint32_t bits) {
+    rw.sweep([&](int, uint32_t bits) {
       m = fmaxf(m, bf2f(bits));
       atomicAdd(my + (key16(bits) >> 8) * kCopies, 1u);
     });
   } else {
-    sweep([&](int, uint32_t bits) { m = fmaxf(m, bf2f(bits)); });
+    rw.sweep([&](int, uint32_t bits) { m = fmaxf(m, bf2f(bits)); });
   }
   m = block_max<kWaves>(m, redf);
 
@@ -236,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     hist_select(hist, scan, (uint32_t)top_k, hi, rest);
     hist_clear(hist);
     __syncthreads();
-    sweep([&](int, uint32_t bits) {
+    rw.sweep([&](int, uint32_t bits) {
       const uint32_t k = key16(bits);
       if ((k >> 8) == hi) atomicAdd(my + (k & 0xffu) * kCopies, 1u);
     });
@@ -253,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
 #pragma unroll
     for (int j = 0; j < kRegVec; ++j) {
       if ((int)threadIdx.x + j * kThreads < nv)
-        for_vec(regs[j], j * 8, [&](int e, uint32_t bits) { kept |= key16(bits) >= t ? 1ull << e : 0ull; });
+        for_vec(rw.regs[j], j * 8, [&](int e, uint32_t bits) { kept |= key16(bits) >= t ? 1ull << e : 0ull; });
     }
     return kept;
   };
@@ -264,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
       const int i = (((int)threadIdx.x + (e >> 3) * kThreads) << 3) + (e & 7);
       f(i, (uint32_t)row[i]);
     }
-    if (threadIdx.x < 8 && ti < V) f(ti, tail);
+    if (threadIdx.x < 8 && ti < V) f(ti, rw.tail);
   };
 
   // ---- nucleus: the lowest key whose mass strictly above is below ceil(top_p * Z), by the same
@@ -272,11 +251,11 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
   if (nucleus) {
     unsigned long long* mhist = reinterpret_cast<unsigned long long*>(hist);
     unsigned long long* mine = mhist + (lane & (kMassCopies - 1));
-    const bool few = select && cached;
+    const bool few = select && rw.cached;
     const unsigned long long kept = few ? mark(thr) : 0ull;
     auto pass = [&](auto f) {
       if (few) for_marked(kept, f);
-      else sweep(f);
+      else rw.sweep(f);
     };
     uint32_t hi, lo;
     unsigned long long rest, unused;
@@ -304,7 +283,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
 
   if constexpr (KEPT) {  // the kept set itself: its lowest value and its size
     uint32_t cnt = 0u, lowest = 0xffffffffu;
-    sweep([&](int, uint32_t bits) {
+    rw.sweep([&](int, uint32_t bits) {
       const uint32_t k = key16(bits);
       if (k < thr || bits == 0xff80u) return;
       ++cnt;
@@ -327,8 +306,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
         cnt += scan[i];
         lowest = (uint32_t)redk[i] < lowest ? (uint32_t)redk[i] : lowest;
       }
-      const uint32_t bits = (lowest & 0x8000u) ? (lowest ^ 0x8000u) : (lowest ^ 0xffffu);  // key16 undone
-      kept_out[2 * b] = cnt ? (int)bits : 0xff80;
+      kept_out[2 * b] = cnt ? (int)key16_bits(lowest) : 0xff80;
       kept_out[2 * b + 1] = (int)cnt;
     }
     return;
@@ -346,23 +324,14 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const bf16_t* __restri
     const unsigned long long k = ((unsigned long long)ordered_f32(s) << 32) | (0xffffffffu - (uint32_t)i);
     best = k > best ? k : best;
   };
-  if ((select || nucleus) && cached) {  // top-k and the nucleus keep a few elements per row
+  if ((select || nucleus) && rw.cached) {  // top-k and the nucleus keep a few elements per row
     for_marked(mark(thr), score);
   } else {
     for_row(row, V, score);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long k = shfl_xor_u64(best, o);
-    best = k > best ? k : best;
-  }
-  if (lane == 0) redk[w] = best;
-  __syncthreads();
+  best = block_max_key(best, redk);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 1; i < kWaves; ++i) best = redk[i] > best ? redk[i] : best;
-    long t = (long)(0xffffffffu - (uint32_t)best);
-    if (t >= V) t = V - 1;  // no candidate (a row without a finite maximum): still a valid id
+    const long t = key_token(best, V);
     if constexpr (RAGGED) {
       ragged_finish(t, b, rpos, (int)params[5], pos_dev, done, tok, seq, seq_ld, row, lse, lp);
     } else {
@@ -392,30 +361,13 @@ __global__ __launch_bounds__(kThreads) void pick_greedy_kernel(const bf16_t* __r
   const int p = pos[b];
   const bf16_t* row = logits + (long)b * ld;
   unsigned long long best = 0ull;
-  auto rank = [&](int i, uint32_t bits) {
+  Row(row, V).sweep([&](int i, uint32_t bits) {
     const unsigned long long k = amax_key(bf2f(bits), i);
     best = k > best ? k : best;
-  };
-  // a row that fits the registers is loaded with every load in flight together, as in the sampler
-  const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
-  if (nv <= kRegVec * kThreads) {
-    uint4 regs[kRegVec];
-#pragma unroll
-    for (int j = 0; j < kRegVec; ++j) {
-      const int v = (int)threadIdx.x + j * kThreads;
-      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
-    const uint32_t tail = (threadIdx.x < 8 && ti < V) ? (uint32_t)row[ti] : 0u;
-    for_regs(regs, tail, V, rank);
-  } else {
-    for_row(row, V, rank);
-  }
+  });
   best = block_max_key(best, redk);
-  if (threadIdx.x == 0) {
-    long t = (long)(0xffffffffu - (uint32_t)best);
-    if (t >= V) t = V - 1;
-    ragged_finish(t, b, p, (int)params[5], pos, done, tok, seq, seq_ld, row, lse, lp);
-  }
+  if (threadIdx.x == 0)
+    ragged_finish(key_token(best, V), b, p, (int)params[5], pos, done, tok, seq, seq_ld, row, lse, lp);
 }
 
 // {m, lnz} of the log-probability rule (common.h) for every row of logits [M, ld], and with targets
@@ -428,28 +380,9 @@ __global__ __launch_bounds__(kThreads) void lse_kernel(const bf16_t* __restrict_
   __shared__ unsigned long long redq[kWaves];
   const long r = blockIdx.x;
   const bf16_t* row = logits + r * ld;
-  const int nv = V >> 3, ti = nv * 8 + (int)threadIdx.x;
-  const bool cached = nv <= kRegVec * kThreads;
-  uint4 regs[kRegVec];
-  uint32_t tail = 0u;
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < kRegVec; ++j) {
-      const int v = (int)threadIdx.x + j * kThreads;
-      regs[j] = v < nv ? ld16(row + (long)v * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (threadIdx.x < 8 && ti < V) tail = row[ti];
-  }
-  auto sweep = [&](auto f) {
-    if (cached) for_regs(regs, tail, V, f);
-    else for_row(row, V, f);
-  };
-  float m = -INFINITY;
-  sweep([&](int, uint32_t bits) { m = fmaxf(m, bf2f(bits)); });
-  m = block_max<kWaves>(m, redf);
-  unsigned long long z = 0ull;
-  sweep([&](int, uint32_t bits) { z += sample_mass(bits, m, 1.0f); });
-  z = block_sum_u64(z, redq);
+  float m;
+  unsigned long long z;
+  row_max_mass(Row(row, V), redf, redq, m, z, [](int, uint32_t) {});
   if (threadIdx.x == 0) {
     const float lnz = logprob_lnz(z);
     lse[2 * r] = m;

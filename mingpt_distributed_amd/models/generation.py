@@ -371,20 +371,36 @@ class _GpuCache:
         [B] from the lse kernel."""
         return tok, self.C.logits_lse(self.logits, self.model.config.vocab_size, tok.contiguous())[1]
 
+    def _lp_args(self, logits, V, st, logprobs):
+        """The trailing ``(lse, lp)`` arguments of a pick call on ``logits``: with ``logprobs`` the
+        lse kernel's {m, lnz} of these logits and the state's ``lp`` buffer, else nothing -- no
+        launch, and a state that owns an ``lp`` buffer from an earlier call does not pass it."""
+        return (self.C.logits_lse(logits, V), st["lp"]) if logprobs else (None, None)
+
+    def _ragged_step(self, st, greedy, logprobs):
+        """The decode step over per-row state ``st`` (``pos``, ``done``, ``tok``, ``seq``, ``params``,
+        with ``logprobs`` also ``lp``): ``_decode`` with one position per row, then the ragged pick
+        kernel, greedy or sampled."""
+        V = self.model.config.vocab_size
+
+        def step():
+            logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
+            self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy,
+                               *self._lp_args(logits, V, st, logprobs))
+            return logits[:, :V]
+
+        return step
+
     def _greedy_lp(self, tok, pos, n):
         """``greedy`` with log-probabilities: (tokens [B, n], lp [B, n]).  A loop of its own
-        (``"greedy_lp"``) on the plain LM head, the lse kernel and the ragged greedy pick kernel,
+        (``"greedy_lp"``) on the ragged greedy step with log-probabilities (``_ragged_step``: the
+        plain LM head, the lse kernel and the ragged greedy pick kernel) over a state of its own,
         with every row at the same position and no stop token -- not the fused argmax of the LM
         head, whose keys have no room for the number.  Both rank the stored bf16 logits with the
         first index on ties.  ``seq`` / ``lp`` are one column longer than the ragged state's: the
         pick kernel keeps the position below the last column, and a window's last token sits at
         column tmax."""
         B = tok.shape[0]
-        V = self.model.config.vocab_size
-
-        def seed(st):
-            st["tok"].copy_(tok)
-            st["pos"].fill_(pos)
 
         def make():
             dev = tok.device
@@ -393,18 +409,12 @@ class _GpuCache:
                   "seq": torch.zeros(B, self.tmax + 2, dtype=torch.long, device=dev),
                   "lp": torch.zeros(B, self.tmax + 2, dtype=torch.float32, device=dev),
                   "params": torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=dev)}
-
-            def step():
-                logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
-                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], True,
-                                   self.C.logits_lse(logits, V), st["lp"])
-                return logits[:, :V]
-
-            return _Loop(step, st)
+            return _Loop(self._ragged_step(st, True, True), st)
 
         lp = self._loop("greedy_lp", make)
         st = lp.state
-        seed(st)  # after the loop is built: its warm-up step moved the state
+        st["tok"].copy_(tok)  # after the loop is built: its warm-up step moved the state
+        st["pos"].fill_(pos)
         lp.run(n)
         return st["seq"][:, pos + 1:pos + 1 + n], st["lp"][:, pos + 1:pos + 1 + n]
 
@@ -498,11 +508,8 @@ class _GpuCache:
 
             def step():
                 logits = self._decode(st["tok"], st["pos"], st["hpos"])
-                if logprobs:
-                    self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"],
-                                         self.C.logits_lse(logits, V), st["lp"])
-                else:
-                    self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"])
+                self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"],
+                                     *self._lp_args(logits, V, st, logprobs))
                 return logits[:, :V]
 
             return _Loop(step, st)
@@ -557,12 +564,8 @@ class _GpuCache:
         st["done"].zero_()
         self._ragged_params(st, words)
         logits = self.logits  # [B, V] view of the padded [B, ld] buffer the LM head wrote
-        if logprobs:
-            self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
-                               greedy, self.C.logits_lse(logits, logits.size(1)), st["lp"])
-        else:
-            self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
-                               greedy)
+        self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
+                           greedy, *self._lp_args(logits, logits.size(1), st, logprobs))
         return st
 
     def ragged(self, n, words, greedy, logprobs=False):
@@ -579,16 +582,7 @@ class _GpuCache:
         kernel, which writes ``lp[b, pos[b] + 1]`` with the token."""
         st = self.ragged_state()
         self._ragged_params(st, words)
-        V = self.model.config.vocab_size
-
-        def step():
-            logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
-            if logprobs:
-                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy,
-                                   self.C.logits_lse(logits, V), st["lp"])
-            else:
-                self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy)
-            return logits[:, :V]
+        step = self._ragged_step(st, greedy, logprobs)
 
         def warm():  # with every row marked finished the step is idempotent: the state the caller
             done = st["done"].clone()  # set up is left as it is
@@ -768,22 +762,15 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
                 lps.append(R.token_logprob(logits[:, -1, :], nxt))
             idx = torch.cat((idx, nxt), dim=1)
         return done(idx)
-    if idx.is_cuda and not do_sample and max_new_tokens > 0:
-        if return_logprobs:
-            return _generate_windowed_gpu(model, idx, max_new_tokens,
-                                          lambda c, T: c.with_logprob(c.logits.argmax(-1)),
-                                          lambda c, tok, L, n, T: c.greedy(tok, L, n, logprobs=True), True)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.logits.argmax(-1),
-                                      lambda c, tok, L, n, T: c.greedy(tok, L, n))
-    if idx.is_cuda and seeded and max_new_tokens > 0:  # the draw counter of a token is its column T
-        words = lambda T: _sample_words(seed, T, temperature, top_k, top_p)
-        if return_logprobs:
-            return _generate_windowed_gpu(model, idx, max_new_tokens,
-                                          lambda c, T: c.with_logprob(c.sample_prefill(words(T))),
-                                          lambda c, tok, L, n, T: c.sample(tok, L, n, words(T), logprobs=True),
-                                          True)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, lambda c, T: c.sample_prefill(words(T)),
-                                      lambda c, tok, L, n, T: c.sample(tok, L, n, words(T)))
+    if idx.is_cuda and max_new_tokens > 0 and (seeded or not do_sample):
+        if seeded:  # the draw counter of a token is its column T
+            words = lambda T: _sample_words(seed, T, temperature, top_k, top_p)
+            first = lambda c, T: c.sample_prefill(words(T))
+            loop = lambda c, tok, L, n, T: c.sample(tok, L, n, words(T), logprobs=return_logprobs)
+        else:
+            first = lambda c, T: c.logits.argmax(-1)
+            loop = lambda c, tok, L, n, T: c.greedy(tok, L, n, logprobs=return_logprobs)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
@@ -811,31 +798,32 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     position ``L``) for every position the window still has room for.  ``T`` is the column of the
     call's first token in the returned sequence.  Once the sequence outgrows block_size, each token
     is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
-    (``/root/reference/mingpt/model.py:333``).  ``logprobs``: ``first`` and ``loop`` return (tokens,
-    log-probabilities) pairs, and so does this."""
+    (``/root/reference/mingpt/model.py:333``).  ``logprobs``: the first token gets its
+    log-probability from the prefill logits (``with_logprob``), ``loop`` returns a (tokens,
+    log-probabilities) pair, and so does this."""
     bs = model.block_size
     B, T0 = idx.shape
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
     out[:, :T0] = idx
-    lp = torch.zeros(out.shape, dtype=torch.float32, device=idx.device) if logprobs else None
+    outs = (out, torch.zeros(out.shape, dtype=torch.float32, device=idx.device)) if logprobs else (out,)
+
+    def put(cols, vals):  # tokens, or with logprobs the (tokens, lp) pair, into columns ``cols``
+        for dst, v in zip(outs, vals if logprobs else (vals,)):
+            dst[:, cols] = v
+
     T, end = T0, T0 + max_new_tokens
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
         cache = _gpu_cache(model, ctx, bs)
-        if logprobs:
-            out[:, T], lp[:, T] = first(cache, T)
-        else:
-            out[:, T] = first(cache, T)
+        tok = first(cache, T)
+        put(T, cache.with_logprob(tok) if logprobs else tok)
         T += 1
         n = min(end - T, bs - L)
         if n > 0:
-            if logprobs:
-                out[:, T:T + n], lp[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
-            else:
-                out[:, T:T + n] = loop(cache, out[:, T - 1:T], L, n, T)
+            put(slice(T, T + n), loop(cache, out[:, T - 1:T], L, n, T))
             T += n
-    return (out, lp) if logprobs else out
+    return outs if logprobs else out
 
 
 # --------------------------------------------------------------------------- ragged batches
@@ -861,6 +849,18 @@ def _ragged_prompts(prompts, who="generate_batch"):
         raise ValueError(f"{who}: no prompts")
     device = rows[0].device
     return [r.to(device=device, dtype=torch.long) for r in rows], device
+
+
+def _check_token_ids(who, V, tokens, pad_token=None, eos_token=None, what="prompt token"):
+    """ValueError unless ``pad_token`` and ``eos_token`` (None: not given) and every entry of
+    ``tokens`` are token ids, 0 <= id < V."""
+    if pad_token is not None and not 0 <= int(pad_token) < V:
+        raise ValueError(f"{who}: pad_token {pad_token} is not a token id (vocab {V})")
+    if eos_token is not None and not 0 <= int(eos_token) < V:
+        raise ValueError(f"{who}: eos_token {eos_token} is not a token id (vocab {V})")
+    lo, hi = tokens.aminmax()
+    if int(lo) < 0 or int(hi) >= V:
+        raise ValueError(f"{who}: {what} outside [0, {V})")
 
 
 @torch.no_grad()
@@ -899,10 +899,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     if Lmax + max_new_tokens > bs:
         raise ValueError(f"generate_batch: longest prompt ({Lmax}) + max_new_tokens ({max_new_tokens}) exceeds "
                          f"block_size ({bs}); this entry point has no sliding window")
-    if not 0 <= int(pad_token) < V:
-        raise ValueError(f"generate_batch: pad_token {pad_token} is not a token id (vocab {V})")
-    if eos_token is not None and not 0 <= int(eos_token) < V:
-        raise ValueError(f"generate_batch: eos_token {eos_token} is not a token id (vocab {V})")
+    _check_token_ids("generate_batch", V, torch.cat(rows), pad_token, eos_token)
     R.check_sample_args(temperature, top_k, top_p)
     if do_sample and seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
@@ -912,9 +909,6 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     tokens = torch.full((B, Lmax + max_new_tokens), int(pad_token), dtype=torch.long, device=device)
     for b, r in enumerate(rows):
         tokens[b, :lens[b]] = r
-    lo, hi = tokens.aminmax()  # the padding is pad_token, a valid id
-    if int(lo) < 0 or int(hi) >= V:
-        raise ValueError(f"generate_batch: prompt token outside [0, {V})")
     logprobs = torch.zeros(tokens.shape, dtype=torch.float32, device=device) if return_logprobs else None
     if max_new_tokens == 0:
         return (tokens, lengths, logprobs) if return_logprobs else (tokens, lengths)
@@ -1032,13 +1026,7 @@ def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Op
     if T + n > bs:
         raise ValueError(f"{who}: prompt ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
                          f"point has no sliding window")
-    if not 0 <= int(pad_token) < V:
-        raise ValueError(f"{who}: pad_token {pad_token} is not a token id (vocab {V})")
-    if eos_token is not None and not 0 <= int(eos_token) < V:
-        raise ValueError(f"{who}: eos_token {eos_token} is not a token id (vocab {V})")
-    lo, hi = idx.aminmax()
-    if int(lo) < 0 or int(hi) >= V:
-        raise ValueError(f"{who}: prompt token outside [0, {V})")
+    _check_token_ids(who, V, idx, pad_token, eos_token)
     a = float(length_penalty)
     device = idx.device
     before_use(*model.parameters())
@@ -1167,9 +1155,7 @@ def score(model, idx, lengths=None):
     tokens = torch.zeros((B, T), dtype=torch.long, device=device)
     for b, r in enumerate(rows):
         tokens[b, :lens[b]] = r
-    lo, hi = tokens.aminmax()  # the padding is 0, a valid id
-    if int(lo) < 0 or int(hi) >= V:
-        raise ValueError(f"score: token outside [0, {V})")
+    _check_token_ids("score", V, tokens, what="token")  # the padding is 0, a valid id
     before_use(*model.parameters())
     out = torch.zeros((B, T), dtype=torch.float32, device=device)
     if T == 1:
