@@ -565,13 +565,19 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
 // with pos_stride 1 it is int32 [B], one position per row (ragged batches)
 // part / counters (optional): the decode state's own workspace (kernels.h); without them a
 // temporary pair is allocated for this call (tests; not for captured graphs)
+// group = K > 1 (speculative decoding, kernels.h): K rows per cache row -- qkv_new [B * K, 3D], out
+// [B * K, D], pos_dev int32 [B * K] with pos_stride 1 (row b * K holds the sequence's position), the
+// workspace sized for B * K rows
 at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, int64_t H,
                             int64_t pos, const c10::optional<at::Tensor>& pos_dev,
                             const c10::optional<at::Tensor>& part,
-                            const c10::optional<at::Tensor>& counters, int64_t pos_stride) {
+                            const c10::optional<at::Tensor>& counters, int64_t pos_stride, int64_t group) {
   CHECK_BF16(qkv_new); CHECK_BF16(cache); CHECK_CONTIG(qkv_new); CHECK_CONTIG(cache);
   TORCH_CHECK(cache.dim() == 3, "cache must be [B, Tmax, 3D]");
-  const int64_t B = cache.size(0), Tmax = cache.size(1), D3 = cache.size(2), D = D3 / 3;
+  TORCH_CHECK(group >= 1 && group <= mg::kSpecRowsMax, "attention_decode: group must be in 1..8");
+  TORCH_CHECK(group == 1 || (pos_dev.has_value() && pos_stride == 1),
+              "attention_decode: group > 1 needs pos_dev with pos_stride 1");
+  const int64_t Bs = cache.size(0), B = Bs * group, Tmax = cache.size(1), D3 = cache.size(2), D = D3 / 3;
   TORCH_CHECK(qkv_new.numel() == B * D3 && D % H == 0, "attention_decode: shape mismatch");
   TORCH_CHECK(pos >= 0 && pos < Tmax && (D / H) % 8 == 0 && D / H <= 128, "attention_decode: pos / head dim");
   TORCH_CHECK(Tmax <= 4096, "attention_decode: KV cache longer than 4096 positions");
@@ -601,9 +607,9 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
     pt = at::empty({np}, cache.options().dtype(at::kFloat));
     ct = at::zeros({B * H}, cache.options().dtype(at::kInt));
   }
-  mg::attention_decode(bp(qkv_new), bp(cache), bp(out), (int)B, (int)H, (int)(D / H), Tmax, (int)pos,
+  mg::attention_decode(bp(qkv_new), bp(cache), bp(out), (int)Bs, (int)H, (int)(D / H), Tmax, (int)pos,
                        cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd,
-                       (int)pos_stride);
+                       (int)pos_stride, (int)group);
   return out;
 }
 
@@ -873,6 +879,76 @@ void beam_reorder(const at::Tensor& kv, int64_t W, const at::Tensor& parent, con
                    pos.data_ptr<int>(), cp, cur_stream());
 }
 
+// ------------------------------------------------------------------------------- speculative decoding
+// spec.hip (kernels.h).  B sequences, K rows each; every buffer lives on seq's / the logits' device and
+// is updated in place.
+
+// seq int64 [B, L] with 1 <= L < 2^31 and 2 <= K <= 8: B, the device.
+int64_t spec_seq(const char* op, const at::Tensor& seq, int64_t K) {
+  CHECK_I64(seq); CHECK_CONTIG(seq); CHECK_DEV(seq);
+  TORCH_CHECK(seq.dim() == 2 && seq.size(0) >= 1 && seq.size(1) >= 1 && seq.size(1) <= 0x7fffffff, op,
+              ": seq int64 [B, L]");
+  TORCH_CHECK(K >= 2 && K <= mg::kSpecRowsMax, op, ": K must be in 2..8");
+  return seq.size(0);
+}
+
+// The draft kernel: seq int64 [B, L], pos int32 [B], ctl int32 [4] -> tok int64 [B * K], pos_rows
+// int32 [B * K], has_draft int32 [B].
+void spec_draft(const at::Tensor& seq, const at::Tensor& pos, const at::Tensor& ctl, int64_t K, const at::Tensor& tok,
+                const at::Tensor& pos_rows, const at::Tensor& has_draft) {
+  const char* op = "spec_draft";
+  const int64_t B = spec_seq(op, seq, K);
+  const at::Device dev = seq.device();
+  dev_i32(op, "pos", pos, B, dev);
+  dev_i32(op, "ctl", ctl, mg::kSpecCtlWords, dev);
+  dev_i32(op, "pos_rows", pos_rows, B * K, dev);
+  dev_i32(op, "has_draft", has_draft, B, dev);
+  CHECK_I64(tok); CHECK_CONTIG(tok);
+  TORCH_CHECK(tok.numel() == B * K && tok.device() == dev, op, ": tok int64 with B * K elements");
+  DevGuard g(dev);
+  mg::spec_draft(seq.data_ptr<int64_t>(), seq.size(1), (int)B, (int)K, pos.data_ptr<int>(), ctl.data_ptr<int>(),
+                 tok.data_ptr<int64_t>(), pos_rows.data_ptr<int>(), has_draft.data_ptr<int>(), cur_stream());
+}
+
+// The row argmax: g int32 [R] (written when given, else allocated) of logits [R, ld] bf16.
+at::Tensor spec_argmax(const at::Tensor& logits, int64_t V, const c10::optional<at::Tensor>& g) {
+  const char* op = "spec_argmax";
+  const LogitsRows lr = logits_rows(op, logits, V);
+  TORCH_CHECK(lr.rows <= 0x7fffffff && V <= 0x7fffffff, op, ": too many rows");
+  DevGuard guard(lr.dev);
+  at::Tensor out;
+  if (g.has_value() && g->defined()) {
+    dev_i32(op, "g", *g, lr.rows, lr.dev);
+    out = *g;
+  } else {
+    out = at::empty({lr.rows}, logits.options().dtype(at::kInt));
+  }
+  mg::spec_argmax(bp(logits), lr.ld, (int)lr.rows, (int)V, out.data_ptr<int>(), cur_stream());
+  return out;
+}
+
+// The accept kernel: g int32 [B * K], tok int64 [B * K], has_draft int32 [B] -> seq int64 [B, L], pos,
+// steps int32 [B], hist int32 [B, K + 1].
+void spec_accept(const at::Tensor& g, const at::Tensor& tok, const at::Tensor& has_draft, int64_t K,
+                 const at::Tensor& pos, const at::Tensor& ctl, const at::Tensor& seq, const at::Tensor& steps,
+                 const at::Tensor& hist) {
+  const char* op = "spec_accept";
+  const int64_t B = spec_seq(op, seq, K);
+  const at::Device dev = seq.device();
+  dev_i32(op, "g", g, B * K, dev);
+  dev_i32(op, "has_draft", has_draft, B, dev);
+  dev_i32(op, "pos", pos, B, dev);
+  dev_i32(op, "ctl", ctl, mg::kSpecCtlWords, dev);
+  dev_i32(op, "steps", steps, B, dev);
+  dev_i32(op, "hist", hist, B * (K + 1), dev);
+  CHECK_I64(tok); CHECK_CONTIG(tok);
+  TORCH_CHECK(tok.numel() == B * K && tok.device() == dev, op, ": tok int64 with B * K elements");
+  DevGuard guard(dev);
+  mg::spec_accept(g.data_ptr<int>(), tok.data_ptr<int64_t>(), has_draft.data_ptr<int>(), (int)B, (int)K,
+                  pos.data_ptr<int>(), ctl.data_ptr<int>(), seq.data_ptr<int64_t>(), seq.size(1), steps.data_ptr<int>(),
+                  hist.data_ptr<int>(), cur_stream());
+}
+
 // ------------------------------------------------------------------------------- native RCCL
 // csrc/comm/rccl_comm.cpp. Every collective runs on the communicator's comm stream after the
 // tensor's device's CURRENT stream (the producers); comm_wait makes that stream wait again.
@@ -1018,7 +1094,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_supported", &mg::gemv_supported);
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
-        py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
+        py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
         py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none(),
         py::arg("lse") = py::none(), py::arg("lp") = py::none());
@@ -1035,6 +1111,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hist_tok"), py::arg("hist_score"), py::arg("pos"), py::arg("ctl"));
   m.def("beam_reorder", &beam_reorder, py::arg("kv"), py::arg("W"), py::arg("parent"), py::arg("pos"),
         py::arg("ctl") = py::none());
+  m.def("spec_draft", &spec_draft, py::arg("seq"), py::arg("pos"), py::arg("ctl"), py::arg("K"), py::arg("tok"),
+        py::arg("pos_rows"), py::arg("has_draft"));
+  m.def("spec_argmax", &spec_argmax, py::arg("logits"), py::arg("V"), py::arg("g") = py::none());
+  m.def("spec_accept", &spec_accept, py::arg("g"), py::arg("tok"), py::arg("has_draft"), py::arg("K"), py::arg("pos"),
+        py::arg("ctl"), py::arg("seq"), py::arg("steps"), py::arg("hist"));
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });

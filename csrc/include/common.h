@@ -302,6 +302,27 @@ MG_DEVICE float token_logprob(uint32_t bits, float m, float lnz) { return (bf2f(
 // {m, lnz} is the lse kernel's, bit for bit (row_common.h holds the shared row code); the result
 // depends on the rows' values and the scores alone, not on a reduction order or graph / eager launch.
 
+// ---------------------------------------------------------------- Speculative greedy decoding
+// K = draft_len + 1 <= 8 rows per sequence and step: the last committed token and K - 1 guessed ones
+// run at K consecutive positions of one KV cache, and the longest prefix of guesses that the model's
+// own argmax confirms is kept.  Integers only; the output is the greedy output.  Per sequence, with
+// tokens s[0 .. p] committed (p the device position) and end = T + n - 1 the column of the last token:
+// Draft (prompt lookup).  For every e in 0 .. p - 1, ml(e) is the largest m <= ngram (1 .. 4) with
+//   e - j >= 0 and s[e - j] == s[p - j] for every j < m.  Take the e with the largest (ml, e): the
+//   longest suffix match, the most recent on ties.  If the best ml is 0 there is no draft.
+//   Otherwise extend: x = s[0 .. p], and for r = 1 .. K - 1: d_r = x[e + r], then append d_r to x
+//   (e + r <= p + r - 1, so the value exists: a repetition with a period below K drafts through
+//   itself).  Row r carries token d_r (row 0: s[p]) at position p + r; without a draft rows
+//   1 .. K - 1 carry s[p] and a flag says "no draft".
+// Accept.  g_r is the argmax of row r's stored bf16 logits, first index on ties (amax_key's order,
+//   the ragged greedy pick's).  a is the largest value with d_r == g_{r-1} for all 1 <= r <= a; 0
+//   without a draft.  The step emits min(a + 1, end - p) tokens g_0, g_1, ... into s[p + 1 ...],
+//   advances p by that count and bumps steps and emitted_hist[count].  A sequence with p == end is
+//   left alone: no token, no position change, no statistics.
+// Row r <= a saw exactly the committed tokens s[0 .. p + r] (its drafts were confirmed), and every
+// kernel of the step computes a row from that row's inputs alone, so g_r is what plain greedy
+// decoding picks at position p + r: the emitted tokens are generate()'s, bit for bit.
+
 // ---------------------------------------------------------------- GELU (tanh approximation)
 constexpr float kGeluK0 = 0.7978845608028654f;  // sqrt(2/pi)
 constexpr float kGeluK1 = 0.044715f;

@@ -140,6 +140,27 @@ void beam_merge(int B, int W, int V, const int* cand_tok, const float* cand_c, f
 void beam_reorder(bf16_t* kv, int L, long layer_stride, int B, int W, int Tmax, int D, const int* parent,
                   const int* pos, int* ctl, hipStream_t stream);
 
+// spec.hip -- the kernels around a speculative verify step (the rule in common.h, 'Speculative
+// greedy decoding'): B sequences, K <= 8 rows each, row b * K + r = row r of sequence b.  ctl
+// (device, 4 x int32): {ngram (clamped to 1 .. 4), end = the column of the last token, 0, 0}.
+constexpr int kSpecRowsMax = 8;
+constexpr int kSpecNgramMax = 4;
+constexpr int kSpecCtlWords = 4;
+// Per sequence b with committed tokens seq[b, 0 .. pos[b]] (seq int64 [B, seq_ld], pos clamped to
+// [0, seq_ld)): the draft of the rule.  Writes tok[b * K + r] (row 0: seq[b, pos[b]]; without a
+// draft every row), pos_rows[b * K + r] = pos[b] + r and has_draft[b] (1 / 0).
+void spec_draft(const int64_t* seq, long seq_ld, int B, int K, const int* pos, const int* ctl, int64_t* tok,
+                int* pos_rows, int* has_draft, hipStream_t stream);
+// g[r] = the argmax of row r of logits [R, ld] (layout as for sample_logits) over its first V columns,
+// first index on ties: the ragged greedy pick's ranking of the stored bf16 logits.
+void spec_argmax(const bf16_t* logits, long ld, int R, int V, int* g, hipStream_t stream);
+// Per sequence b with pos[b] < min(end, seq_ld - 1): a = the number of leading drafts with
+// tok[b * K + r] == g[b * K + r - 1] (0 without a draft), cnt = min(a + 1, end - pos[b]);
+// seq[b, pos[b] + 1 + i] = g[b * K + i] for i < cnt, pos[b] += cnt, steps[b] += 1 and
+// hist[b, cnt] += 1 (hist int32 [B, K + 1]).  Any other sequence is left alone.
+void spec_accept(const int* g, const int64_t* tok, const int* has_draft, int B, int K, int* pos, const int* ctl,
+                 int64_t* seq, long seq_ld, int* steps, int* hist, hipStream_t stream);
+
 // elementwise.hip
 void bias_act_fwd(const bf16_t* x, const bf16_t* b, bf16_t* pre, bf16_t* y, long M, int N, int act,
                   hipStream_t stream);
@@ -201,9 +222,16 @@ void attention_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, con
 // another state's (possibly freed) buffers.  pos_dev: the position in device memory (clamped to
 // [0, Tmax)), one for the batch (pos_stride 0) or one per row (pos_stride 1, ragged batches: row b
 // appends at cache row pos_dev[b] and attends to keys 0..pos_dev[b], with its own split count).
+// group = K > 1 (speculative decoding; needs pos_dev, one int per row): qkv_new [B * K, 3D] and out
+// [B * K, D] hold K rows per sequence of cache [B, Tmax, 3D].  Row m = b * K + r sits at position
+// base + r, base = pos_dev[b * K] clamped to [0, Tmax): it appends its K/V at cache row base + r of
+// sequence b and attends to keys 0 .. base + r -- those at or past base from qkv_new rows b * K ..,
+// the earlier ones from the cache -- with the split structure of a plain decode of B sequences at
+// that position.  A row with base + r > Tmax - 1 appends nothing and gets a zero out row.  part and
+// counters are then sized for B * K rows (attention_decode_part_floats(B * K, H, hd), B * K * H).
 size_t attention_decode_part_floats(int B, int H, int hd);
 void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, int H, int hd,
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                      const int* pos_dev = nullptr, int pos_stride = 0);
+                      const int* pos_dev = nullptr, int pos_stride = 0, int group = 1);
 
 }  // namespace mg

@@ -24,8 +24,19 @@ namespace {
 // partials (sc1: no cache of another CU or XCD is involved), each wave draining its stores before
 // the workgroup's counter increment (MI355X_MICROARCH 'Correctness boundaries').  The last
 // workgroup resets the counter, so the kernel can be replayed inside a hipGraph.
+//
+// GROUPED (speculative decoding: `group` = K rows per sequence, pos_dev one int per row): row m is
+// row r = m % K of sequence m / K, sits at position base + r with base = pos_dev[(m / K) * K]
+// (clamped to [0, Tmax - 1]) and uses that sequence's cache.  It appends its own K/V at cache row
+// base + r, takes keys j >= base from qkv_new row (m / K) * K + (j - base) and keys j < base from
+// the cache: no row reads a cache row at or past base, so the group's appends do not race its
+// reads.  A row past Tmax - 1 appends nothing, touches no counter and writes zeros to its out row.
+// Everything else -- Se, CH, the key order, the combine -- is the plain kernel's at that position
+// (the launcher picks KPS from the number of sequences), so a row computes bit for bit what a plain
+// decode of the sequence at base + r computes.  The plain instantiation is the code as it was.
 constexpr int kDecSplitsMax = 16;  // combine handles up to this many partials per (b, h)
 
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ qkv_new,
                                                           bf16_t* __restrict__ cache,
                                                           bf16_t* __restrict__ out, int H, int hd,
@@ -35,7 +46,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
                                                           int KPS,
                                                           float* __restrict__ part,
                                                           unsigned* __restrict__ counters,
-                                                          int pos_stride) {
+                                                          int pos_stride, int group) {
   __shared__ float qs[128];
   __shared__ float sc[256];
   __shared__ float red[16];
@@ -48,10 +59,23 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   // CH and the early return -- is per row, and the last-arrival counter is per (b, h) already).
   // A right-padded prefill leaves garbage K/V in cache rows at or past a row's length; no step
   // reads it: row pos is taken from qkv_new, and written here before any later step reads it.
-  if (pos_dev) pos = min(max(pos_dev[(long)b * pos_stride], 0), (int)Tmax - 1);
+  int base = 0;                     // GROUPED: the first position of the row's group,
+  const bf16_t* gk = nullptr;       //   and the K columns of its row 0 in qkv_new (head hh)
   const long ld = 3L * D;
+  if constexpr (GROUPED) {
+    const int m0 = (b / group) * group;
+    base = min(max(pos_dev[m0], 0), (int)Tmax - 1);
+    pos = base + (b - m0);
+    gk = qkv_new + (long)m0 * ld + D + hh * hd;
+    if (pos > (int)Tmax - 1) {  // the whole workgroup: no room for this row
+      if (sp == 0 && threadIdx.x < hd) out[(long)b * D + hh * hd + threadIdx.x] = 0;
+      return;
+    }
+  } else {
+    if (pos_dev) pos = min(max(pos_dev[(long)b * pos_stride], 0), (int)Tmax - 1);
+  }
   const bf16_t* qrow = qkv_new + (long)b * ld + hh * hd;
-  bf16_t* cb = cache + (long)b * Tmax * ld;
+  bf16_t* cb = cache + (long)(GROUPED ? b / group : b) * Tmax * ld;
   if (sp == 0) {  // append this step's K/V at row pos (readers take row pos from qkv_new)
     for (int i = threadIdx.x; i < 2 * hd; i += 256) {
       const int which = i / hd, d = i % hd;
@@ -72,7 +96,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   float s = -INFINITY;
   if (threadIdx.x < nk) {
     const int j = k0 + threadIdx.x;
-    const bf16_t* kr = (j == pos) ? qrow + D : cb + (long)j * ld + D + hh * hd;
+    const bf16_t* kr = GROUPED ? (j >= base ? gk + (long)(j - base) * ld : cb + (long)j * ld + D + hh * hd)
+                               : ((j == pos) ? qrow + D : cb + (long)j * ld + D + hh * hd);
     float a = 0.f;
     for (int d = 0; d < hd; d += 8) {
       float k8[8];
@@ -99,7 +124,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int j = k0 + jj + u * ngrp;
-        const bf16_t* vr = (j == pos) ? qrow + 2 * D : cb + (long)j * ld + 2 * D + hh * hd;
+        const bf16_t* vr = GROUPED ? (j >= base ? gk + (long)(j - base) * ld + D : cb + (long)j * ld + 2 * D + hh * hd)
+                                   : ((j == pos) ? qrow + 2 * D : cb + (long)j * ld + 2 * D + hh * hd);
         vv[u] = ld16(vr + d8);
       }
 #pragma unroll
@@ -113,7 +139,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     }
     for (; jj < nk; jj += ngrp) {
       const int j = k0 + jj;
-      const bf16_t* vr = (j == pos) ? qrow + 2 * D : cb + (long)j * ld + 2 * D + hh * hd;
+      const bf16_t* vr = GROUPED ? (j >= base ? gk + (long)(j - base) * ld + D : cb + (long)j * ld + 2 * D + hh * hd)
+                                 : ((j == pos) ? qrow + 2 * D : cb + (long)j * ld + 2 * D + hh * hd);
       float v8[8];
       unpack8(ld16(vr + d8), v8);
       const float pj = sc[jj];
@@ -195,7 +222,7 @@ size_t attention_decode_part_floats(int B, int H, int hd) {
 // memory once another batch size had re-allocated it.
 void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, int H, int hd,
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                      const int* pos_dev, int pos_stride) {
+                      const int* pos_dev, int pos_stride, int group) {
   // fixed grid (graph replays move pos only); the kernel uses ceil(L / 128) of the S splits, so
   // each holds <= 256 keys for Tmax <= 4096 (checked by the binding)
   const int S = kDecSplitsMax;
@@ -205,9 +232,17 @@ void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, 
   // workgroup up to 256 keys beats splitting (B = 1 greedy: 3,167 -> 3,289 tok/s), with many the
   // extra parallelism pays (B = 8: 14.3k vs 13.9k)
   const int kps = B * H <= 32 ? 256 : 128;
-  attn_decode_kernel<<<B * H * S, 256, 0, stream>>>(qkv_new, cache, out, H, hd, H * hd, Tmax, pos, pos_dev,
-                                                    1.4426950408889634f / sqrtf((float)hd), S, CH, kps,
-                                                    part, counters, pos_stride);
+  if (group > 1) {
+    // B sequences of `group` rows: a workgroup per (row, head, split); the keys per split are the
+    // plain kernel's at B sequences, so a row splits as a plain decode at its position does
+    attn_decode_kernel<true><<<B * group * H * S, 256, 0, stream>>>(
+        qkv_new, cache, out, H, hd, H * hd, Tmax, pos, pos_dev, 1.4426950408889634f / sqrtf((float)hd), S, CH, kps,
+        part, counters, pos_stride, group);
+    return;
+  }
+  attn_decode_kernel<false><<<B * H * S, 256, 0, stream>>>(qkv_new, cache, out, H, hd, H * hd, Tmax, pos, pos_dev,
+                                                           1.4426950408889634f / sqrtf((float)hd), S, CH, kps,
+                                                           part, counters, pos_stride, group);
 }
 
 }  // namespace mg

@@ -43,6 +43,14 @@ at one batch-wide position, the row kernel, the merge, the in-place reorder of e
 cache by parent beam -- is the loop ``("beam", W)`` (``_GpuCache.beam``).  The token history is never
 permuted: the sequences are rebuilt from the per-step parent / token histories at the end.  The CPU
 path runs ``ops.reference.beam_step`` on ``_CpuCache``.
+
+Speculative greedy decoding (``generate_speculative``; the rule in common.h): K = draft_len + 1 rows
+per sequence and step -- the last committed token and an n-gram (prompt-lookup) draft -- at K
+consecutive positions of one KV cache, keeping what the model's own argmax confirms.  The state has
+B sequences and B * K step rows and lives beside the others (``_spec_cache``); the step -- draft
+kernel, embedding, ``_blocks`` with the grouped decode attention, the plain LM head, row argmax,
+accept kernel -- is the loop ``("spec", K)`` (``_GpuCache.spec``).  The CPU path runs
+``ops.reference.ngram_draft`` / ``spec_accept`` around one model forward per step.
 """
 from __future__ import annotations
 
@@ -670,6 +678,77 @@ class _GpuCache:
         self._beam_tail(st, W, logits)
         return st
 
+    # ----------------------------------------------------------------- speculative decoding
+    def spec_state(self, K):
+        """The device state of the speculative loop with K rows per sequence on this state's B
+        sequences (row b * K + r = row r of sequence b), allocated once (the captured step bakes the
+        pointers in): ``seq`` int64 [B, tmax + 1] (the committed tokens), ``pos`` int32 [B] (the
+        column of a sequence's newest token), ``ctl`` int32 [4] = {ngram, end, 0, 0}, the step's
+        rows ``tok`` int64 [B * K, 1] / ``pos_rows`` int32 [B * K] / ``has`` int32 [B] / ``g`` int32
+        [B * K], the statistics ``steps`` int32 [B] and ``hist`` int32 [B, K + 1], and the grouped
+        decode attention's workspace for B * K rows."""
+        states = self.__dict__.setdefault("_sstate", {})
+        if K not in states:
+            dev, B, cfg = self.caches[0].device, self.B, self.model.config
+            H = cfg.n_head
+            i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+            states[K] = {"seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev), "pos": i32(B),
+                         "ctl": i32(4), "tok": torch.zeros(B * K, 1, dtype=torch.long, device=dev),
+                         "pos_rows": i32(B * K), "has": i32(B), "g": i32(B * K), "steps": i32(B),
+                         "hist": i32(B, K + 1),
+                         "part": torch.empty(self.C.attention_decode_part_floats(B * K, H, cfg.n_embed // H),
+                                             device=dev, dtype=torch.float32),
+                         "cnt": i32(B * K * H)}
+        return states[K]
+
+    def spec(self, K):
+        """The speculative loop of this state (``_loops[("spec", K)]``; the rule in common.h): the
+        draft kernel, the embedding with one position per row, the blocks on the skinny GEMM with the
+        grouped decode attention (K rows share a sequence's cache), the plain LM head, the row argmax
+        and the accept kernel, which writes the emitted tokens to ``seq`` and advances ``pos``.  A
+        finished sequence (pos == end) keeps flowing through the step and the accept kernel leaves
+        it alone, so the launch shapes never change.  Build it BEFORE the prefill: the warm-up step
+        runs with end = 0 -- every sequence finished, no state moved -- but writes K/V rows."""
+        st = self.spec_state(K)
+        C, bf = self.C, self.bf
+        tr, cfg = self.model.transformer, self.model.config
+        D, H, V = cfg.n_embed, cfg.n_head, cfg.vocab_size
+        R = self.B * K
+        if not C.gemv_supported(R, 4 * D):
+            raise RuntimeError(f"speculative decoding: {R} rows of width {4 * D} do not fit the skinny GEMM")
+
+        def step():
+            C.spec_draft(st["seq"], st["pos"], st["ctl"], K, st["tok"], st["pos_rows"], st["has"])
+            x = C.embedding_fwd(st["tok"], bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, st["pos_rows"], None, None,
+                                1).view(R, D)
+            x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, 0, st["pos_rows"],
+                                                                  st["part"], st["cnt"], 1, K), True)
+            logits = self._head(x, True)
+            C.spec_argmax(logits, V, st["g"])
+            C.spec_accept(st["g"], st["tok"], st["has"], K, st["pos"], st["ctl"], st["seq"], st["steps"], st["hist"])
+            return logits[:, :V]
+
+        def warm():
+            st["ctl"].zero_()
+            st["pos"].zero_()
+            step()
+
+        return self._loop(("spec", K), lambda: _Loop(step, st, warm))
+
+    def spec_start(self, K, idx, first, n, ngram):
+        """Point the speculative state at the prefilled prompts ``idx`` [B, T] with the first new
+        token ``first`` [B] at column T: pos = T, end = T + n - 1, the statistics zeroed."""
+        st = self.spec_state(K)
+        T = idx.size(1)
+        st["seq"].zero_()
+        st["seq"][:, :T].copy_(idx)
+        st["seq"][:, T].copy_(first)
+        st["pos"].fill_(T)
+        st["ctl"].copy_(torch.tensor([int(ngram), T + n - 1, 0, 0], dtype=torch.int32))
+        st["steps"].zero_()
+        st["hist"].zero_()
+        return st
+
 
 _I64_MIN = -(1 << 63)
 
@@ -1114,6 +1193,132 @@ def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token):
             break
     hparent, htok = st["hparent"][:, :, T:T + steps].cpu(), st["htok"][:, :, T:T + steps].cpu()
     return hparent, htok, st["len"].view(B, W).long(), st["score"].view(B, W).clone()
+
+
+# --------------------------------------------------------------------------- speculative decoding
+_SPEC_ROWS_MAX = 8   # rows of one verify step over the whole batch (the skinny GEMM's, kernels.h kSpecRowsMax)
+_SPEC_NGRAM_MAX = 4  # kernels.h kSpecNgramMax
+
+
+@torch.no_grad()
+def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ngram: int = 3,
+                         return_stats: bool = False):
+    """Greedy decoding, several tokens per step (the rule in common.h, 'Speculative greedy
+    decoding'): every step guesses the next ``draft_len`` tokens of a sequence by prompt lookup --
+    the continuation of the most recent earlier occurrence of its last up to ``ngram`` tokens -- runs
+    the last committed token and the guesses as K = ``draft_len + 1`` rows at K consecutive
+    positions of the same KV cache, and keeps the longest prefix of guesses that the model's own
+    argmax confirms, plus the model's next token: 1 to K tokens per step.  The result is
+    ``generate(model, idx, max_new_tokens)``'s greedy output: tokens int64 [B, T + max_new_tokens]
+    (on the GPU bit for bit, every row of a step being computed from that row's inputs alone).
+
+    Greedy only: no sampling, no log-probabilities and no stop token on this entry.  ``idx``: int64
+    [B, T], rectangular.  ``1 <= draft_len <= 7`` with ``B * (draft_len + 1) <= 8`` (the rows of a step
+    go through the skinny GEMM together), ``1 <= ngram <= 4``, and ``T + max_new_tokens`` must fit
+    ``block_size`` (no sliding window here); ValueError otherwise.
+
+    ``return_stats``: also a dict with ``steps`` (int64 [B]: the verify steps in which the sequence
+    was live) and ``emitted_hist`` (int64 [B, K + 1]: entry e counts the steps that emitted e
+    tokens).  The first token comes from the prefill, so a row's histogram adds up to
+    ``max_new_tokens - 1`` tokens.
+
+    On the GPU the step -- draft kernel, embedding, blocks with the grouped decode attention, LM head,
+    row argmax, accept kernel -- is one captured graph per (B, K) replayed back to back
+    (``_GpuCache.spec``); the host reads the positions back once per round of replays.  On the CPU
+    the same rule runs through ``ops.reference.ngram_draft`` / ``spec_accept`` and one model forward
+    over the extended sequence per step."""
+    who = "generate_speculative"
+    if not (torch.is_tensor(idx) and idx.dim() == 2 and idx.dtype == torch.long and idx.size(0) >= 1
+            and idx.size(1) >= 1):
+        raise ValueError(f"{who}: idx must be an int64 [B, T] tensor with B, T >= 1")
+    V, bs = model.config.vocab_size, model.block_size
+    B, T = idx.shape
+    n = int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"{who}: max_new_tokens must be >= 0, got {max_new_tokens}")
+    if int(draft_len) != draft_len or not 1 <= int(draft_len) <= _SPEC_ROWS_MAX - 1:
+        raise ValueError(f"{who}: draft_len must be in 1..{_SPEC_ROWS_MAX - 1}, got {draft_len}")
+    K = int(draft_len) + 1
+    if B * K > _SPEC_ROWS_MAX:
+        raise ValueError(f"{who}: draft_len {draft_len} at batch {B} needs {B * K} rows per step; a step takes "
+                         f"at most {_SPEC_ROWS_MAX}")
+    if int(ngram) != ngram or not 1 <= int(ngram) <= _SPEC_NGRAM_MAX:
+        raise ValueError(f"{who}: ngram must be in 1..{_SPEC_NGRAM_MAX}, got {ngram}")
+    if T + n > bs:
+        raise ValueError(f"{who}: prompt ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
+                         f"point has no sliding window")
+    _check_token_ids(who, V, idx)
+    before_use(*model.parameters())
+    if n == 0:
+        out = idx.clone()
+        steps = torch.zeros(B, dtype=torch.long, device=idx.device)
+        hist = torch.zeros(B, K + 1, dtype=torch.long, device=idx.device)
+    elif idx.is_cuda:
+        out, steps, hist = _generate_speculative_gpu(model, idx.contiguous(), n, K, int(ngram))
+    else:
+        out, steps, hist = _generate_speculative_cpu(model, idx, n, K, int(ngram))
+    return (out, {"steps": steps, "emitted_hist": hist}) if return_stats else out
+
+
+def _generate_speculative_cpu(model, idx, n, K, ngram):
+    """The CPU half of ``generate_speculative``, the executable definition of the semantics: per
+    sequence and step, ``ops.reference.ngram_draft``, one model forward over the committed tokens
+    extended by the draft (only the min(K, end - p) rows that can still be emitted), the argmax of
+    the rows' logits and ``ops.reference.spec_accept``.  Eval mode, as for ``score``."""
+    B, T = idx.shape
+    out = torch.zeros(B, T + n, dtype=torch.long, device=idx.device)
+    out[:, :T] = idx
+    steps = torch.zeros(B, dtype=torch.long, device=idx.device)
+    hist = torch.zeros(B, K + 1, dtype=torch.long, device=idx.device)
+    end = T + n - 1
+    was = model.training
+    model.eval()
+    try:
+        for b in range(B):
+            logits, _ = model(idx[b:b + 1])
+            out[b, T] = logits[0, -1].argmax()
+            p = T
+            while p < end:
+                rows, has = R.ngram_draft(out[b], p, K, ngram)
+                rows = rows[:min(K, end - p)]
+                x = torch.cat([out[b, :p], torch.tensor(rows, dtype=torch.long, device=idx.device)])
+                logits, _ = model(x.view(1, -1))
+                g = logits[0, p:].argmax(dim=-1)
+                _, cnt = R.spec_accept(rows, g.tolist(), has, p, end)
+                out[b, p + 1:p + 1 + cnt] = g[:cnt]
+                p += cnt
+                steps[b] += 1
+                hist[b, cnt] += 1
+    finally:
+        model.train(was)
+    return out, steps, hist
+
+
+def _spec_cache(model, idx, tmax):
+    """The model's speculative decode state of B sequences, kept beside (not in place of) the plain
+    and beam states: speculative calls leave their loops and graphs alone."""
+    c = model.__dict__.get("_mg_spec_cache")
+    if c is None or c.B != idx.size(0) or c.tmax != tmax or c.caches[0].device != idx.device:
+        c = _GpuCache(model, idx, tmax, rows=idx.size(0))
+        model.__dict__["_mg_spec_cache"] = c
+    return c
+
+
+def _generate_speculative_gpu(model, idx, n, K, ngram):
+    """The GPU half of ``generate_speculative``: build (once per (B, K)) the speculative loop, prefill
+    the prompts and take the first token from the prefill logits as ``generate`` does, then replay
+    the captured step in rounds of ceil((end - min p) / K) -- the fewest steps that could finish --
+    reading the positions back after each round, until every sequence has reached ``end``."""
+    B, T = idx.shape
+    cache = _spec_cache(model, idx, model.block_size)
+    loop = cache.spec(K)  # before the prefill: building it runs a warm-up step
+    cache.prefill(idx)
+    st = cache.spec_start(K, idx, cache.logits.argmax(-1), n, ngram)
+    end, low = T + n - 1, T
+    while low < end:
+        loop.run(-(-(end - low) // K))
+        low = int(st["pos"].min())
+    return st["seq"][:, :T + n].clone(), st["steps"].long(), st["hist"].long()
 
 
 # --------------------------------------------------------------------------- scoring

@@ -260,6 +260,18 @@ class GPT(nn.Module):
                              length_penalty=length_penalty)
 
     @torch.no_grad()
+    def generate_speculative(self, idx, max_new_tokens: int, draft_len: int = 3, ngram: int = 3,
+                             return_stats: bool = False):
+        """Greedy decoding of ``idx`` [B, T] with n-gram drafts verified ``draft_len + 1`` rows per step:
+        the tokens of ``generate`` (greedy), several per step (``generation.generate_speculative``).
+        ``B * (draft_len + 1) <= 8``; no sliding window: ``T + max_new_tokens`` must fit
+        ``block_size``.  ``return_stats``: returns ``(tokens, {"steps", "emitted_hist"})``."""
+        from .generation import generate_speculative
+
+        return generate_speculative(self, idx, max_new_tokens, draft_len=draft_len, ngram=ngram,
+                                    return_stats=return_stats)
+
+    @torch.no_grad()
     def score(self, idx, lengths=None):
         """Per-token log-probabilities of given sequences, float32 [B, T]: ``out[b, j]`` is the
         log-probability of ``idx[b, j]`` given ``idx[b, :j]`` for 1 <= j < lengths[b], 0.0 elsewhere

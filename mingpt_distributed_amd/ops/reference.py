@@ -201,6 +201,48 @@ def beam_step(scores: torch.Tensor, finished: torch.Tensor, logits: torch.Tensor
     return parents, tokens, new, done
 
 
+def ngram_draft(s, p: int, K: int, ngram: int):
+    """The draft of the speculative rule of ``csrc/include/common.h`` ('Speculative greedy
+    decoding'; the kernel is ``csrc/kernels/spec.hip``) for one sequence: ``s`` holds the committed
+    tokens ``s[0 .. p]`` (a 1-D tensor or a sequence of ints; entries past ``p`` are ignored).  For
+    every e in 0 .. p - 1, ml(e) is the largest m <= ngram with e - j >= 0 and s[e - j] == s[p - j]
+    for every j < m; the e with the largest (ml, e) wins -- the longest suffix match, the most recent
+    on ties -- and if its ml is 0 there is no draft.  Otherwise x = s[0 .. p] and for r = 1 .. K - 1:
+    d_r = x[e + r], appended to x (a period below K drafts through itself).  Returns ``(rows,
+    has_draft)``: the K tokens of the step's rows (row 0: s[p]; without a draft every row) at
+    positions p .. p + K - 1, and the flag."""
+    x = [int(t) for t in (s.tolist() if torch.is_tensor(s) else s)][:p + 1]
+    if len(x) != p + 1 or p < 0:
+        raise ValueError(f"ngram_draft: s must hold the tokens 0..{p}")
+    best = (0, -1)
+    for e in range(p):
+        ml = 0
+        while ml < ngram and e - ml >= 0 and x[e - ml] == x[p - ml]:
+            ml += 1
+        best = max(best, (ml, e))
+    if best[0] == 0:
+        return [x[p]] * K, False
+    e = best[1]
+    for r in range(1, K):
+        x.append(x[e + r])
+    return x[p:], True
+
+
+def spec_accept(rows, g, has_draft: bool, p: int, end: int):
+    """The accept half of the same rule: ``rows`` the step's input tokens (``ngram_draft``), ``g`` the
+    argmax of each row's logits (first index on ties), as many as the step ran.  a is the largest
+    value with rows[r] == g[r - 1] for all 1 <= r <= a (0 without a draft); the step emits
+    min(a + 1, end - p) tokens g[0], g[1], ... at columns p + 1 ...  Returns ``(a, count)``; count is
+    0 for a sequence with p == end, which is left alone."""
+    if p >= end:
+        return 0, 0
+    a = 0
+    if has_draft:
+        while a + 1 < min(len(rows), len(g)) and int(rows[a + 1]) == int(g[a]):
+            a += 1
+    return a, min(a + 1, end - p)
+
+
 def cross_entropy(logits, targets, ignore_index: int = -1):
     return F.cross_entropy(logits.reshape(-1, logits.size(-1)).float(), targets.reshape(-1),
                            ignore_index=ignore_index)

@@ -22,6 +22,11 @@ decoded together in one ragged batch (``GPT.generate_batch``): every prompt keep
 prints the N beams best first with their summed log-probability; ``--length-penalty a`` re-ranks them
 by ``score / n_generated ** a``.
 
+``--speculative DRAFT_LEN`` (1..7) decodes the one prompt greedily with n-gram drafts verified
+``DRAFT_LEN + 1`` rows per step (``GPT.generate_speculative``; ``--ngram N``, 1..4, is the longest
+suffix the draft looks up) -- the text of ``--greedy``, in fewer steps -- and prints the steps taken
+and the mean tokens per step.
+
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
 """
@@ -59,6 +64,10 @@ def main(argv=None):
                     help="beam search with this many beams (1..8) on one prompt instead of sampling")
     ap.add_argument("--length-penalty", type=float, default=0.0,
                     help="with --beams: re-rank the final beams by score / n_generated ** penalty")
+    ap.add_argument("--speculative", type=int, default=0, metavar="DRAFT_LEN",
+                    help="greedy decoding of one prompt with n-gram drafts of this many tokens (1..7) per step")
+    ap.add_argument("--ngram", type=int, default=3,
+                    help="with --speculative: the longest suffix (1..4) the draft looks up in the text so far")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -84,6 +93,8 @@ def main(argv=None):
             texts += [ln.rstrip("\n") for ln in f if ln.strip()]
     if a.beams and len(texts) > 1:
         ap.error("--beams takes one prompt")
+    if a.speculative and (len(texts) > 1 or a.beams):
+        ap.error("--speculative takes one prompt and does not go with --beams")
     if len(texts) > 1:
         return generate_many(model, tok, texts, a, dev)
     prompt = texts[0] if texts else ""
@@ -93,6 +104,8 @@ def main(argv=None):
         x = torch.tensor([[50256]], dtype=torch.long, device=dev)
     if a.beams:
         return generate_beams(model, tok, x, a)
+    if a.speculative:
+        return generate_speculative(model, tok, x, a)
     x = x.expand(a.num_samples, -1).contiguous()
     kw = {"return_logprobs": True} if a.logprobs else {}
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
@@ -131,6 +144,20 @@ def generate_beams(model, tok, x, a):
         print(out)
         print(f"[beam {w}: logprob {float(scores[0, w]):.4f} over {int(n[0, w]) - x.size(1)} tokens]")
     return outs
+
+
+def generate_speculative(model, tok, x, a):
+    """``--speculative``: greedy decoding of the one prompt x [1, T] with n-gram drafts
+    (``GPT.generate_speculative``), then the verify steps taken and the mean tokens per step."""
+    y, stats = model.generate_speculative(x, a.steps, draft_len=a.speculative, ngram=a.ngram, return_stats=True)
+    out = tok.decode(y[0].cpu()) if tok is not None else y[0].tolist()
+    print("-" * 80)
+    print(out)
+    steps = int(stats["steps"][0])
+    hist = stats["emitted_hist"][0].tolist()
+    print(f"[speculative: {max(a.steps - 1, 0)} tokens in {steps} verify steps of {a.speculative + 1} rows, "
+          f"{(a.steps - 1) / steps if steps else 0.0:.2f} tokens per step; steps by tokens emitted: {hist}]")
+    return [out]
 
 
 def generate_many(model, tok, texts, a, dev):
