@@ -117,6 +117,46 @@ def logprobs(model, a):
         print(json.dumps(res), flush=True)
 
 
+def process(model, a):
+    """Tokens/s of ``generate`` with the logits processors off against on per batch size B, greedy
+    and seeded sampling (--top-k / --top-p / --seed, default seed 1): B prompts of --prompt tokens,
+    --new tokens.  'On' is repetition_penalty 1.3, presence_penalty 0.2, frequency_penalty 0.1 and
+    no_repeat_ngram_size 3.  The four cases are warmed up (each has its own captured loop), then
+    timed --reps times in turn; the median is reported with the spread.  Greedy with the processors
+    on also pays for leaving the LM head's fused argmax: ``greedy_logprobs`` -- the same
+    construction without the process kernel, plus the lse kernel -- is timed beside it."""
+    import statistics
+
+    on = dict(repetition_penalty=1.3, presence_penalty=0.2, frequency_penalty=0.1, no_repeat_ngram_size=3)
+    samp = dict(do_sample=True, top_k=a.top_k or None, top_p=a.top_p, seed=1 if a.seed is None else a.seed)
+    for B in map(int, a.batches.split(",")):
+        idx = torch.randint(0, 50257, (B, a.prompt), generator=torch.Generator().manual_seed(B)).cuda()
+        cases = {"greedy_off": lambda: model.generate(idx, a.new),
+                 "greedy_on": lambda: model.generate(idx, a.new, **on),
+                 "greedy_logprobs": lambda: model.generate(idx, a.new, return_logprobs=True)[0],
+                 "sample_off": lambda: model.generate(idx, a.new, **samp),
+                 "sample_on": lambda: model.generate(idx, a.new, **samp, **on)}
+        with torch.no_grad():
+            for fn in cases.values():  # warm-up at the timed shapes (kernels, states, graph capture)
+                fn()
+            times = {k: [] for k in cases}
+            for _ in range(a.reps):
+                for k, fn in cases.items():
+                    times[k].append(timed(fn)[1])
+        res = {"metric": "decode tokens/s, logits processors off / on", "model": "gpt2 (random init)", "batch": B,
+               "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "top_p": a.top_p, "seed": samp["seed"],
+               "processors": on, "reps": a.reps}
+        for k, ts in times.items():
+            res[k + "_tok_s"] = round(B * a.new / statistics.median(ts), 1)
+            res[k + "_tok_s_range"] = [round(B * a.new / max(ts), 1), round(B * a.new / min(ts), 1)]
+            res[k + "_us_per_step"] = round(statistics.median(ts) / a.new * 1e6, 1)
+        med = lambda k: statistics.median(times[k])
+        res["greedy_on_over_off_time"] = round(med("greedy_on") / med("greedy_off"), 4)
+        res["greedy_logprobs_over_off_time"] = round(med("greedy_logprobs") / med("greedy_off"), 4)
+        res["sample_on_over_off_time"] = round(med("sample_on") / med("sample_off"), 4)
+        print(json.dumps(res), flush=True)
+
+
 def beams(model, a):
     """Beam search per beam count W of --beams: ``generate_beam`` on one prompt of --prompt tokens,
     next to the same row count through ``generate_batch(return_logprobs=True)`` greedy (W copies of
@@ -177,6 +217,9 @@ def main():
     ap.add_argument("--logprobs", action="store_true",
                     help="time the same call without and with return_logprobs=True (this framework only): "
                          "generate, greedy or with --sample [--seed]; with --ragged generate_batch")
+    ap.add_argument("--process", action="store_true",
+                    help="time generate with the logits processors off and on, greedy and seeded (this "
+                         "framework only)")
     a = ap.parse_args()
     from mingpt_distributed_amd.models import GPT, GPTConfig
 
@@ -185,6 +228,8 @@ def main():
     ours = ours.cuda().to(torch.bfloat16).eval()
     if a.beams:
         return beams(ours, a)
+    if a.process:
+        return process(ours, a)
     if a.logprobs:
         return logprobs(ours, a)
     if a.ragged:

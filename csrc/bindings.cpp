@@ -794,6 +794,39 @@ py::object logits_lse(const at::Tensor& logits, int64_t V, const c10::optional<a
   return py::cast(l);
 }
 
+// The logits processors (process.hip, the rule in common.h) on logits [R, ld] bf16, in place: the
+// first V columns of every row are edited from the row's history hist[r, 0 .. pos_r] (hist int64 [R,
+// n] with unit column stride, n <= kProcHistMax; a view of a wider buffer is fine) under params (int32
+// [kProcParamWords] on the device: rp, inv, pp, fp as fp32 bits, g, 0, 0, 0).  pos: int32 [1] with
+// pos_stride 0 or [R] with pos_stride 1; done (optional): int32 [R], a finished row is left alone.
+void logits_process(const at::Tensor& logits, int64_t V, const at::Tensor& hist, const at::Tensor& pos,
+                    int64_t pos_stride, const c10::optional<at::Tensor>& done, const at::Tensor& params) {
+  const char* op = "logits_process";
+  const LogitsRows lr = logits_rows(op, logits, V);
+  const int64_t R = lr.rows;
+  TORCH_CHECK(R <= 0x7fffffff && V <= 0x7fffffff, op, ": too many rows or columns");
+  CHECK_I64(hist); CHECK_DEV(hist);
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) == R && hist.size(1) >= 1 && hist.stride(1) == 1 &&
+              (R == 1 || hist.stride(0) >= hist.size(1)) && hist.device() == lr.dev,
+              op, ": hist int64 [R, n] with unit column stride on the logits' device");
+  TORCH_CHECK(hist.size(1) <= mg::kProcHistMax, op, ": at most ", mg::kProcHistMax, " history columns, got ",
+              hist.size(1));
+  TORCH_CHECK(pos_stride == 0 || pos_stride == 1, op, ": pos_stride 0 or 1");
+  dev_i32(op, "pos", pos, pos_stride ? R : 1, lr.dev);
+  const int* dp = nullptr;
+  if (done.has_value() && done->defined()) {
+    dev_i32(op, "done", *done, R, lr.dev);
+    dp = done->data_ptr<int>();
+  }
+  CHECK_DEV(params);
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() && params.numel() == mg::kProcParamWords &&
+              params.device() == lr.dev, op, ": params int32 [8] on the logits' device");
+  DevGuard g(lr.dev);
+  mg::logits_process(bp(logits), lr.ld, (int)R, (int)V, hist.data_ptr<int64_t>(), R > 1 ? hist.stride(0) : 0,
+                     (int)hist.size(1), pos.data_ptr<int>(), (int)pos_stride, dp,
+                     reinterpret_cast<const uint32_t*>(params.data_ptr<int>()), cur_stream());
+}
+
 // ------------------------------------------------------------------------------- beam search
 // beam.hip (kernels.h).  Every per-beam buffer has R = B * W elements, row b * W + w = beam w of
 // prompt b; all of them live on the logits' / the cache's device and are updated in place.
@@ -1104,6 +1137,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lp") = py::none());
   m.def("logits_lse", &logits_lse, py::arg("logits"), py::arg("V"), py::arg("targets") = py::none(),
         py::arg("lse") = py::none(), py::arg("lp") = py::none());
+  m.def("logits_process", &logits_process, py::arg("logits"), py::arg("V"), py::arg("hist"), py::arg("pos"),
+        py::arg("pos_stride"), py::arg("done"), py::arg("params"));
+  m.attr("PROC_HIST_MAX") = (int64_t)mg::kProcHistMax;
   m.def("beam_rows", &beam_rows, py::arg("logits"), py::arg("V"), py::arg("W"), py::arg("score"), py::arg("fin"),
         py::arg("ctl"), py::arg("cand_tok"), py::arg("cand_c"), py::arg("lse"));
   m.def("beam_merge", &beam_merge, py::arg("W"), py::arg("V"), py::arg("cand_tok"), py::arg("cand_c"),

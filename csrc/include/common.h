@@ -323,6 +323,44 @@ MG_DEVICE float token_logprob(uint32_t bits, float m, float lnz) { return (bf2f(
 // kernel of the step computes a row from that row's inputs alone, so g_r is what plain greedy
 // decoding picks at position p + r: the emitted tokens are generate()'s, bit for bit.
 
+// ---------------------------------------------------------------- Logits processors
+// Repetition, presence and frequency penalties and the no-repeat n-gram ban: an edit of one row of
+// stored logits l_0 .. l_{V-1} (bf16 on the device, the tensor's own dtype on host paths) from a
+// history h[0 .. n-1] of token ids, n >= 1, BEFORE anything else looks at the row.  Temperature,
+// top-k, top-p and the Gumbel pass see the edited row; greedy is its argmax (first index on ties);
+// a log-probability reported with a processor on is the rule above applied to the edited row.
+// History: generate() -- for the token at column T of the returned sequence, h = idx[b, max(0, T -
+// block_size) : T], exactly the context the model saw (n <= block_size); generate_batch() -- the row's
+// own unpadded sequence s[0 .. pos].  An id outside [0, V) counts for nothing: it has no c, is never
+// banned and equals nothing in an n-gram comparison, not even itself.
+// Parameters (a device block of kProcParamWords int32: rp, inv, pp, fp as fp32 bits, g, 0, 0, 0):
+//   rp = float32(repetition_penalty) (> 0; 1: off)       inv = float32(1.0 / repetition_penalty)
+//   pp = float32(presence_penalty), fp = float32(frequency_penalty) (0: off)
+//   g  = no_repeat_ngram_size (0 .. 8; 0: off)
+// Penalties.  c_i = the number of j with h[j] == i.  Every i with c_i >= 1 whose logit is not -inf is
+// rewritten by one fixed sequence of single correctly rounded fp32 operations (proc_penalty: no step
+// may fuse with another, whatever -ffp-contract says):
+//   x = float(l_i)    a = x > 0 ? x (*) inv : x (*) rp    q = fp (*) float(c_i)    q = q (+) pp
+//   y = a (-) q       l_i' = y rounded to the row's dtype (bf16: round-to-nearest-even, f2bf)
+// A -inf logit stays -inf; entries with c_i == 0 keep their bits; with every parameter off the
+// sequence is the identity on every non-NaN value.
+// No-repeat n-gram, after the penalties, if g >= 1: for every e in g-2 .. n-2 with h[e-j] == h[n-1-j]
+// for all j < g-1, the logit of h[e+1] becomes -inf.  g = 1 bans every history token; n < g bans
+// nothing.
+// The edited row must keep a finite maximum; otherwise it is outside the rule (any token, no fault).
+// The result is a function of (row, history, parameters) alone: one writer per element and phase,
+// nothing accumulated in floating point, nothing kept between launches -- a replay, a warm-up or a
+// repeated launch on fresh logits gives the same bits.
+MG_DEVICE bf16_t proc_penalty(uint32_t bits, int c, float rp, float inv, float pp, float fp) {
+  const float x = bf2f(bits);
+  float a = x > 0.f ? __fmul_rn(x, inv) : __fmul_rn(x, rp);
+  asm volatile("" : "+v"(a));  // a product the compiler cannot see into: nothing to contract with
+  float q = __fmul_rn(fp, (float)c);
+  asm volatile("" : "+v"(q));
+  q = __fadd_rn(q, pp);
+  return f2bf(__fsub_rn(a, q));
+}
+
 // ---------------------------------------------------------------- GELU (tanh approximation)
 constexpr float kGeluK0 = 0.7978845608028654f;  // sqrt(2/pi)
 constexpr float kGeluK1 = 0.044715f;

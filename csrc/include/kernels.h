@@ -115,6 +115,21 @@ void pick_ragged(const bf16_t* logits, long ld, int B, int V, uint32_t* params, 
 void logits_lse(const bf16_t* logits, long ld, int M, int V, const int64_t* targets, float* lse, float* lp,
                 hipStream_t stream);
 
+// process.hip -- the logits processors (the rule in common.h, 'Logits processors'): repetition /
+// presence / frequency penalties and the no-repeat n-gram ban, applied in place to the first V
+// columns of every row of logits [R, ld] (layout as for sample_logits; columns >= V are never read or
+// written).  Row r's history is hist[r * hist_ld + 0 .. min(pos_r, hist_n - 1)] (int64; hist_n <=
+// kProcHistMax), pos_r = pos[0] (pos_stride 0) or pos[r] (pos_stride 1), read on the device; a row
+// with pos_r < 0 or with done[r] set (done optional, int32 [R]) is left alone.  params (device,
+// kProcParamWords x int32): {rp, inv, pp, fp as fp32 bits, g, 0, 0, 0}.  Everything comes from device
+// memory and nothing but the logits is written, so a captured launch serves every setting and a
+// replay, a warm-up or a repeated launch cannot corrupt any state.
+constexpr int kProcParamWords = 8;
+constexpr int kProcHistMax = 4096;
+constexpr int kProcNgramMax = 8;
+void logits_process(bf16_t* logits, long ld, int R, int V, const int64_t* hist, long hist_ld, int hist_n,
+                    const int* pos, int pos_stride, const int* done, const uint32_t* params, hipStream_t stream);
+
 // beam.hip -- the tail of a beam decode step (the rule in common.h, 'Beam search'): B prompts, W <= 8
 // beams each, R = B * W rows, row b * W + w = beam w of prompt b.  ctl (device, 4 x int32): {history
 // column, stop token (negative: none), pad token, 0}.

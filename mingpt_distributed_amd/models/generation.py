@@ -36,6 +36,18 @@ epilogue for the last token; its step is the ragged greedy step on equal positio
 ranks the same stored bf16 logits with the first index on ties.  Host loops use
 ``ops.reference.token_logprob``.
 
+Logits processors (``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
+``no_repeat_ngram_size`` on ``generate`` / ``generate_batch``; the rule in common.h): an edit of the
+stored logits from the token history -- the context the model saw -- before anything picks from
+them.  On the device loops the process kernel (``logits_process``) runs right after the LM head inside
+the captured step, reads the history from the loop's own ``seq`` buffer (which therefore holds the
+window's context before a run) and its settings from a device parameter block (``_proc_params``), in
+loops of their own (``"sample_proc"``, ``"greedy_proc"``, ``("ragged_proc", greedy)`` and their
+``_lp`` forms): with every argument off nothing changes and no loop is added.  Greedy with a processor
+on is ``_greedy_lp``'s construction -- the LM head's fused argmax cannot see edited logits.  A window's
+first token is picked after one eager launch over the prefill logits (``process_prefill``).  Host
+loops use ``ops.reference.process_logits``.
+
 Beam search (``generate_beam``; the rule in common.h): W beams per prompt, scored by the running fp32
 sum of those log-probabilities.  The decode state has B * W rows and lives beside the plain one
 (``_beam_cache``), the prompt is prefilled once per prompt and broadcast, and the step -- ``_decode``
@@ -385,19 +397,79 @@ class _GpuCache:
         launch, and a state that owns an ``lp`` buffer from an earlier call does not pass it."""
         return (self.C.logits_lse(logits, V), st["lp"]) if logprobs else (None, None)
 
-    def _ragged_step(self, st, greedy, logprobs):
+    def _proc_params(self, words):
+        """The device parameter block of the process kernel (``_proc_words``), owned by this state:
+        the captured steps that apply the processors bake the pointer in.  An unchanged block is not
+        uploaded again, as for ``_ragged_params``."""
+        p = self.__dict__.get("_pparams")
+        if p is None:
+            p = self._pparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
+            self._pwords = None
+        if self._pwords != list(words):
+            p.copy_(torch.tensor(words, dtype=torch.int32))
+            self._pwords = list(words)
+        return p
+
+    def _process(self, logits, st, pos_stride, done=None):
+        """The process kernel on a step's ``logits`` in place: row b's history is columns 0 ..
+        pos[b] of the state's own ``seq``, which the step's pick kernel extends."""
+        self.C.logits_process(logits, self.model.config.vocab_size, st["seq"][:, :self.tmax], st["pos"], pos_stride,
+                              done, self._pparams)
+
+    def process_prefill(self, ctx, proc):
+        """Edit the prefill logits in place with the processors ``proc`` (``_proc_words``) over the
+        context ``ctx`` [B, L] they were computed from: one eager launch before a window's first pick."""
+        pos = torch.full((1,), ctx.size(1) - 1, dtype=torch.int32, device=ctx.device)
+        self.C.logits_process(self.logits, self.model.config.vocab_size, ctx, pos, 0, None, self._proc_params(proc))
+
+    def _ragged_step(self, st, greedy, logprobs, proc=False):
         """The decode step over per-row state ``st`` (``pos``, ``done``, ``tok``, ``seq``, ``params``,
         with ``logprobs`` also ``lp``): ``_decode`` with one position per row, then the ragged pick
-        kernel, greedy or sampled."""
+        kernel, greedy or sampled.  ``proc``: the process kernel on the logits first (and before the
+        lse kernel: the log-probability is the processed row's)."""
         V = self.model.config.vocab_size
 
         def step():
             logits = self._decode(st["tok"], st["pos"], 1, pos_stride=1)
+            if proc:
+                self._process(logits, st, 1, st["done"])
             self.C.pick_ragged(logits, V, st["params"], st["pos"], st["done"], st["tok"], st["seq"], greedy,
                                *self._lp_args(logits, V, st, logprobs))
             return logits[:, :V]
 
         return step
+
+    def greedy_proc(self, tok, pos, n, proc, ctx, logprobs=False):
+        """``greedy`` with the logits processors ``proc`` (``_proc_words``) on: the n new tokens [B,
+        n], with ``logprobs`` (tokens, lp).  The LM head's fused argmax cannot see edited logits, so
+        this is ``_greedy_lp``'s construction -- the ragged greedy step on equal positions over a
+        state of its own, no stop token -- with the process kernel in front of the pick: loops
+        ``"greedy_proc"`` / ``"greedy_proc_lp"``.  ``ctx`` [B, pos] is the window's context: the
+        state's ``seq`` holds it in columns 0 .. pos - 1 and ``tok`` at column pos before the run,
+        since the kernel reads the history from there."""
+        assert pos + n <= self.tmax
+        B = tok.shape[0]
+        self._proc_params(proc)
+
+        def make():
+            dev = tok.device
+            st = {"tok": tok.clone(), "pos": torch.full((B,), pos, dtype=torch.int32, device=dev),
+                  "done": torch.zeros(B, dtype=torch.int32, device=dev),
+                  "seq": torch.zeros(B, self.tmax + 2, dtype=torch.long, device=dev),
+                  "params": torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=dev)}
+            if logprobs:
+                st["lp"] = torch.zeros(B, self.tmax + 2, dtype=torch.float32, device=dev)
+            return _Loop(self._ragged_step(st, True, logprobs, proc=True), st)
+
+        lp = self._loop("greedy_proc_lp" if logprobs else "greedy_proc", make)
+        st = lp.state
+        st["tok"].copy_(tok)  # after the loop is built: its warm-up step moved the state
+        st["pos"].fill_(pos)
+        st["seq"][:, :pos].copy_(ctx)
+        st["seq"][:, pos:pos + 1].copy_(tok)
+        lp.run(n)
+        toks = st["seq"][:, pos + 1:pos + 1 + n]
+        return (toks, st["lp"][:, pos + 1:pos + 1 + n]) if logprobs else toks
 
     def _greedy_lp(self, tok, pos, n):
         """``greedy`` with log-probabilities: (tokens [B, n], lp [B, n]).  A loop of its own
@@ -493,7 +565,7 @@ class _GpuCache:
         """The token [B] drawn from the prefill logits (the first token of a context window)."""
         return self.C.sample_logits(self.logits, self.model.config.vocab_size, self._sample_params(words))
 
-    def sample(self, tok, pos, n, words, logprobs=False):
+    def sample(self, tok, pos, n, words, logprobs=False, proc=None, ctx=None):
         """n sampled decode steps starting with token ``tok`` [B, 1] at position ``pos``: each step
         is the plain LM head followed by the sample kernel, which writes the next token into the
         buffer the next step's embedding reads and advances the device position and draw counter.
@@ -501,10 +573,16 @@ class _GpuCache:
         captured step serves every call.  Returns the n new tokens [B, n] (positions pos + 1 ..
         pos + n).  ``logprobs``: a loop of its own (``"sample_lp"``) with the lse kernel between the
         LM head and the sampler, which writes each token's log-probability beside it; returns
-        (tokens, lp [B, n])."""
+        (tokens, lp [B, n]).  ``proc`` (``_proc_words``; with ``ctx`` [B, pos], the window's context):
+        loops of their own again (``"sample_proc"`` / ``"sample_proc_lp"``) with the process kernel
+        right after the LM head; it reads the history from the loop's ``seq``, which therefore holds
+        ``ctx`` in columns 0 .. pos - 1 and ``tok`` at column pos before the run."""
         assert pos + n <= self.tmax
         B = tok.shape[0]
         V = self.model.config.vocab_size
+        on = proc is not None
+        if on:
+            self._proc_params(proc)
 
         def make():
             dev = tok.device
@@ -516,14 +594,19 @@ class _GpuCache:
 
             def step():
                 logits = self._decode(st["tok"], st["pos"], st["hpos"])
+                if on:
+                    self._process(logits, st, 0)
                 self.C.sample_logits(logits, V, params, st["pos"], st["tok"], st["seq"],
                                      *self._lp_args(logits, V, st, logprobs))
                 return logits[:, :V]
 
             return _Loop(step, st)
 
-        lp = self._loop("sample_lp" if logprobs else "sample", make)
+        lp = self._loop(("sample_proc" if on else "sample") + ("_lp" if logprobs else ""), make)
         self._seed(lp.state, tok, pos)
+        if on:
+            lp.state["seq"][:, :pos].copy_(ctx)
+            lp.state["seq"][:, pos:pos + 1].copy_(tok)
         self._sample_params(words)
         lp.run(n)
         toks = lp.state["seq"][:, pos + 1:pos + 1 + n]
@@ -555,12 +638,14 @@ class _GpuCache:
             st["params"].copy_(torch.tensor(words, dtype=torch.int32))
             self._rwords = list(words)
 
-    def ragged_start(self, idx, lengths, words, greedy, logprobs=False):
+    def ragged_start(self, idx, lengths, words, greedy, logprobs=False, proc=None):
         """Point the ragged state at a prefilled right-padded batch ``idx`` [B, Tp] with ``lengths``
         [B] (``self.logits`` = row b's logits at column lengths[b] - 1) and pick every row's first
         token with the loop's own pick kernel: pos = lengths - 1 and done = 0 going in.
         ``logprobs``: the state's ``lp`` buffer (float32, the shape of ``seq``; allocated on first
-        use) is zeroed with ``seq`` and gets the first tokens' log-probabilities."""
+        use) is zeroed with ``seq`` and gets the first tokens' log-probabilities.  ``proc``
+        (``_proc_words``): the prefill logits are edited by the process kernel over each row's own
+        prompt first."""
         st = self.ragged_state()
         if logprobs:
             if "lp" not in st:
@@ -572,11 +657,14 @@ class _GpuCache:
         st["done"].zero_()
         self._ragged_params(st, words)
         logits = self.logits  # [B, V] view of the padded [B, ld] buffer the LM head wrote
+        if proc is not None:
+            self._proc_params(proc)
+            self._process(logits, st, 1, st["done"])
         self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
                            greedy, *self._lp_args(logits, logits.size(1), st, logprobs))
         return st
 
-    def ragged(self, n, words, greedy, logprobs=False):
+    def ragged(self, n, words, greedy, logprobs=False, proc=None):
         """n decode steps of a ragged batch on the current device state (``ragged_state``): embed
         ``tok[b]`` at ``pos[b]``, the blocks with per-row decode attention, the plain LM head, then
         the pick kernel -- greedy argmax or the seeded draw with counter ``pos[b] + 1`` -- which
@@ -587,10 +675,16 @@ class _GpuCache:
         call of n steps.  ``words``: the parameter block (``_ragged_words``).  Returns the state;
         the last step's logits are the loop's ``logits``.  ``logprobs`` (after a ``ragged_start``
         with it): loops of their own (``("ragged_lp", greedy)``) with the lse kernel before the pick
-        kernel, which writes ``lp[b, pos[b] + 1]`` with the token."""
+        kernel, which writes ``lp[b, pos[b] + 1]`` with the token.  ``proc`` (``_proc_words``, after
+        a ``ragged_start`` with it): loops of their own once more (``("ragged_proc", greedy)`` /
+        ``("ragged_proc_lp", greedy)``) with the process kernel right after the LM head, reading each
+        row's history from ``seq``."""
         st = self.ragged_state()
         self._ragged_params(st, words)
-        step = self._ragged_step(st, greedy, logprobs)
+        on = proc is not None
+        if on:
+            self._proc_params(proc)
+        step = self._ragged_step(st, greedy, logprobs, proc=on)
 
         def warm():  # with every row marked finished the step is idempotent: the state the caller
             done = st["done"].clone()  # set up is left as it is
@@ -598,7 +692,8 @@ class _GpuCache:
             step()
             st["done"].copy_(done)
 
-        self._loop(("ragged_lp" if logprobs else "ragged", greedy), lambda: _Loop(step, st, warm)).run(n)
+        key = ("ragged_proc" if on else "ragged") + ("_lp" if logprobs else "")
+        self._loop((key, greedy), lambda: _Loop(step, st, warm)).run(n)
         return st
 
     # ----------------------------------------------------------------- beam search
@@ -763,6 +858,31 @@ def _sample_words(seed, draw, temperature, top_k, top_p=None):
     return [s32(seed), s32(seed >> 32), s32(draw), inv_t, min(int(top_k or 0), 0x7FFFFFFF), 0, p_bits, 0]
 
 
+_PROC_HIST_MAX = 4096  # history entries the process kernel stages (kernels.h kProcHistMax)
+
+
+def _proc_words(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size):
+    """The process kernel's parameter block as 8 int32 (the rule in common.h, 'Logits processors'):
+    float32(repetition_penalty), float32(1 / repetition_penalty), float32(presence_penalty) and
+    float32(frequency_penalty) as bits, no_repeat_ngram_size, 0, 0, 0."""
+    bits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
+    vals = R.process_values(repetition_penalty, presence_penalty, frequency_penalty)
+    return [bits(v) for v in vals] + [int(no_repeat_ngram_size), 0, 0, 0]
+
+
+def _processors(who, model, kernel, repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size):
+    """(args, words) of a call's logits processors -- the arguments as ``R.process_logits`` takes them
+    and the device parameter block -- or (None, None) when every one is at its off value.
+    ``kernel``: the call goes through the process kernel, whose history is bounded."""
+    args = (repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size)
+    if not R.check_process_args(*args):
+        return None, None
+    if kernel and model.block_size > _PROC_HIST_MAX:
+        raise ValueError(f"{who}: the logits processors keep at most {_PROC_HIST_MAX} history tokens on the "
+                         f"device, block_size is {model.block_size}")
+    return args, _proc_words(*args)
+
+
 def _weight_stamp(model):
     return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
@@ -789,8 +909,23 @@ def _gpu_cache(model, idx, tmax, last=None):
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
-             top_p: Optional[float] = None, return_logprobs: bool = False):
-    """``return_logprobs``: return ``(idx, logprobs)``, ``logprobs`` float32 of ``idx``'s shape --
+             top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
+             presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
+    """``repetition_penalty`` (finite, > 0; 1.0 off), ``presence_penalty``, ``frequency_penalty``
+    (finite; 0.0 off), ``no_repeat_ngram_size`` (0 .. 8; 0 off): the logits processors (the rule in
+    common.h, 'Logits processors'), applied to the stored logits before the temperature, top-k, top-p
+    and the draw; greedy takes the argmax of the processed row.  A token seen c >= 1 times in the
+    history has its logit x replaced by (x > 0 ? x / rp : x * rp) - (fp * c + pp), and with
+    ``no_repeat_ngram_size = g`` every token that would complete a g-gram already in the history gets
+    -inf.  The history of the token at column T is ``idx[b, max(0, T - block_size):T]`` -- exactly
+    the context the model saw, NOT the whole sequence as in libraries that keep it all: past
+    ``block_size`` the oldest tokens drop out of the penalties as they drop out of the attention,
+    which bounds the history by ``block_size``.  With any processor on, ``return_logprobs`` reports
+    the log-softmax of the processed row.  On the GPU (greedy or seeded) the process kernel runs
+    inside the captured step, in loops of their own; with every argument at its off value every
+    path is what it is without them.  ValueError for anything else.
+
+    ``return_logprobs``: return ``(idx, logprobs)``, ``logprobs`` float32 of ``idx``'s shape --
     entry [b, j] is the model's log-probability of ``idx[b, j]`` given ``idx[b, :j]`` (the cropped
     window past ``block_size``, as for the token itself) at every generated position and 0.0 at the
     prompt's.  It is the log-softmax of the model's logits at temperature 1, before top-k and
@@ -812,6 +947,12 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         R.check_sample_args(temperature, top_k, top_p)
     if seeded:
         seed = int(seed) & ((1 << 64) - 1)
+    on_device = idx.is_cuda and use_cache and max_new_tokens > 0 and (seeded or not do_sample)  # the device loops
+    proc, pwords = _processors("generate", model, on_device, repetition_penalty, presence_penalty,
+                               frequency_penalty, no_repeat_ngram_size)
+
+    def edit(logits, hist):  # host loops: the processors on the logits of the token after ``hist``
+        return logits if proc is None else R.process_logits(logits, hist, *proc)
 
     def pick(logits, col):
         if seeded:
@@ -836,20 +977,25 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         for _ in range(max_new_tokens):
             idx_cond = idx if idx.size(1) <= bs else idx[:, -bs:]
             logits, _ = model(idx_cond)
-            nxt = pick(logits[:, -1, :], idx.size(1))
+            last = edit(logits[:, -1, :], idx_cond)
+            nxt = pick(last, idx.size(1))
             if return_logprobs:
-                lps.append(R.token_logprob(logits[:, -1, :], nxt))
+                lps.append(R.token_logprob(last, nxt))
             idx = torch.cat((idx, nxt), dim=1)
         return done(idx)
-    if idx.is_cuda and max_new_tokens > 0 and (seeded or not do_sample):
+    if on_device:
         if seeded:  # the draw counter of a token is its column T
             words = lambda T: _sample_words(seed, T, temperature, top_k, top_p)
-            first = lambda c, T: c.sample_prefill(words(T))
-            loop = lambda c, tok, L, n, T: c.sample(tok, L, n, words(T), logprobs=return_logprobs)
+            first = lambda c, T, ctx: c.sample_prefill(words(T))
+            loop = lambda c, tok, L, n, T, ctx: c.sample(tok, L, n, words(T), logprobs=return_logprobs,
+                                                         proc=pwords, ctx=ctx)
         else:
-            first = lambda c, T: c.logits.argmax(-1)
-            loop = lambda c, tok, L, n, T: c.greedy(tok, L, n, logprobs=return_logprobs)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs)
+            first = lambda c, T, ctx: c.logits.argmax(-1)
+            if proc is None:
+                loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs)
+            else:
+                loop = lambda c, tok, L, n, T, ctx: c.greedy_proc(tok, L, n, pwords, ctx, logprobs=return_logprobs)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
@@ -858,6 +1004,7 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             cache = _gpu_cache(model, idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond)
             cache.pos = idx_cond.size(1)
             logits = cache.logits
+        logits = edit(logits, idx[:, max(0, T - bs):])
         idx_next = pick(logits, T)
         if return_logprobs:
             lps.append(R.token_logprob(logits, idx_next))
@@ -870,12 +1017,14 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     return done(idx)
 
 
-def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False):
+def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False, proc=None):
     """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
-    window's first token ``first(cache, T)`` [B], then the device-side token loop ``loop(cache,
-    tok, L, n, T)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
+    window's first token ``first(cache, T, ctx)`` [B], then the device-side token loop ``loop(cache,
+    tok, L, n, T, ctx)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
     position ``L``) for every position the window still has room for.  ``T`` is the column of the
-    call's first token in the returned sequence.  Once the sequence outgrows block_size, each token
+    call's first token in the returned sequence, ``ctx`` the window's context.  ``proc``
+    (``_proc_words``): the prefill logits are edited by the logits processors over ``ctx`` before
+    the first pick (``process_prefill``).  Once the sequence outgrows block_size, each token
     is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
     (``/root/reference/mingpt/model.py:333``).  ``logprobs``: the first token gets its
     log-probability from the prefill logits (``with_logprob``), ``loop`` returns a (tokens,
@@ -895,12 +1044,14 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
         cache = _gpu_cache(model, ctx, bs)
-        tok = first(cache, T)
+        if proc is not None:
+            cache.process_prefill(ctx, proc)
+        tok = first(cache, T, ctx)
         put(T, cache.with_logprob(tok) if logprobs else tok)
         T += 1
         n = min(end - T, bs - L)
         if n > 0:
-            put(slice(T, T + n), loop(cache, out[:, T - 1:T], L, n, T))
+            put(slice(T, T + n), loop(cache, out[:, T - 1:T], L, n, T, ctx))
             T += n
     return outs if logprobs else out
 
@@ -945,7 +1096,9 @@ def _check_token_ids(who, V, tokens, pad_token=None, eos_token=None, what="promp
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                    top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
-                   pad_token: int = 0, top_p: Optional[float] = None, return_logprobs: bool = False):
+                   pad_token: int = 0, top_p: Optional[float] = None, return_logprobs: bool = False,
+                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                   no_repeat_ngram_size: int = 0):
     """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``, or
     with ``return_logprobs`` ``(tokens, lengths, logprobs)``: float32 of ``tokens``' shape, entry
     [b, j] the model's log-probability of ``tokens[b, j]`` given ``tokens[b, :j]`` at every generated
@@ -966,6 +1119,11 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     tokens.  There is no sliding window here: ``max(len) + max_new_tokens`` must fit ``block_size``
     (ValueError otherwise).
 
+    ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``, ``no_repeat_ngram_size``: the
+    logits processors of ``generate`` (the rule in common.h), with the row's own unpadded sequence so
+    far as its history -- never the padding, never another row.  With any of them on the reported
+    log-probabilities are the processed rows'.
+
     On the GPU the right-padded batch is prefilled once and the token loop is one captured step
     replayed back to back (``_GpuCache.ragged``): per-row positions and finished flags live in
     device memory.  On the CPU each row runs through the cache path on its own."""
@@ -980,6 +1138,8 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
                          f"block_size ({bs}); this entry point has no sliding window")
     _check_token_ids("generate_batch", V, torch.cat(rows), pad_token, eos_token)
     R.check_sample_args(temperature, top_k, top_p)
+    proc, pwords = _processors("generate_batch", model, device.type == "cuda", repetition_penalty, presence_penalty,
+                               frequency_penalty, no_repeat_ngram_size)
     if do_sample and seed is None:
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
     seed = int(seed or 0) & ((1 << 64) - 1)
@@ -993,11 +1153,13 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
         return (tokens, lengths, logprobs) if return_logprobs else (tokens, lengths)
     if device.type == "cuda":
         return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
-                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs)
+                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs, pwords)
     for b, r in enumerate(rows):  # the executable definition of the semantics
         cache = _CpuCache(model, r.view(1, -1))
         logits, n = cache.logits, lens[b]
         for _ in range(max_new_tokens):
+            if proc is not None:  # the history is the row's own sequence so far
+                logits = R.process_logits(logits, tokens[b:b + 1, :n], *proc)
             if do_sample:
                 nxt = R.sample_gumbel(logits, temperature, top_k, seed, n, row0=b, top_p=top_p)
             else:
@@ -1015,24 +1177,25 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
 
 def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
-                        pad_token, top_p=None, logprobs=False):
+                        pad_token, top_p=None, logprobs=False, proc=None):
     """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
     causal attention makes every position before a row's length exact -- take row b's logits at
     column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
     ragged step max_new_tokens - 1 times.  With a stop token the finished flags are read every
     ``_EXIT_EVERY`` replays; stopping early changes nothing, since a step leaves finished rows as
     they are.  ``logprobs``: the loops with the lse kernel, and the state's ``lp`` buffer (zero but
-    at the generated positions) as a third result."""
+    at the generated positions) as a third result.  ``proc`` (``_proc_words``): the loops with the
+    process kernel in front of the pick, the first pick included."""
     B, Lmax = idx.shape
     cache = _gpu_cache(model, idx, model.block_size, last=lengths - 1)
     words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
-    st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs)
+    st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs, proc=proc)
     n = max_new_tokens - 1
     check = _EARLY_EXIT and eos_token is not None  # without a stop token no row finishes early
     while n > 0:
         k = min(n, _EXIT_EVERY) if check else n
-        cache.ragged(k, words, greedy, logprobs=logprobs)
+        cache.ragged(k, words, greedy, logprobs=logprobs, proc=proc)
         n -= k
         if check and n > 0 and bool(st["done"].all()):
             break

@@ -219,33 +219,42 @@ class GPT(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                  top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
-                 top_p: Optional[float] = None, return_logprobs: bool = False):
+                 top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
         prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
         ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
         (``generation.generate``); None draws from torch's global generator as before.  ``top_p``:
         nucleus filtering after the temperature and top-k (None or 1.0: off).  ``return_logprobs``:
         returns ``(idx, logprobs)``, the model's log-probability of every generated token (0.0 at
-        the prompt)."""
+        the prompt).  ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` /
+        ``no_repeat_ngram_size``: the logits processors over the context the model saw, applied to
+        the logits before everything else (1.0 / 0.0 / 0.0 / 0: off)."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
-                        top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs)
+                        top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs,
+                        repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                        frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                        top_k: Optional[int] = None, seed: Optional[int] = None,
                        eos_token: Optional[int] = None, pad_token: int = 0, top_p: Optional[float] = None,
-                       return_logprobs: bool = False):
+                       return_logprobs: bool = False, repetition_penalty: float = 1.0,
+                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
         """Decode prompts of different lengths in one batch, each row stopping at ``eos_token`` or
         after ``max_new_tokens``; returns ``(tokens, lengths)`` (``generation.generate_batch``).  No
         sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``.
-        ``return_logprobs``: returns ``(tokens, lengths, logprobs)``."""
+        ``return_logprobs``: returns ``(tokens, lengths, logprobs)``.  The logits processors
+        (``repetition_penalty`` ...) are those of ``generate``, per row over its own sequence."""
         from .generation import generate_batch
 
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, do_sample=do_sample,
                               top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token, top_p=top_p,
-                              return_logprobs=return_logprobs)
+                              return_logprobs=return_logprobs, repetition_penalty=repetition_penalty,
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                              no_repeat_ngram_size=no_repeat_ngram_size)
 
     @torch.no_grad()
     def generate_beam(self, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,

@@ -41,7 +41,8 @@ _ERR_BITS = {1: "embedding_fwd: token id outside [0, vocab)",
              2: "embedding_bwd: token id outside [0, vocab)",
              4: "cross-entropy: target >= vocab",
              8: "beam_merge: chosen token outside [0, vocab)",
-             16: "beam_reorder: parent outside [0, beams)"}
+             16: "beam_reorder: parent outside [0, beams)",
+             32: "logits_process: history token id outside [0, vocab)"}
 
 
 class DeviceCheckError(RuntimeError):

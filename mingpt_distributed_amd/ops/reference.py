@@ -13,6 +13,7 @@ cross-entropy with ``ignore_index=-1`` (``model.py:316-318``).
 from __future__ import annotations
 
 import math
+import numbers
 
 import torch
 import torch.nn.functional as F
@@ -86,6 +87,67 @@ def check_sample_args(temperature: float, top_k, top_p=None) -> None:
         raise ValueError(f"sampling needs top_k >= 1 (or None), got {top_k}")
     if top_p is not None and not 0 < float(top_p) <= 1:  # NaN fails both comparisons
         raise ValueError(f"sampling needs 0 < top_p <= 1 (or None), got {top_p}")
+
+
+PROC_NGRAM_MAX = 8  # kernels.h kProcNgramMax
+
+
+def check_process_args(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                       no_repeat_ngram_size=0) -> bool:
+    """ValueError unless the logits processors' arguments are valid (common.h, 'Logits processors');
+    returns whether any processor is on (an argument differs from its off value)."""
+    fin = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(v)
+    if not (fin(repetition_penalty) and repetition_penalty > 0):
+        raise ValueError(f"repetition_penalty must be finite and > 0 (1.0: off), got {repetition_penalty}")
+    if not fin(presence_penalty):
+        raise ValueError(f"presence_penalty must be finite (0.0: off), got {presence_penalty}")
+    if not fin(frequency_penalty):
+        raise ValueError(f"frequency_penalty must be finite (0.0: off), got {frequency_penalty}")
+    g = no_repeat_ngram_size
+    if isinstance(g, bool) or not isinstance(g, numbers.Integral) or not 0 <= g <= PROC_NGRAM_MAX:
+        raise ValueError(f"no_repeat_ngram_size must be an integer in 0..{PROC_NGRAM_MAX} (0: off), got {g}")
+    return repetition_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0 or g != 0
+
+
+def process_values(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """(rp, inv, pp, fp) of the rule as Python floats holding float32 values: the arguments rounded
+    to float32 and inv = float32(1.0 / repetition_penalty), computed as ``sample_inv_t`` does."""
+    f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32).item())
+    return (f32(repetition_penalty), sample_inv_t(repetition_penalty), f32(presence_penalty),
+            f32(frequency_penalty))
+
+
+def process_logits(logits: torch.Tensor, hist: torch.Tensor, repetition_penalty=1.0, presence_penalty=0.0,
+                   frequency_penalty=0.0, no_repeat_ngram_size=0) -> torch.Tensor:
+    """The logits processors of ``csrc/include/common.h`` ('Logits processors'; the kernel is
+    ``csrc/kernels/process.hip``) in torch: rows ``logits`` [B, V] (any floating dtype) edited from the
+    histories ``hist`` [B, n] (int64, n >= 1) -- the penalties as single float32 operations rounded to
+    the logits' dtype, then the no-repeat n-gram ban.  Returns a new tensor of ``logits``' dtype."""
+    check_process_args(repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size)
+    B, V = logits.shape
+    n, dev = hist.size(1), logits.device
+    hist = hist.to(dev)
+    rp, inv, pp, fp = (torch.tensor(v, dtype=torch.float32, device=dev)
+                       for v in process_values(repetition_penalty, presence_penalty, frequency_penalty))
+    valid = (hist >= 0) & (hist < V)  # an id outside [0, V) counts for nothing
+    safe = torch.where(valid, hist, torch.zeros_like(hist))
+    c = torch.zeros(B, V, dtype=torch.long, device=dev).scatter_add_(1, safe, valid.long())
+    x = logits.float()
+    a = torch.where(x > 0, x * inv, x * rp)
+    q = fp * c.float()
+    q = q + pp
+    y = (a - q).to(logits.dtype)
+    out = torch.where((c > 0) & (x != float("-inf")), y, logits)
+    g = int(no_repeat_ngram_size)
+    if g >= 1 and n >= g:
+        ok = torch.ones(B, n - g + 1, dtype=torch.bool, device=dev)  # column i: slot t = g - 1 + i
+        for j in range(g - 1):  # h[t - 1 - j] == h[n - 1 - j], both real ids
+            a_ = hist[:, g - 2 - j:n - 1 - j]
+            ok &= (a_ == hist[:, n - 1 - j:n - j]) & valid[:, g - 2 - j:n - 1 - j]
+        ok &= valid[:, g - 1:]
+        ban = torch.zeros(B, V, dtype=torch.long, device=dev).scatter_add_(1, safe[:, g - 1:], ok.long())
+        out = out.masked_fill(ban > 0, float("-inf"))
+    return out
 
 
 def sample_inv_t(temperature: float) -> float:

@@ -60,6 +60,15 @@ def main(argv=None):
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--logprobs", action="store_true",
                     help="print each sample's summed log-probability and per-token perplexity")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="divide (positive) or multiply (negative) the logit of every token already in the "
+                         "context by this (1.0: off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0,
+                    help="subtract this from the logit of every token already in the context (0.0: off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0,
+                    help="subtract this times its count from the logit of every token in the context (0.0: off)")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0,
+                    help="never complete an n-gram of this size (1..8) that is already in the context (0: off)")
     ap.add_argument("--beams", type=int, default=0,
                     help="beam search with this many beams (1..8) on one prompt instead of sampling")
     ap.add_argument("--length-penalty", type=float, default=0.0,
@@ -93,6 +102,9 @@ def main(argv=None):
             texts += [ln.rstrip("\n") for ln in f if ln.strip()]
     if a.beams and len(texts) > 1:
         ap.error("--beams takes one prompt")
+    proc = process_args(a)
+    if proc and (a.beams or a.speculative):
+        ap.error("the logits processors do not go with --beams or --speculative")
     if a.speculative and (len(texts) > 1 or a.beams):
         ap.error("--speculative takes one prompt and does not go with --beams")
     if len(texts) > 1:
@@ -107,7 +119,7 @@ def main(argv=None):
     if a.speculative:
         return generate_speculative(model, tok, x, a)
     x = x.expand(a.num_samples, -1).contiguous()
-    kw = {"return_logprobs": True} if a.logprobs else {}
+    kw = dict({"return_logprobs": True} if a.logprobs else {}, **proc)
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
                        top_k=a.top_k, seed=a.seed, top_p=a.top_p, **kw)
     y, lp = y if a.logprobs else (y, None)
@@ -120,6 +132,15 @@ def main(argv=None):
         if lp is not None:
             print_logprob(lp[i, x.size(1):])
     return outs
+
+
+def process_args(a):
+    """The logits-processor arguments of ``generate`` / ``generate_batch`` that the command line
+    moved from their off values (none: the call is what it is without them)."""
+    kw = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
+              frequency_penalty=a.frequency_penalty, no_repeat_ngram_size=a.no_repeat_ngram)
+    off = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram_size=0)
+    return {k: v for k, v in kw.items() if v != off[k]}
 
 
 def print_logprob(lp):
@@ -171,7 +192,7 @@ def generate_many(model, tok, texts, a, dev):
         rows = [torch.tensor([int(w) for w in t.split()] or [0], dtype=torch.long) for t in texts]
         eos = None
     rows = [r.to(dev) for r in rows for _ in range(a.num_samples)]
-    kw = {"return_logprobs": True} if a.logprobs else {}
+    kw = dict({"return_logprobs": True} if a.logprobs else {}, **process_args(a))
     y, n, *lp = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature,
                                      do_sample=not a.greedy, top_k=a.top_k, seed=a.seed, eos_token=eos,
                                      top_p=a.top_p, **kw)
