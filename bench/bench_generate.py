@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Greedy-decode throughput (BASELINE config #4, the generate.ipynb path) on random GPT-2 124M
-weights: this framework's ``GPT.generate`` (prefill once on the gfx950 kernels, then one-token
-steps against the KV cache with the decode-attention kernel) vs the reference's algorithm
-(``/root/reference/mingpt/model.py:322-356``: re-run the full forward over the whole prefix for
+"""Greedy-decode throughput (BASELINE config #4, the generate.ipynb path) on random weights of a
+GPT-2 preset (--model-type, default gpt2 = 124M): this framework's ``GPT.generate`` (prefill once
+on the gfx950 kernels, then one-token steps against the KV cache with the decode-attention
+kernel) vs the reference's algorithm (``/root/reference/mingpt/model.py:322-356``: re-run the full forward over the whole prefix for
 every new token, no cache) in stock PyTorch bf16 (autocast + SDPA).  Prints one JSON line per B."""
 import argparse
 import json
@@ -59,7 +59,7 @@ def ragged(model, a):
             for _ in range(a.reps):
                 for k, fn in cases.items():
                     times[k].append(timed(fn)[1])
-        res = {"metric": "ragged greedy decode tokens/s", "model": "gpt2 (random init)", "batch": B,
+        res = {"metric": "ragged greedy decode tokens/s", "model": f"{a.model_type} (random init)", "batch": B,
                "equal_prompt": a.prompt, "mixed_lengths": lens, "new_tokens": a.new, "reps": a.reps}
         for k, ts in times.items():
             res[k + "_tok_s"] = round(B * a.new / statistics.median(ts), 1)
@@ -104,7 +104,7 @@ def logprobs(model, a):
             for _ in range(a.reps):
                 for k, fn in cases.items():
                     times[k].append(timed(fn)[1])
-        res = {"metric": "decode tokens/s without / with return_logprobs", "model": "gpt2 (random init)",
+        res = {"metric": "decode tokens/s without / with return_logprobs", "model": f"{a.model_type} (random init)",
                "batch": B, "entry": "generate_batch" if a.ragged else "generate", "prompt_lengths": lens,
                "new_tokens": a.new, "sample": bool(a.sample), "top_k": a.top_k if a.sample else None,
                "top_p": a.top_p if a.sample else None, "seed": a.seed, "reps": a.reps}
@@ -143,7 +143,7 @@ def process(model, a):
             for _ in range(a.reps):
                 for k, fn in cases.items():
                     times[k].append(timed(fn)[1])
-        res = {"metric": "decode tokens/s, logits processors off / on", "model": "gpt2 (random init)", "batch": B,
+        res = {"metric": "decode tokens/s, logits processors off / on", "model": f"{a.model_type} (random init)", "batch": B,
                "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "top_p": a.top_p, "seed": samp["seed"],
                "processors": on, "reps": a.reps}
         for k, ts in times.items():
@@ -180,7 +180,7 @@ def beams(model, a):
             for _ in range(a.reps):
                 for k, fn in cases.items():
                     times[k].append(timed(fn)[1])
-        res = {"metric": "beam search: best-beam tokens/s and us per step", "model": "gpt2 (random init)",
+        res = {"metric": "beam search: best-beam tokens/s and us per step", "model": f"{a.model_type} (random init)",
                "beams": W, "prompt": a.prompt, "new_tokens": a.new, "reps": a.reps,
                "reorder": "per layer" if a.per_layer else "one launch"}
         for k, ts in times.items():
@@ -220,11 +220,14 @@ def main():
     ap.add_argument("--process", action="store_true",
                     help="time generate with the logits processors off and on, greedy and seeded (this "
                          "framework only)")
+    ap.add_argument("--model-type", default="gpt2", choices=["gpt2", "gpt2-medium", "gpt2-large", "gpt2-xl"],
+                    help="the preset whose shape is timed, on random weights (default: gpt2, 124M)")
     a = ap.parse_args()
     from mingpt_distributed_amd.models import GPT, GPTConfig
 
     torch.manual_seed(0)
-    ours = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False)
+    cfg = GPTConfig(model_type=a.model_type, vocab_size=50257, block_size=1024)
+    ours = GPT(cfg, verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
     if a.beams:
         return beams(ours, a)
@@ -246,7 +249,7 @@ def main():
                 ours.generate(idx, 4, **kw)  # warm-up (kernels, caches, graph capture)
                 out, t = timed(lambda: ours.generate(idx, a.new, **kw))
             assert out.shape == (B, a.prompt + a.new)
-            print(json.dumps({"metric": "sampled decode tokens/s", "model": "gpt2 (random init)", "batch": B,
+            print(json.dumps({"metric": "sampled decode tokens/s", "model": f"{a.model_type} (random init)", "batch": B,
                               "prompt": a.prompt, "new_tokens": a.new, "top_k": a.top_k, "top_p": a.top_p,
                               "seed": a.seed,
                               "tok_s": round(B * a.new / t, 1), "ms_per_step": round(t / a.new * 1e3, 4)}),
@@ -254,7 +257,7 @@ def main():
         return
     from bench.baseline_torch import GPT as TorchGPT
 
-    ref = TorchGPT(p=0.0, attn="sdpa").cuda().eval()
+    ref = TorchGPT(L=cfg.n_layer, H=cfg.n_head, D=cfg.n_embed, p=0.0, attn="sdpa").cuda().eval()
     for B in map(int, a.batches.split(",")):
         idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
         with torch.no_grad():
@@ -271,7 +274,7 @@ def main():
             ref_generate() if a.new <= 8 else None
             _, t_ref = timed(ref_generate)
         assert out.shape == (B, a.prompt + a.new)
-        print(json.dumps({"metric": "greedy decode tokens/s", "model": "gpt2 (random init)", "batch": B,
+        print(json.dumps({"metric": "greedy decode tokens/s", "model": f"{a.model_type} (random init)", "batch": B,
                           "prompt": a.prompt, "new_tokens": a.new,
                           "ours_kv_cache_tok_s": round(B * a.new / t_ours, 1),
                           "reference_algorithm_torch_tok_s": round(B * a.new / t_ref, 1),

@@ -526,7 +526,11 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
                 const c10::optional<at::Tensor>& am_pos) {
   CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
   const int64_t K = W.size(1), N = W.size(0), B = x.numel() / K;
-  TORCH_CHECK(x.size(-1) == K && mg::gemv_supported((int)B, (int)K), "gemv: B <= 8, K % 8 == 0, K <= 4096");
+  TORCH_CHECK(x.size(-1) == K && mg::gemv_supported((int)B, (int)K), "gemv: B <= 8, K % 8 == 0, K <= 8192");
+  // rows staged in two segments: the one-row-per-wave path without fused LayerNorm only
+  TORCH_CHECK(K <= mg::kGemvSegK || N <= 8192, "gemv: K > 4096 needs N <= 8192 (wide outputs take K <= 4096)");
+  TORCH_CHECK(K <= mg::kGemvSegK || !(lnw.has_value() || lnb.has_value()),
+              "gemv: K > 4096 cannot take LayerNorm weights (the fused LayerNorm takes K <= 4096)");
   if (ldy <= 0) ldy = N;
   TORCH_CHECK(ldy >= N && epi >= 0 && epi <= 3, "gemv: ldy / epi");
   if (bias.has_value()) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N); }

@@ -66,6 +66,10 @@ void comm_proxy(const void* src, void* dst, long n16, long total16, int channels
                 hipStream_t stream);
 
 // gemv.hip (decode-time skinny GEMM, B <= 8 rows; epi 0 none, 1 bias, 2 bias+GELU, 3 bias+residual)
+// gemv_supported: 1 <= B <= 8, K % 8 == 0, K <= 8192.  K > kGemvSegK (rows staged in two segments)
+// only for N <= 8192 outputs and without fused LayerNorm (lnw / lnb null); the caller checks
+// (bindings.cpp)
+constexpr int kGemvSegK = 4096;  // B x kGemvSegK bf16 of x is the LDS staging buffer (64 KiB at B = 8)
 bool gemv_supported(int B, int K);
 // greedy-decode epilogue of the LM-head GEMV: each workgroup's best (ordered bf16 logit << 32 |
 // ~index) key per row into part[b][workgroup]; workgroup 0 advances *pos.  The argmax over the

@@ -8,6 +8,8 @@
 // matrix (K x N bf16, read once) against B vectors that fit in LDS, so here:
 //   * x [B, K] is staged once per workgroup in LDS -- optionally LayerNorm'ed on the way in (the
 //     LN that precedes every decode projection but the residual ones; one kernel instead of two);
+//     rows of 4096 < K <= 8192 (the MLP output projection of gpt2-large / -xl) go through the
+//     same 64 KiB buffer in two segments (gemv_kernel's KMAX);
 //   * a wave owns one output column n (outputs <= 8k: every block projection) or 4 (the LM head):
 //     its 64 (or 16) lanes read row n = W[n, :] in 16-byte chunks, 4 loads in flight per lane,
 //     FMA against the B vectors from LDS;
@@ -28,7 +30,7 @@ using namespace mg;
 namespace {
 
 constexpr int kGemvMaxB = 8;
-constexpr int kGemvMaxK = 4096;  // B x K bf16 of x must fit the LDS staging buffer
+constexpr int kGemvMaxK = 2 * kGemvSegK;  // narrow outputs: two segments of x (kernels.h kGemvSegK)
 
 MG_DEVICE unsigned long long umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
@@ -54,7 +56,17 @@ MG_DEVICE void gemv_argmax(const GemvArgmax& am, const unsigned long long (&key)
   if (blockIdx.x == 0 && threadIdx.x == 0) *am.pos += 1;  // nothing else in this kernel reads it
 }
 
-template <int B, int LPR, bool NTW>
+// KMAX: the longest row an instantiation takes.  kGemvSegK: x is staged whole, [B][K].  kGemvMaxK
+// (one row per wave only; launched for K > kGemvSegK): the whole weight row is still requested up
+// front (16 chunks per lane), x goes through the LDS buffer in segments of kGemvSegK columns,
+// [B][kGemvSegK], with a workgroup barrier between segments -- segment s + 1's weight chunks and
+// its x chunks are in flight (or already in registers) while segment s is multiplied.  Chosen over
+// whole-row staging (B x 8192 x 2 B = 128 KiB: an opt-in above the 64 KiB dynamic-LDS default and
+// one workgroup per CU): 64 KiB keeps two workgroups on a CU, so the 320 / 400 workgroups of the
+// gpt2-large / -xl MLP projection are all resident on the 256 CUs at once instead of running as
+// one full round and a part-filled second.  A lane's sum is the same chain either way: chunks
+// u = 0, 1, ... in order, 8 fmas each, then the xor fold.
+template <int B, int LPR, bool NTW, int KMAX = kGemvSegK>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ W,
                                                    bf16_t* __restrict__ y, int N, int K, long ldy,
@@ -63,15 +75,17 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ lnw,
                                                    const bf16_t* __restrict__ lnb, float eps,
                                                    const GemvArgmax am) {
-  extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [B][K]
+  extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [B][K]; LONGK: [B][kGemvSegK]
+  constexpr bool LONGK = KMAX > kGemvSegK;
+  static_assert(!LONGK || LPR == 64, "rows longer than kGemvSegK: one row per wave only");
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   constexpr int RPW = 64 / LPR;  // rows per wave
   const int g = lane / LPR, j = lane % LPR;
   const int n = (blockIdx.x * 4 + wid) * RPW + g;
   constexpr int STRIDE = LPR * 8;  // elements per load round of a row
-  // one row per wave: the whole row (K <= 4096: <= 8 loads per lane) is requested before x is
-  // staged and normalised, so the weight stream's memory latency overlaps the LayerNorm's
-  constexpr int NPF = LPR == 64 ? kGemvMaxK / STRIDE : 1;
+  // one row per wave: the whole row (K <= 4096: <= 8 loads per lane; LONGK: <= 16) is requested
+  // before x is staged and normalised, so the weight stream's memory latency overlaps the LayerNorm's
+  constexpr int NPF = LPR == 64 ? KMAX / STRIDE : 1;
   uint4 wpf[NPF];
   if constexpr (LPR == 64) {
     const bf16_t* wr = W + (long)min(n, N - 1) * K;
@@ -81,7 +95,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
       wpf[u] = c < K ? (NTW ? ld16_nt(wr + c) : ld16(wr + c)) : make_uint4(0, 0, 0, 0);
     }
   }
-  if (lnw) {
+  if (!LONGK && lnw) {  // (LONGK: no fused LayerNorm -- a LayerNorm'ed row is at most 4096 wide)
     // fused LayerNorm of the B input rows (wave w normalises rows w, w+4): the same lane/chunk
     // order and wave reduction as ln_fwd_kernel, so the staged bf16 rows equal its output
     // K <= 1024 (GPT-2 small / medium): the row, gamma and beta chunks are loaded once into
@@ -168,10 +182,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
       }
     }
     }
-  } else {
+  } else if constexpr (!LONGK) {
     for (int i = threadIdx.x * 8; i < B * K; i += 256 * 8) st16(xs + i, ld16(x + i));
   }
-  __syncthreads();
+  if constexpr (!LONGK) __syncthreads();
   // LPR lanes per output row: 16 (4 rows per wave) for wide outputs (the LM head), 64 (one row per
   // wave, the whole row's loads in flight at once) for the block projections, whose 48-192
   // workgroups at 16 lanes per row left most of the chip idle and the HBM latency exposed
@@ -197,7 +211,56 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
   float acc[B];
 #pragma unroll
   for (int b = 0; b < B; ++b) acc[b] = 0.f;
-  if constexpr (LPR == 64) {
+  if constexpr (LONGK) {
+    constexpr int UPS = kGemvSegK / STRIDE;  // weight chunks per lane and segment
+    constexpr int CPT = kGemvSegK / (256 * 8);  // x chunks per thread, row and segment
+    constexpr int NSEG = KMAX / kGemvSegK;
+    uint4 xv[B][CPT];  // a segment of x on its way to LDS: requested one segment ahead
+    auto load_x = [&](int s0) {
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+#pragma unroll
+        for (int h = 0; h < CPT; ++h) {
+          const int c = s0 + (threadIdx.x + h * 256) * 8;
+          xv[b][h] = c < K ? ld16(x + (long)b * K + c) : make_uint4(0, 0, 0, 0);
+        }
+      }
+    };
+    load_x(0);
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s) {
+      const int s0 = s * kGemvSegK;
+      if (s0 < K) {  // K is uniform over the workgroup: so are the barriers
+        if (s > 0) __syncthreads();  // every wave is done reading the previous segment
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+#pragma unroll
+          for (int h = 0; h < CPT; ++h) {
+            const int c = (threadIdx.x + h * 256) * 8;
+            if (s0 + c < K) st16(xs + b * kGemvSegK + c, xv[b][h]);
+          }
+        }
+        __syncthreads();
+        if (s + 1 < NSEG) load_x(s0 + kGemvSegK);
+#pragma unroll
+        for (int u = s * UPS; u < (s + 1) * UPS; ++u) {
+          const int c = j * 8 + u * STRIDE;
+          if (c < K) {
+            float wf[8];
+            unpack8(wpf[u], wf);
+#pragma unroll
+            for (int b = 0; b < B; ++b) {
+              float xf[8];
+              unpack8(ld16(xs + b * kGemvSegK + c - s0), xf);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) acc[b] = __builtin_fmaf(wf[e], xf[e], acc[b]);
+            }
+          }
+        }
+      }
+    }
+    epilogue(acc, n);
+  } else if constexpr (LPR == 64) {
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int c = j * 8 + u * STRIDE;
@@ -279,6 +342,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 
 namespace mg {
 
+// K > kGemvSegK: narrow outputs (N <= 8192) without fused LayerNorm only (the bindings check)
 bool gemv_supported(int B, int K) { return B >= 1 && B <= kGemvMaxB && K % 8 == 0 && K <= kGemvMaxK; }
 
 // wide outputs: a few workgroups per CU, grid-striding over the 16-row blocks
@@ -314,7 +378,8 @@ bool gemv_nt_weights() {
 void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long ldy, const bf16_t* bias,
           const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw, const bf16_t* lnb,
           float eps, const GemvArgmax* am) {
-  const size_t smem = sizeof(bf16_t) * (size_t)B * K;
+  const bool longk = K > kGemvSegK;  // x staged in segments of kGemvSegK columns
+  const size_t smem = sizeof(bf16_t) * (size_t)B * (longk ? kGemvSegK : K);
   // one row per wave (N / 4 workgroups) up to ~8k outputs; 4 rows per wave beyond (the LM head
   // already launches thousands of workgroups and re-stages x in each)
   const bool wide = N > 8192;
@@ -324,9 +389,14 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
 #define MG_GEMV_LAUNCH(b, lpr)                                                                                        \
   if (ntw) gemv_kernel<b, lpr, true><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv); \
   else gemv_kernel<b, lpr, false><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv);
+#define MG_GEMV_LAUNCH_LONG(b)                                                                                         \
+  if (ntw) gemv_kernel<b, 64, true, kGemvMaxK><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, nullptr, nullptr, eps, amv); \
+  else gemv_kernel<b, 64, false, kGemvMaxK><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, nullptr, nullptr, eps, amv);
 #define MG_GEMV_CASE(b)        \
   case b:                      \
-    if (wide) {                \
+    if (longk) {               \
+      MG_GEMV_LAUNCH_LONG(b)   \
+    } else if (wide) {         \
       MG_GEMV_LAUNCH(b, 16)    \
     } else {                   \
       MG_GEMV_LAUNCH(b, 64)    \
@@ -338,6 +408,7 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
     default: break;
   }
 #undef MG_GEMV_CASE
+#undef MG_GEMV_LAUNCH_LONG
 #undef MG_GEMV_LAUNCH
 }
 

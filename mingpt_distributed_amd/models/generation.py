@@ -341,7 +341,9 @@ class _GpuCache:
         tr, cfg = self.model.transformer, self.model.config
         B, D, H = tok.shape[0], cfg.n_embed, cfg.n_head
         # decode rows (B <= 8) go through the skinny GEMM (gemv.hip): at M = B the MFMA GEMM has
-        # one row tile and walks K latency-bound
+        # one row tile and walks K latency-bound.  The widest row is the MLP output projection's,
+        # 4 D <= 8192: every preset up to gpt2-xl (6400); the LayerNorm'ed projections and the LM
+        # head have K = D <= 2048, inside the kernel's 4096 for fused LayerNorm and wide outputs
         skinny = C.gemv_supported(B, 4 * D)
         x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
                             pos_stride).view(B, D)
@@ -501,7 +503,8 @@ class _GpuCache:
     def greedy(self, tok, pos, n, logprobs=False):
         """n greedy decode steps starting with token ``tok`` [B, 1] at position ``pos``: the step
         takes its input token and position from device buffers that its own kernels advance (the
-        fused argmax of ``_decode``; for a small vocabulary the argmax in torch).  Returns the n
+        fused argmax of ``_decode`` when the rows fit the skinny GEMM -- B <= 8, 4 * n_embed <= 8192
+        -- and V > 8192; otherwise the argmax in torch).  Returns the n
         new tokens [B, n] (positions pos + 1 .. pos + n); with ``logprobs`` also their
         log-probabilities [B, n] (``_greedy_lp``)."""
         assert pos + n <= self.tmax
@@ -809,7 +812,7 @@ class _GpuCache:
         tr, cfg = self.model.transformer, self.model.config
         D, H, V = cfg.n_embed, cfg.n_head, cfg.vocab_size
         R = self.B * K
-        if not C.gemv_supported(R, 4 * D):
+        if not C.gemv_supported(R, 4 * D):  # R <= 8 rows of at most 8192 columns (gemv.hip)
             raise RuntimeError(f"speculative decoding: {R} rows of width {4 * D} do not fit the skinny GEMM")
 
         def step():
@@ -1378,7 +1381,9 @@ def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ng
     Greedy only: no sampling, no log-probabilities and no stop token on this entry.  ``idx``: int64
     [B, T], rectangular.  ``1 <= draft_len <= 7`` with ``B * (draft_len + 1) <= 8`` (the rows of a step
     go through the skinny GEMM together), ``1 <= ngram <= 4``, and ``T + max_new_tokens`` must fit
-    ``block_size`` (no sliding window here); ValueError otherwise.
+    ``block_size`` (no sliding window here); ValueError otherwise.  On the GPU the model's widest
+    projection input, ``4 * n_embed``, must fit the skinny GEMM's 8192 columns (every preset up to
+    gpt2-xl); RuntimeError otherwise.
 
     ``return_stats``: also a dict with ``steps`` (int64 [B]: the verify steps in which the sequence
     was live) and ``emitted_hist`` (int64 [B, K + 1]: entry e counts the steps that emitted e
