@@ -4,6 +4,7 @@ import os
 import pytest
 import torch
 
+from _attn_probe import _dense_keep  # the one definition of the keep-word layout
 from mingpt_distributed_amd.ops import reference as R
 from mingpt_distributed_amd.ops._ext import ext
 
@@ -150,21 +151,6 @@ def test_attention_dropout_gradient_directional():
     fd = (fp - fm) / (2 * eps)
     an = (d * delta).sum()
     assert abs(fd.item() - an.item()) < 0.08 * abs(an.item()) + 1.0
-
-
-def _dense_keep(mask, B, T, H):
-    """Dense [B, H, T(query), T(key)] keep matrix from the keep-bit row words (layout and bit
-    order: attention_fwd.hip attn_dropmask_kernel; words of tiles past the diagonal are
-    unspecified)."""
-    ntw = 2 * ((T + 63) // 64)
-    words = mask.view(B * H, ntw, T).to(torch.int64) & 0xFFFFFFFF  # [bh, j, q]
-    key = torch.arange(T, device=mask.device)
-    kk = key % 64
-    j = (key // 64) * 2 + ((kk >> 2) & 1)
-    e = 16 * (kk >> 5) + 4 * ((kk >> 3) & 3) + (kk & 3)  # the forward lane's value index
-    bit = 16 * (e & 1) + (e >> 1)  # attn_common.h drop_bit: packed pair e >> 1
-    w = words[:, j, :]  # [bh, key, q]
-    return ((w >> bit[None, :, None]) & 1).transpose(1, 2).reshape(B, H, T, T).float()
 
 
 @pytest.mark.parametrize("hd", [8, 16, 24, 32, 48, 64, 80, 96, 112, 128])
