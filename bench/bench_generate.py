@@ -158,9 +158,10 @@ def process(model, a):
 
 
 def beams(model, a):
-    """Beam search per beam count W of --beams: ``generate_beam`` on one prompt of --prompt tokens,
-    next to the same row count through ``generate_batch(return_logprobs=True)`` greedy (W copies of
-    the prompt: the same decode step and lse kernel without the search).  Tokens/s of the best
+    """Beam search per beam count W of --beams: ``generate_beam`` on --beam-prompts prompts (default
+    one) of --prompt tokens, next to the same row count through
+    ``generate_batch(return_logprobs=True)`` greedy (W copies of each
+    prompt: the same decode step and lse kernel without the search).  Tokens/s of one prompt's best
     beam (--new tokens per call) and microseconds per step, median of --reps alternating runs with
     the spread.  --per-layer launches the cache reorder once per layer instead of once."""
     import statistics
@@ -168,9 +169,10 @@ def beams(model, a):
     from mingpt_distributed_amd.models import generation as gen
 
     gen._BEAM_REORDER_PER_LAYER = bool(a.per_layer)
-    idx = torch.randint(0, 50257, (1, a.prompt), generator=torch.Generator().manual_seed(1)).cuda()
+    P = a.beam_prompts  # the step runs on P * W rows (past 8: the rows GEMM, gemm_rows.hip)
+    idx = torch.randint(0, 50257, (P, a.prompt), generator=torch.Generator().manual_seed(1)).cuda()
     for W in map(int, a.beams.split(",")):
-        rows = [idx[0]] * W
+        rows = [p for p in idx for _ in range(W)]
         cases = {"beam": lambda: model.generate_beam(idx, a.new, W)[0],
                  "rows_logprobs": lambda: model.generate_batch(rows, a.new, return_logprobs=True)[0]}
         with torch.no_grad():
@@ -181,7 +183,7 @@ def beams(model, a):
                 for k, fn in cases.items():
                     times[k].append(timed(fn)[1])
         res = {"metric": "beam search: best-beam tokens/s and us per step", "model": f"{a.model_type} (random init)",
-               "beams": W, "prompt": a.prompt, "new_tokens": a.new, "reps": a.reps,
+               "beams": W, "prompts": P, "prompt": a.prompt, "new_tokens": a.new, "reps": a.reps,
                "reorder": "per layer" if a.per_layer else "one launch"}
         for k, ts in times.items():
             res[k + "_tok_s"] = round(a.new / statistics.median(ts), 1)
@@ -198,6 +200,8 @@ def main():
                     help="time generate_beam at these beam counts (e.g. 1,4,8) on one prompt, beside the same "
                          "row count through generate_batch(return_logprobs=True)")
     ap.add_argument("--per-layer", action="store_true", help="--beams: one cache-reorder launch per layer")
+    ap.add_argument("--beam-prompts", type=int, default=1,
+                    help="--beams: this many prompts per call (the step runs on prompts x beams rows)")
     ap.add_argument("--prompt", type=int, default=32)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--batches", default="1,8")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Greedy decode throughput of GPT.generate for an fp32-loaded model (the generate.ipynb /
 projects/generate path: weights left fp32, bf16 copies made once by the decode path) and a bf16
-model, GPT-2 124M random init, B = 1 and 8.  One JSON line per (dtype, B)."""
+model, GPT-2 124M random init, B = 1 and 8 (or the comma-separated BATCHES of the environment).  One
+JSON line per (dtype, B)."""
 import json
 import os
 import sys
@@ -19,7 +20,7 @@ for dt in (torch.float32, torch.bfloat16):
     m = GPT(GPTConfig(model_type="gpt2", vocab_size=50257, block_size=1024), verbose=False).eval()
     m.load_state_dict(base.state_dict())
     m = m.cuda().to(dt)
-    for B in (1, 8):
+    for B in map(int, os.environ.get("BATCHES", "1,8").split(",")):
         idx = torch.randint(0, 50257, (B, 32), device="cuda")
         with torch.no_grad():
             m.generate(idx, 8, do_sample=False)

@@ -565,6 +565,30 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
   return y;
 }
 
+// y[M, ldy] (ldy >= N) = epi(x[M, K] @ W[N, K]^T) at 1 <= M <= 64 rows: the decode-time projection
+// past the skinny GEMM's 8 rows (gemm_rows.hip)
+at::Tensor gemm_rows(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10::optional<at::Tensor>& bias,
+                     const c10::optional<at::Tensor>& resid, int64_t ldy) {
+  CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
+  TORCH_CHECK(W.dim() == 2 && W.size(0) >= 1 && W.size(1) >= 1, "gemm_rows: W [N, K]");
+  const int64_t K = W.size(1), N = W.size(0), M = x.numel() / K;
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K && M <= 64 && mg::gemm_rows_supported((int)M, (int)K),
+              "gemm_rows: 1 <= M <= 64, K % 8 == 0, K <= 8192");
+  if (ldy <= 0) ldy = N;
+  TORCH_CHECK(ldy >= N && epi >= 0 && epi <= 3, "gemm_rows: ldy / epi");
+  if (bias.has_value()) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N); }
+  if (epi == 3) {
+    TORCH_CHECK(resid.has_value(), "gemm_rows: residual epilogue needs resid");
+    CHECK_BF16(*resid); CHECK_CONTIG(*resid);
+    TORCH_CHECK(resid->numel() == M * ldy, "gemm_rows: resid shape");
+  }
+  DevGuard g(x.device());
+  auto y = at::empty({M, ldy}, x.options());
+  mg::gemm_rows(bp(x), bp(W), bp(y), (int)M, (int)N, (int)K, ldy, bias.has_value() ? bp(*bias) : nullptr,
+                epi == 3 ? bp(*resid) : nullptr, (int)epi, cur_stream());
+  return y;
+}
+
 // pos_dev (int32 [1] on the device, optional): the position is read by the kernel (hipGraph decode);
 // with pos_stride 1 it is int32 [B], one position per row (ragged batches)
 // part / counters (optional): the decode state's own workspace (kernels.h); without them a
@@ -1129,6 +1153,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_argmax_groups", [](int64_t N, int64_t B) { return (int64_t)mg::gemv_grid((int)N, (int)B); },
         py::arg("N"), py::arg("B"));
   m.def("gemv_supported", &mg::gemv_supported);
+  m.def("gemm_rows", &gemm_rows, py::arg("x"), py::arg("W"), py::arg("epi"), py::arg("bias") = py::none(),
+        py::arg("resid") = py::none(), py::arg("ldy") = 0);
+  m.def("gemm_rows_supported", &mg::gemm_rows_supported);
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);

@@ -83,6 +83,19 @@ int gemv_grid(int N, int B);  // workgroups of gemv() for N outputs at B rows (a
 void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long ldy, const bf16_t* bias,
           const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw = nullptr,
           const bf16_t* lnb = nullptr, float eps = 1e-5f, const GemvArgmax* am = nullptr);
+bool gemv_nt_weights();  // weight loads non-temporal (default) or cached (MINGPT_GEMV_NT=0); gemv.hip
+
+// gemm_rows.hip (decode-time rows GEMM on MFMA: y[M, ldy] = epi(x[M, K] @ W[N, K]^T); the decode
+// loops use it at 9..64 rows).  gemm_rows_supported: 1 <= M <= 64, K % 8 == 0, K <= 8192; any
+// N >= 1, ldy >= N.  bf16 in and out, fp32 accumulation, one rounding to bf16 per element; epi as
+// gemv's (0 none, 1 bias, 2 bias + GELU, 3 bias + residual; resid [M, ldy]), applied in gemv's order
+// without dropout.  Contract: the bits of y[m, :] depend on x[m, :], W, bias, resid[m, :], epi, N
+// and K only -- not on M, on which of the 64 slots the row sits in, or on the other rows' contents
+// (NaN included); a pure function of the inputs, the same in a captured graph and eagerly.  Nothing
+// is read past x + M * K or W + N * K; columns N .. ldy-1 of y are left untouched.
+bool gemm_rows_supported(int M, int K);
+void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K, long ldy, const bf16_t* bias,
+               const bf16_t* resid, int epi, hipStream_t stream);
 
 // sample.hip -- one sampled token per row of bf16 logits [B, ld] (columns >= V never read; ld % 8
 // == 0, rows 16-byte aligned): exact top-k + Gumbel-max, the rule in common.h.  params (device,

@@ -67,6 +67,7 @@ accept kernel -- is the loop ``("spec", K)`` (``_GpuCache.spec``).  The CPU path
 from __future__ import annotations
 
 import gc
+import os
 import struct
 from typing import Optional
 
@@ -178,6 +179,9 @@ def _capture(fn):
 
 
 _GRAPH_DECODE = True  # set False to launch the decode step eagerly
+# decode steps of 9..64 rows run their projections on the rows GEMM (gemm_rows.hip); False
+# (MINGPT_ROWS_GEMM=0) sends them to the MFMA GEMM as more than 64 rows go
+_ROWS_GEMM = os.environ.get("MINGPT_ROWS_GEMM", "1") != "0"
 
 
 class _Loop:
@@ -254,44 +258,53 @@ class _GpuCache:
         self.C, self.G, self.bf, self.model = ext(), G, bf16_weights(model), model
         return self
 
-    def _lin(self, skinny, inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
-        """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first (fused into
-        the skinny GEMM's staging at decode time)."""
+    def _lin(self, route, inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
+        """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first, on the GEMM that
+        ``route`` names: ``"gemv"`` the skinny GEMM (gemv.hip, up to 8 decode rows; the LayerNorm is
+        fused into its staging, and ``am`` fuses the LM head's greedy argmax), ``"rows"`` the rows GEMM
+        (gemm_rows.hip, 9..64 decode rows) and ``"mfma"`` the MFMA GEMM (gemm.hip), both behind a
+        LayerNorm launch."""
         C, G, bf = self.C, self.G, self.bf
         eps = self.model.config.layer_norm_eps
-        if skinny:
-            code = {"none": 0, "bias": 1, "gelu": 2, "resid": 3}[epi]
+        if route not in ("gemv", "rows", "mfma"):
+            raise ValueError(f"unknown GEMM route {route!r}")
+        if am is not None and route != "gemv":
+            raise ValueError("the fused argmax is the skinny GEMM's")
+        code = {"none": 0, "bias": 1, "gelu": 2, "resid": 3}[epi]
+        if route == "gemv":
             lw, lb = (bf(ln.weight), bf(ln.bias)) if ln is not None else (None, None)
             if am is not None:
                 return C.gemv(inp, bf(w), code, None, None, ld, lw, lb, eps, am[0], am[1])
             return C.gemv(inp, bf(w), code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
         if ln is not None:
             inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
+        if route == "rows":
+            return C.gemm_rows(inp, bf(w), code, bf(b) if b is not None else None, resid, ld)
         if epi == "gelu":
             pre = torch.empty((inp.shape[0], w.shape[0]), dtype=torch.bfloat16, device=inp.device)
             return G.gemm_nt(inp, bf(w), bias=bf(b), epi="gelu", pre_out=pre)
         return G.gemm_nt(inp, bf(w), bias=bf(b) if b is not None else None, epi=epi, resid=resid,
                          ld=ld or None)
 
-    def _blocks(self, x, attend, skinny):
+    def _blocks(self, x, attend, route):
         """The transformer blocks on rows x [M, D]; ``attend(i, qkv)`` is layer i's attention on its
-        qkv projection [M, 3D], cache update included.  ``skinny``: the projections go through
-        the skinny GEMM (gemv.hip) instead of the MFMA GEMM."""
+        qkv projection [M, 3D], cache update included.  ``route``: the GEMM the projections go
+        through (``_lin``)."""
         for i, blk in enumerate(self.model.transformer.h):
             a, mm = blk.attn, blk.mlp
-            qkv = self._lin(skinny, x, a.c_attn.weight, a.c_attn.bias, "bias", ln=blk.ln_1)
+            qkv = self._lin(route, x, a.c_attn.weight, a.c_attn.bias, "bias", ln=blk.ln_1)
             y = attend(i, qkv)
-            x = self._lin(skinny, y, a.c_proj.weight, a.c_proj.bias, "resid", resid=x)
-            u = self._lin(skinny, x, mm.c_fc.weight, mm.c_fc.bias, "gelu", ln=blk.ln_2)
-            x = self._lin(skinny, u, mm.c_proj.weight, mm.c_proj.bias, "resid", resid=x)
+            x = self._lin(route, y, a.c_proj.weight, a.c_proj.bias, "resid", resid=x)
+            u = self._lin(route, x, mm.c_fc.weight, mm.c_fc.bias, "gelu", ln=blk.ln_2)
+            x = self._lin(route, u, mm.c_proj.weight, mm.c_proj.bias, "resid", resid=x)
         return x
 
-    def _head(self, x_last, skinny, am=None):
+    def _head(self, x_last, route, am=None):
         """ln_f and the LM head on x_last [B, D]: logits [B, ld], ld = V rounded up to 8 (the
         columns from V on are padding).  ``am`` = (part, pos): see ``_decode``."""
         m = self.model
         V = m.config.vocab_size
-        return self._lin(skinny, x_last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8,
+        return self._lin(route, x_last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8,
                          ln=m.transformer.ln_f, am=am)
 
     def _prompt(self, idx, keep=True):
@@ -310,7 +323,7 @@ class _GpuCache:
                 self.caches[i].view(B, -1, self.tmax, 3 * D)[:, :, :T].copy_(qkv.view(B, 1, T, 3 * D))
             return C.attention_fwd(qkv, B, T, H, 0.0, 0)[0]
 
-        return self._blocks(x, attend, False).view(B, T, D)
+        return self._blocks(x, attend, "mfma").view(B, T, D)
 
     def prefill(self, idx, last=None):
         """Run the prompt idx [B, T] on the MFMA GEMM path, keep every layer's qkv rows as the
@@ -323,7 +336,7 @@ class _GpuCache:
             x = x[torch.arange(B, device=x.device), last]
         else:
             x = x[:, -1]
-        self.logits = self._head(x.contiguous(), False)[:, :cfg.vocab_size]
+        self.logits = self._head(x.contiguous(), "mfma")[:, :cfg.vocab_size]
         return self.logits
 
     def _decode(self, tok, pos, hpos, pos_stride=0, am_part=None, seq=None):
@@ -344,12 +357,19 @@ class _GpuCache:
         # one row tile and walks K latency-bound.  The widest row is the MLP output projection's,
         # 4 D <= 8192: every preset up to gpt2-xl (6400); the LayerNorm'ed projections and the LM
         # head have K = D <= 2048, inside the kernel's 4096 for fused LayerNorm and wide outputs
-        skinny = C.gemv_supported(B, 4 * D)
+        # 9..64 rows: the rows GEMM (gemm_rows.hip) streams each weight matrix once with the rows
+        # as MFMA operands; more rows, or _ROWS_GEMM off: the MFMA GEMM
+        if C.gemv_supported(B, 4 * D):
+            route = "gemv"
+        elif _ROWS_GEMM and B >= 9 and C.gemm_rows_supported(B, 4 * D):
+            route = "rows"
+        else:
+            route = "mfma"
         x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
                             pos_stride).view(B, D)
         x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part,
-                                                              self.dec_cnt, pos_stride), skinny)
-        return self._head(x, skinny, am=(am_part, pos) if am_part is not None else None)
+                                                              self.dec_cnt, pos_stride), route)
+        return self._head(x, route, am=(am_part, pos) if am_part is not None else None)
 
     def _fresh(self):
         st = _weight_stamp(self.model)
@@ -759,7 +779,7 @@ class _GpuCache:
         prompt (``_prompt``), and the last position's padded logits [B, ld] come back W times over,
         [B * W, ld] -- the input of the first beam step."""
         x = self._prompt(idx)[:, -1]
-        full = self._head(x.contiguous(), False)
+        full = self._head(x.contiguous(), "mfma")
         self.logits = full[:, :self.model.config.vocab_size]
         return full.repeat_interleave(W, dim=0)
 
@@ -820,8 +840,8 @@ class _GpuCache:
             x = C.embedding_fwd(st["tok"], bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, st["pos_rows"], None, None,
                                 1).view(R, D)
             x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, 0, st["pos_rows"],
-                                                                  st["part"], st["cnt"], 1, K), True)
-            logits = self._head(x, True)
+                                                                  st["part"], st["cnt"], 1, K), "gemv")
+            logits = self._head(x, "gemv")
             C.spec_argmax(logits, V, st["g"])
             C.spec_accept(st["g"], st["tok"], st["has"], K, st["pos"], st["ctl"], st["seq"], st["steps"], st["hist"])
             return logits[:, :V]
@@ -1555,6 +1575,6 @@ def score(model, idx, lengths=None):
     step = max(1, _SCORE_LOGITS_BYTES // (2 * ((V + 7) // 8 * 8)))
     for r0 in range(0, B * T, step):
         r1 = min(B * T, r0 + step)
-        c.C.logits_lse(c._head(x[r0:r1], False), V, targets[r0:r1], None, lp[r0:r1])
+        c.C.logits_lse(c._head(x[r0:r1], "mfma"), V, targets[r0:r1], None, lp[r0:r1])
     out[:, 1:] = lp.view(B, T)[:, :-1]
     return out
