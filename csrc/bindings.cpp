@@ -519,26 +519,45 @@ at::Tensor attention_bwd(const at::Tensor& qkv, const at::Tensor& out, const at:
   return dqkv;
 }
 
+// The shared arguments of the decode-time projections y[M, ldy] = epi(x[M, K] @ W[N, K]^T) (gemv.hip,
+// gemm_rows.hip): x bf16 [..., K] and W bf16 [N, K], contiguous; ldy <= 0 means N, else ldy >= N;
+// epi 0 none, 1 bias, 2 bias + GELU, 3 bias + residual, with bias bf16 [N] when given (null
+// otherwise) and resid bf16 [M, ldy] for epi 3 (null otherwise).  How many rows and how long a row
+// an op takes is that op's own check.
+struct ProjArgs {
+  int64_t M, N, K, ldy;
+  const bf16_t *bias, *resid;
+};
+
+ProjArgs proj_args(const char* op, const at::Tensor& x, const at::Tensor& W, int64_t epi,
+                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy) {
+  CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
+  TORCH_CHECK(W.dim() == 2 && W.size(0) >= 1 && W.size(1) >= 1, op, ": W [N, K]");
+  const int64_t K = W.size(1), N = W.size(0), M = x.numel() / K;
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, op, ": x [..., K] against W [N, K]");
+  if (ldy <= 0) ldy = N;
+  TORCH_CHECK(ldy >= N && epi >= 0 && epi <= 3, op, ": ldy / epi");
+  if (bias.has_value()) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N, op, ": bias size"); }
+  if (epi == 3) {
+    TORCH_CHECK(resid.has_value(), op, ": residual epilogue needs resid");
+    CHECK_BF16(*resid); CHECK_CONTIG(*resid);
+    TORCH_CHECK(resid->numel() == M * ldy, op, ": resid shape");
+  }
+  return {M, N, K, ldy, bias.has_value() ? bp(*bias) : nullptr, epi == 3 ? bp(*resid) : nullptr};
+}
+
 // y[B, ldy] (ldy >= N) = epi(x[B, K] @ W[N, K]^T): the decode-time projection (gemv.hip)
 at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10::optional<at::Tensor>& bias,
                 const c10::optional<at::Tensor>& resid, int64_t ldy, const c10::optional<at::Tensor>& lnw,
                 const c10::optional<at::Tensor>& lnb, double eps, const c10::optional<at::Tensor>& am_part,
                 const c10::optional<at::Tensor>& am_pos) {
-  CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
-  const int64_t K = W.size(1), N = W.size(0), B = x.numel() / K;
-  TORCH_CHECK(x.size(-1) == K && mg::gemv_supported((int)B, (int)K), "gemv: B <= 8, K % 8 == 0, K <= 8192");
+  const ProjArgs p = proj_args("gemv", x, W, epi, bias, resid, ldy);
+  const int64_t B = p.M, N = p.N, K = p.K;
+  TORCH_CHECK(mg::gemv_supported((int)B, (int)K), "gemv: B <= 8, K % 8 == 0, K <= 8192");
   // rows staged in two segments: the one-row-per-wave path without fused LayerNorm only
   TORCH_CHECK(K <= mg::kGemvSegK || N <= 8192, "gemv: K > 4096 needs N <= 8192 (wide outputs take K <= 4096)");
   TORCH_CHECK(K <= mg::kGemvSegK || !(lnw.has_value() || lnb.has_value()),
               "gemv: K > 4096 cannot take LayerNorm weights (the fused LayerNorm takes K <= 4096)");
-  if (ldy <= 0) ldy = N;
-  TORCH_CHECK(ldy >= N && epi >= 0 && epi <= 3, "gemv: ldy / epi");
-  if (bias.has_value()) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N); }
-  if (epi == 3) {
-    TORCH_CHECK(resid.has_value(), "gemv: residual epilogue needs resid");
-    CHECK_BF16(*resid); CHECK_CONTIG(*resid);
-    TORCH_CHECK(resid->numel() == B * ldy, "gemv: resid shape");
-  }
   TORCH_CHECK(lnw.has_value() == lnb.has_value(), "gemv: LayerNorm needs weight and bias");
   if (lnw.has_value()) {
     CHECK_BF16(*lnw); CHECK_BF16(*lnb);
@@ -558,10 +577,9 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
     am.part = reinterpret_cast<unsigned long long*>(am_part->data_ptr<int64_t>());
     am.pos = am_pos->data_ptr<int>();
   }
-  auto y = at::empty({B, ldy}, x.options());
-  mg::gemv(bp(x), bp(W), bp(y), (int)B, (int)N, (int)K, ldy, bias.has_value() ? bp(*bias) : nullptr,
-           epi == 3 ? bp(*resid) : nullptr, (int)epi, cur_stream(), bp_opt(lnw), bp_opt(lnb), (float)eps,
-           am_part.has_value() ? &am : nullptr);
+  auto y = at::empty({B, p.ldy}, x.options());
+  mg::gemv(bp(x), bp(W), bp(y), (int)B, (int)N, (int)K, p.ldy, p.bias, p.resid, (int)epi, cur_stream(), bp_opt(lnw),
+           bp_opt(lnb), (float)eps, am_part.has_value() ? &am : nullptr);
   return y;
 }
 
@@ -569,23 +587,12 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
 // past the skinny GEMM's 8 rows (gemm_rows.hip)
 at::Tensor gemm_rows(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10::optional<at::Tensor>& bias,
                      const c10::optional<at::Tensor>& resid, int64_t ldy) {
-  CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
-  TORCH_CHECK(W.dim() == 2 && W.size(0) >= 1 && W.size(1) >= 1, "gemm_rows: W [N, K]");
-  const int64_t K = W.size(1), N = W.size(0), M = x.numel() / K;
-  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K && M <= 64 && mg::gemm_rows_supported((int)M, (int)K),
+  const ProjArgs p = proj_args("gemm_rows", x, W, epi, bias, resid, ldy);
+  TORCH_CHECK(p.M <= 64 && mg::gemm_rows_supported((int)p.M, (int)p.K),
               "gemm_rows: 1 <= M <= 64, K % 8 == 0, K <= 8192");
-  if (ldy <= 0) ldy = N;
-  TORCH_CHECK(ldy >= N && epi >= 0 && epi <= 3, "gemm_rows: ldy / epi");
-  if (bias.has_value()) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N); }
-  if (epi == 3) {
-    TORCH_CHECK(resid.has_value(), "gemm_rows: residual epilogue needs resid");
-    CHECK_BF16(*resid); CHECK_CONTIG(*resid);
-    TORCH_CHECK(resid->numel() == M * ldy, "gemm_rows: resid shape");
-  }
   DevGuard g(x.device());
-  auto y = at::empty({M, ldy}, x.options());
-  mg::gemm_rows(bp(x), bp(W), bp(y), (int)M, (int)N, (int)K, ldy, bias.has_value() ? bp(*bias) : nullptr,
-                epi == 3 ? bp(*resid) : nullptr, (int)epi, cur_stream());
+  auto y = at::empty({p.M, p.ldy}, x.options());
+  mg::gemm_rows(bp(x), bp(W), bp(y), (int)p.M, (int)p.N, (int)p.K, p.ldy, p.bias, p.resid, (int)epi, cur_stream());
   return y;
 }
 

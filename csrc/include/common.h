@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define MG_DEVICE __device__ __forceinline__
 
 namespace mg {
@@ -398,7 +400,26 @@ MG_DEVICE void gelu2(f32x2 x, f32x2& y, f32x2& g) {
   g = (2.f * kGeluK0) * x * sg * (f32x2{1.f, 1.f} - sg) * ((3.f * kGeluK1) * x2 + 1.f) + sg;
 }
 
+// ---------------------------------------------------------------- decode projection epilogue
+// One output element of the decode-time projections (gemv.hip, gemm_rows.hip; kernels.h epi codes):
+// add the bias (0.f without one), GELU for epi 2, add the residual element for epi 3 (resid_elem is
+// read for epi 3 only), one rounding to bf16 -- in this order, for both kernels.
+MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* resid_elem) {
+  float v = acc + bias;
+  if (epi == 2) v = gelu_f(v);
+  if (epi == 3) v += bf2f(*resid_elem);
+  return f2bf(v);
+}
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Host: f(std::true_type{}) or f(std::false_type{}) for a run-time flag that is a template argument
+// of the kernel f launches (the decode projections' weight-load policy)
+template <class F>
+inline void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 }  // namespace mg
 

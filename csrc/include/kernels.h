@@ -88,8 +88,9 @@ bool gemv_nt_weights();  // weight loads non-temporal (default) or cached (MINGP
 // gemm_rows.hip (decode-time rows GEMM on MFMA: y[M, ldy] = epi(x[M, K] @ W[N, K]^T); the decode
 // loops use it at 9..64 rows).  gemm_rows_supported: 1 <= M <= 64, K % 8 == 0, K <= 8192; any
 // N >= 1, ldy >= N.  bf16 in and out, fp32 accumulation, one rounding to bf16 per element; epi as
-// gemv's (0 none, 1 bias, 2 bias + GELU, 3 bias + residual; resid [M, ldy]), applied in gemv's order
-// without dropout.  Contract: the bits of y[m, :] depend on x[m, :], W, bias, resid[m, :], epi, N
+// gemv's (0 none, 1 bias, 2 bias + GELU, 3 bias + residual; resid [M, ldy]), applied by the function
+// gemv applies them with (proj_epilogue, common.h), without dropout.
+// Contract: the bits of y[m, :] depend on x[m, :], W, bias, resid[m, :], epi, N
 // and K only -- not on M, on which of the 64 slots the row sits in, or on the other rows' contents
 // (NaN included); a pure function of the inputs, the same in a captured graph and eagerly.  Nothing
 // is read past x + M * K or W + N * K; columns N .. ldy-1 of y are left untouched.

@@ -17,7 +17,8 @@
 //     (at any moment the workgroup reads 256 contiguous bytes of each weight row), kRowsU (4) steps of
 //     loads requested one group ahead of the MFMAs that use them;
 //   * the 4 partial accumulators meet in LDS and are added in wave order, ((p0 + p1) + p2) + p3,
-//     then bias | bias + GELU | bias + residual as in gemv.hip (no dropout), one rounding to bf16.
+//     then gemv.hip's epilogue (proj_epilogue, common.h): bias | bias + GELU | bias + residual, no
+//     dropout, one rounding to bf16.
 // The split and the step order are functions of K alone and an MFMA computes each output row from
 // that row's operand alone, so the bits of y[m, :] depend on x[m, :], W, bias, resid[m, :], epi, N
 // and K -- not on M, the row's slot, the other rows' contents (NaN included), or graph / eager
@@ -116,12 +117,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = wid * 16 + q * 4 + i;
-        if (m < M) {
-          float v = s[i] + bv;
-          if (epi == 2) v = gelu_f(v);
-          if (epi == 3) v += bf2f(resid[(long)m * ldy + n]);
-          y[(long)m * ldy + n] = f2bf(v);
-        }
+        if (m < M) y[(long)m * ldy + n] = proj_epilogue(s[i], bv, epi, resid + (long)m * ldy + n);
       }
     }
   }
@@ -139,13 +135,18 @@ void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K,
                const bf16_t* resid, int epi, hipStream_t stream) {
   const int grid = cdiv(N, 16);
   const bool ntw = gemv_nt_weights();
-#define MG_ROWS_CASE(rt)                                                                                      \
-  case rt:                                                                                                    \
-    if (ntw) gemm_rows_kernel<rt, true><<<grid, 256, 0, stream>>>(x, W, y, M, N, K, ldy, bias, resid, epi);   \
-    else gemm_rows_kernel<rt, false><<<grid, 256, 0, stream>>>(x, W, y, M, N, K, ldy, bias, resid, epi);      \
-    break;
+  // the one launch: the row tiles and the weight-load policy pick the instantiation
+  auto launch = [&](auto rt) {
+    dispatch_bool(ntw, [&](auto nt) {
+      gemm_rows_kernel<decltype(rt)::value, decltype(nt)::value><<<grid, 256, 0, stream>>>(x, W, y, M, N, K, ldy,
+                                                                                           bias, resid, epi);
+    });
+  };
   switch (cdiv(M, 16)) {  // row tiles: rows past M are zero operands, never stored
-    MG_ROWS_CASE(1) MG_ROWS_CASE(2) MG_ROWS_CASE(3) MG_ROWS_CASE(4)
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
     default:  // the caller checks gemm_rows_supported: nothing is launched, y is left as it was
 #ifdef MG_DEBUG
       fprintf(stderr, "gemm_rows: M = %d outside 1..%d\n", M, kRowsMaxM);
@@ -153,7 +154,6 @@ void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K,
 #endif
       break;
   }
-#undef MG_ROWS_CASE
 }
 
 }  // namespace mg

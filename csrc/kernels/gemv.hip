@@ -1,27 +1,31 @@
 // Skinny GEMM ("GEMV") for autoregressive decode on gfx950.
 //
-// One decode step pushes B <= 8 rows through every projection of the model
-// (/root/reference/mingpt/model.py:322-356 re-runs the whole prefix instead; the KV-cache path in
-// models/generation.py needs only the new token's rows).  At M = B the MFMA GEMM has 1 row tile:
+// One decode step pushes B <= 8 rows through every projection of the model (the reference's
+// generate() re-runs the whole prefix instead; the KV-cache path in models/generation.py needs only
+// the new token's rows).  At M = B the MFMA GEMM has 1 row tile:
 // 6-24 workgroups walk a K loop one tile at a time and the projection is latency-bound
 // (26 us for the 3072 -> 768 MLP projection at B = 1).  The work is a stream of the weight
 // matrix (K x N bf16, read once) against B vectors that fit in LDS, so here:
 //   * x [B, K] is staged once per workgroup in LDS -- optionally LayerNorm'ed on the way in (the
 //     LN that precedes every decode projection but the residual ones; one kernel instead of two);
 //     rows of 4096 < K <= 8192 (the MLP output projection of gpt2-large / -xl) go through the
-//     same 64 KiB buffer in two segments (gemv_kernel's KMAX);
+//     same 64 KiB buffer in two segments;
 //   * a wave owns one output column n (outputs <= 8k: every block projection) or 4 (the LM head):
 //     its 64 (or 16) lanes read row n = W[n, :] in 16-byte chunks, 4 loads in flight per lane,
-//     FMA against the B vectors from LDS;
+//     FMA against the B vectors from LDS (gemv_fma: the one chain every path runs);
 //   * the lanes of a row fold with xor-shuffles; the row's first lane writes y[b, n] with the same
 //     fused epilogues as gemm.hip's forward (bias | bias + GELU | residual + bias), no dropout
-//     (inference);
+//     (inference): proj_epilogue, common.h;
 //   * weights are read non-temporally (streamed once per token; MI355X_MICROARCH launches-baseline:
 //     nt weight loads ~11 % faster per decode layer);
 //   * greedy decode (LM head): the argmax of the logits is fused -- each workgroup publishes its
 //     best (value, index) key and the next decode step's embedding kernel reduces them into the
 //     token (and advances the device position), so a captured decode step can be replayed back
 //     to back with no host round trip per token.
+// gemv_kernel<B, LPR, NTW, KMAX> is one of three paths, each a block of the kernel's body:
+//   LPR 64, KMAX kGemvSegK  one column per wave          N <= 8192, K <= 4096
+//   LPR 64, KMAX kGemvMaxK  long rows in segments        N <= 8192, 4096 < K <= 8192
+//   LPR 16                  wide, grid-strided + argmax  N > 8192 (K <= 4096)
 #include "common.h"
 #include "kernels.h"
 
@@ -56,16 +60,28 @@ MG_DEVICE void gemv_argmax(const GemvArgmax& am, const unsigned long long (&key)
   if (blockIdx.x == 0 && threadIdx.x == 0) *am.pos += 1;  // nothing else in this kernel reads it
 }
 
-// KMAX: the longest row an instantiation takes.  kGemvSegK: x is staged whole, [B][K].  kGemvMaxK
-// (one row per wave only; launched for K > kGemvSegK): the whole weight row is still requested up
-// front (16 chunks per lane), x goes through the LDS buffer in segments of kGemvSegK columns,
-// [B][kGemvSegK], with a workgroup barrier between segments -- segment s + 1's weight chunks and
-// its x chunks are in flight (or already in registers) while segment s is multiplied.  Chosen over
-// whole-row staging (B x 8192 x 2 B = 128 KiB: an opt-in above the 64 KiB dynamic-LDS default and
-// one workgroup per CU): 64 KiB keeps two workgroups on a CU, so the 320 / 400 workgroups of the
-// gpt2-large / -xl MLP projection are all resident on the 256 CUs at once instead of running as
-// one full round and a part-filled second.  A lane's sum is the same chain either way: chunks
-// u = 0, 1, ... in order, 8 fmas each, then the xor fold.
+// The FMA chain of one 8-column chunk: weight chunk w against the B staged rows' chunks at xcol,
+// xcol + ldx, ...  A lane's sum is this chain over its chunks in ascending column order (e = 0..7
+// within a chunk, rows inner), whichever path runs it: tests/_gemv_oracle.py restates it.
+template <int B>
+MG_DEVICE void gemv_fma(const uint4& w, const bf16_t* xcol, int ldx, float (&acc)[B]) {
+  float wf[8];
+  unpack8(w, wf);
+#pragma unroll
+  for (int b = 0; b < B; ++b) {
+    float xf[8];
+    unpack8(ld16(xcol + b * ldx), xf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[b] = __builtin_fmaf(wf[e], xf[e], acc[b]);
+  }
+}
+
+// KMAX: the longest row an instantiation takes (kGemvMaxK: one column per wave only); LPR: lanes per
+// output row.  The body is: request the weight row (one column per wave), stage x, then one of
+// the three paths.  The paths are blocks of this body and the LayerNorm passes a lambda in it, not
+// device functions beside gemv_fma: -ffp-contract leaves to the compiler which of the LayerNorm's
+// squares fuse with their add, and that choice -- the staged bits -- changed for some B whenever
+// this code was compiled from inside another function (PERF.md 'Decode projections refactor').
 template <int B, int LPR, bool NTW, int KMAX = kGemvSegK>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ W,
@@ -75,7 +91,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ lnw,
                                                    const bf16_t* __restrict__ lnb, float eps,
                                                    const GemvArgmax am) {
-  extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [B][K]; LONGK: [B][kGemvSegK]
+  extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [B][K]; long rows: [B][kGemvSegK]
   constexpr bool LONGK = KMAX > kGemvSegK;
   static_assert(!LONGK || LPR == 64, "rows longer than kGemvSegK: one row per wave only");
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -97,98 +113,76 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
   }
   if (!LONGK && lnw) {  // (LONGK: no fused LayerNorm -- a LayerNorm'ed row is at most 4096 wide)
     // fused LayerNorm of the B input rows (wave w normalises rows w, w+4): the same lane/chunk
-    // order and wave reduction as ln_fwd_kernel, so the staged bf16 rows equal its output
-    // K <= 1024 (GPT-2 small / medium): the row, gamma and beta chunks are loaded once into
-    // registers (one memory round trip instead of three dependent L2 reads); wider rows re-read
-    if (K <= 1024) {
+    // order and wave reduction as ln_fwd_kernel, so the staged bf16 rows equal its output.  Three
+    // passes over a lane's chunks c = 8 lane + 512 u (sum, sum of squares, write), written once
+    // over how a chunk is obtained.  HELD = 2 (K <= 1024: GPT-2 small / medium): the row, gamma and
+    // beta chunks are loaded once into registers (one memory round trip instead of three dependent
+    // L2 reads), zero past K; HELD = 0 (wider rows): every pass re-reads its chunks
+    auto stage_ln = [&](auto held) {
+      constexpr int HELD = decltype(held)::value;
       for (int b = wid; b < B; b += 4) {
         const bf16_t* xr = x + (long)b * K;
-        uint4 xv[2], wv[2], bv[2];
+        constexpr int NH = HELD ? HELD : 1;
+        uint4 xv[NH], wv[NH], bv[NH];
+        if constexpr (HELD > 0) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int c = lane * 8 + u * 512;
-          const bool ok = c < K;
-          xv[u] = ok ? ld16(xr + c) : make_uint4(0, 0, 0, 0);
-          wv[u] = ok ? ld16(lnw + c) : make_uint4(0, 0, 0, 0);
-          bv[u] = ok ? ld16(lnb + c) : make_uint4(0, 0, 0, 0);
+          for (int u = 0; u < HELD; ++u) {
+            const int c = lane * 8 + u * 512;
+            const bool ok = c < K;
+            xv[u] = ok ? ld16(xr + c) : make_uint4(0, 0, 0, 0);
+            wv[u] = ok ? ld16(lnw + c) : make_uint4(0, 0, 0, 0);
+            bv[u] = ok ? ld16(lnb + c) : make_uint4(0, 0, 0, 0);
+          }
         }
-        float s = 0.f;
+        auto each = [&](auto&& f) {  // f(u, c) for the lane's chunks; HELD: the zero ones past K too
+          if constexpr (HELD > 0) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
+            for (int u = 0; u < HELD; ++u) f(u, lane * 8 + u * 512);
+          } else {
+            for (int c = lane * 8; c < K; c += 512) f(0, c);
+          }
+        };
+        float s = 0.f;
+        each([&](int u, int c) {
           float v[8];
-          unpack8(xv[u], v);
+          unpack8(HELD ? xv[u] : ld16(xr + c), v);
 #pragma unroll
           for (int e = 0; e < 8; ++e) s += v[e];  // zero chunks past K add nothing
-        }
+        });
         const float mu = wave_sum(s) / K;
         float ss = 0.f;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          if (lane * 8 + u * 512 < K) {
+        each([&](int u, int c) {
+          if (c < K) {
             float v[8];
-            unpack8(xv[u], v);
+            unpack8(HELD ? xv[u] : ld16(xr + c), v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               const float d = v[e] - mu;
               ss += d * d;
             }
           }
-        }
+        });
         const float rs = rsqrtf(wave_sum(ss) / K + eps);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int c = lane * 8 + u * 512;
+        each([&](int u, int c) {
           if (c < K) {
             float v[8], wf[8], bf[8], o[8];
-            unpack8(xv[u], v);
-            unpack8(wv[u], wf);
-            unpack8(bv[u], bf);
+            unpack8(HELD ? xv[u] : ld16(xr + c), v);
+            unpack8(HELD ? wv[u] : ld16(lnw + c), wf);
+            unpack8(HELD ? bv[u] : ld16(lnb + c), bf);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (v[e] - mu) * rs * wf[e] + bf[e];
             st16(xs + b * K + c, pack8(o));
           }
-        }
+        });
       }
-    } else {
-    for (int b = wid; b < B; b += 4) {
-      const bf16_t* xr = x + (long)b * K;
-      float s = 0.f;
-      for (int c = lane * 8; c < K; c += 512) {
-        float v[8];
-        unpack8(ld16(xr + c), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e];
-      }
-      const float mu = wave_sum(s) / K;
-      float ss = 0.f;
-      for (int c = lane * 8; c < K; c += 512) {
-        float v[8];
-        unpack8(ld16(xr + c), v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = v[e] - mu;
-          ss += d * d;
-        }
-      }
-      const float rs = rsqrtf(wave_sum(ss) / K + eps);
-      for (int c = lane * 8; c < K; c += 512) {
-        float v[8], wf[8], bf[8], o[8];
-        unpack8(ld16(xr + c), v);
-        unpack8(ld16(lnw + c), wf);
-        unpack8(ld16(lnb + c), bf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[e] - mu) * rs * wf[e] + bf[e];
-        st16(xs + b * K + c, pack8(o));
-      }
-    }
-    }
+    };
+    if (K <= 1024) stage_ln(std::integral_constant<int, 2>{});
+    else stage_ln(std::integral_constant<int, 0>{});
   } else if constexpr (!LONGK) {
     for (int i = threadIdx.x * 8; i < B * K; i += 256 * 8) st16(xs + i, ld16(x + i));
   }
   if constexpr (!LONGK) __syncthreads();
-  // LPR lanes per output row: 16 (4 rows per wave) for wide outputs (the LM head), 64 (one row per
-  // wave, the whole row's loads in flight at once) for the block projections, whose 48-192
-  // workgroups at 16 lanes per row left most of the chip idle and the HBM latency exposed
+  // a row's LPR lanes fold with xor-shuffles; lane j == 0 applies the epilogue and writes y[b, n]
   auto epilogue = [&](float (&acc)[B], int n) {
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -199,10 +193,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
       const float bv = bias ? bf2f(bias[n]) : 0.f;
 #pragma unroll
       for (int b = 0; b < B; ++b) {
-        float v = acc[b] + bv;
-        if (epi == 2) v = gelu_f(v);
-        if (epi == 3) v += bf2f(resid[(long)b * ldy + n]);
-        const bf16_t o = f2bf(v);
+        const bf16_t o = proj_epilogue(acc[b], bv, epi, resid + (long)b * ldy + n);
         y[(long)b * ldy + n] = o;
         acc[b] = bf2f(o);  // the argmax ranks the stored (bf16) logits
       }
@@ -212,6 +203,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
   for (int b = 0; b < B; ++b) acc[b] = 0.f;
   if constexpr (LONGK) {
+    // ---- long rows in segments: kGemvSegK < K <= kGemvMaxK, one column per wave.  The whole weight
+    // row was requested up front (16 chunks per lane); x goes through the LDS buffer in segments of
+    // kGemvSegK columns, [B][kGemvSegK], with a workgroup barrier between segments -- segment s + 1's
+    // weight chunks and its x chunks are in flight (or already in registers) while segment s is
+    // multiplied.  Chosen over whole-row staging (B x 8192 x 2 B = 128 KiB: an opt-in above the
+    // 64 KiB dynamic-LDS default and one workgroup per CU): 64 KiB keeps two workgroups on a CU, so
+    // the 320 / 400 workgroups of the gpt2-large / -xl MLP projection are all resident on the 256
+    // CUs at once instead of running as one full round and a part-filled second.  A lane's sum is
+    // the same chain either way: chunks u = 0, 1, ... in order, 8 fmas each, then the xor fold.
     constexpr int UPS = kGemvSegK / STRIDE;  // weight chunks per lane and segment
     constexpr int CPT = kGemvSegK / (256 * 8);  // x chunks per thread, row and segment
     constexpr int NSEG = KMAX / kGemvSegK;
@@ -245,41 +245,27 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
         for (int u = s * UPS; u < (s + 1) * UPS; ++u) {
           const int c = j * 8 + u * STRIDE;
-          if (c < K) {
-            float wf[8];
-            unpack8(wpf[u], wf);
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-              float xf[8];
-              unpack8(ld16(xs + b * kGemvSegK + c - s0), xf);
-#pragma unroll
-              for (int e = 0; e < 8; ++e) acc[b] = __builtin_fmaf(wf[e], xf[e], acc[b]);
-            }
-          }
+          if (c < K) gemv_fma<B>(wpf[u], xs + c - s0, kGemvSegK, acc);
         }
       }
     }
     epilogue(acc, n);
   } else if constexpr (LPR == 64) {
+    // ---- one column per wave: the block projections (N <= 8192, K <= kGemvSegK), N / 4 workgroups,
+    // a wave's 64 lanes on one column with the whole row's loads in flight at once.  (16 lanes per
+    // row, the wide path's layout, left most of the chip idle at these 48-192 workgroups and the
+    // HBM latency exposed.)
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int c = j * 8 + u * STRIDE;
-      if (c < K) {
-        float wf[8];
-        unpack8(wpf[u], wf);
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          float xf[8];
-          unpack8(ld16(xs + b * K + c), xf);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[b] = __builtin_fmaf(wf[e], xf[e], acc[b]);
-        }
-      }
+      if (c < K) gemv_fma<B>(wpf[u], xs + c, K, acc);
     }
     epilogue(acc, n);
   } else {
-    // wide outputs: grid-stride over 16-row blocks (a few hundred workgroups stage x once each;
-    // the fused argmax then pays its cross-workgroup hand-off once per workgroup)
+    // ---- wide, grid-strided, with the fused argmax: N > 8192 (the LM head), 16 lanes per output
+    // row and 4 rows per wave; a grid of a few hundred workgroups (gemv_grid) strides over the
+    // 16-row blocks, each staging x once, and the fused argmax pays its cross-workgroup hand-off
+    // once per workgroup
     unsigned long long best[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) best[b] = 0ull;
@@ -312,17 +298,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int c = seg * 1024 + j * 8 + u * STRIDE;
-        if (c < K) {
-          float wf[8];
-          unpack8(cur[u], wf);
-#pragma unroll
-          for (int b = 0; b < B; ++b) {
-            float xf[8];
-            unpack8(ld16(xs + b * K + c), xf);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[b] = __builtin_fmaf(wf[e], xf[e], acc[b]);
-          }
-        }
+        if (c < K) gemv_fma<B>(cur[u], xs + c, K, acc);
       }
       if (seg == nseg - 1) {
         epilogue(acc, nr);
@@ -345,23 +321,16 @@ namespace mg {
 // K > kGemvSegK: narrow outputs (N <= 8192) without fused LayerNorm only (the bindings check)
 bool gemv_supported(int B, int K) { return B >= 1 && B <= kGemvMaxB && K % 8 == 0 && K <= kGemvMaxK; }
 
-// wide outputs: a few workgroups per CU, grid-striding over the 16-row blocks
-int gemv_wide_cap() {
-  static int cap = 0;
-  if (!cap) {
-    const char* e = getenv("MINGPT_GEMV_WIDE_GRID");
-    cap = e ? atoi(e) : 512;
-    if (cap <= 0) cap = 512;
-  }
-  return cap;
-}
+// wide outputs: a few workgroups per CU, grid-striding over the 16-row blocks -- at most
+// MINGPT_GEMV_WIDE_GRID (default 512) of them when the variable is set or B > 2, else 1024
 // (B <= 2: twice the workgroups -- the LM head's 16-row blocks are then latency-, not
 // bandwidth-bound: 3,359 / 3,335 vs 3,319 / 3,302 tok/s at B = 1, equal at B = 8;
 // profiles/round2_s8_decode_gemv_policy_ab.jsonl)
 int gemv_grid(int N, int B) {
   if (N <= 8192) return cdiv(N, 4);
-  const char* e = getenv("MINGPT_GEMV_WIDE_GRID");
-  return min(cdiv(N, 16), (e || B > 2) ? gemv_wide_cap() : 1024);
+  static const char* const env = getenv("MINGPT_GEMV_WIDE_GRID");
+  static const int cap = env && atoi(env) > 0 ? atoi(env) : 512;
+  return min(cdiv(N, 16), (env || B > 2) ? cap : 1024);
 }
 // weight loads non-temporal (default) or default cache policy (MINGPT_GEMV_NT=0): the decode step
 // re-reads the same ~250 MB of GPT-2 weights every token, about the Infinity Cache's size
@@ -373,7 +342,6 @@ bool gemv_nt_weights() {
   }
   return nt != 0;
 }
-// argmax partials: one 8-byte key per (row, workgroup)
 
 void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long ldy, const bf16_t* bias,
           const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw, const bf16_t* lnb,
@@ -385,31 +353,29 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
   const bool wide = N > 8192;
   const int grid = gemv_grid(N, B);
   const GemvArgmax amv = am ? *am : GemvArgmax{nullptr, nullptr};
-  const bool ntw = gemv_nt_weights();
-#define MG_GEMV_LAUNCH(b, lpr)                                                                                        \
-  if (ntw) gemv_kernel<b, lpr, true><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv); \
-  else gemv_kernel<b, lpr, false><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv);
-#define MG_GEMV_LAUNCH_LONG(b)                                                                                         \
-  if (ntw) gemv_kernel<b, 64, true, kGemvMaxK><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, nullptr, nullptr, eps, amv); \
-  else gemv_kernel<b, 64, false, kGemvMaxK><<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, nullptr, nullptr, eps, amv);
-#define MG_GEMV_CASE(b)        \
-  case b:                      \
-    if (longk) {               \
-      MG_GEMV_LAUNCH_LONG(b)   \
-    } else if (wide) {         \
-      MG_GEMV_LAUNCH(b, 16)    \
-    } else {                   \
-      MG_GEMV_LAUNCH(b, 64)    \
-    }                          \
-    break;
+  // the one launch: B, the path (LPR, KMAX) and the weight-load policy pick the instantiation
+  auto launch = [&](auto b, auto lpr, auto kmax) {
+    dispatch_bool(gemv_nt_weights(), [&](auto nt) {
+      gemv_kernel<decltype(b)::value, decltype(lpr)::value, decltype(nt)::value, decltype(kmax)::value>
+          <<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv);
+    });
+  };
+  auto rows = [&](auto b) {
+    if (longk) launch(b, std::integral_constant<int, 64>{}, std::integral_constant<int, kGemvMaxK>{});
+    else if (wide) launch(b, std::integral_constant<int, 16>{}, std::integral_constant<int, kGemvSegK>{});
+    else launch(b, std::integral_constant<int, 64>{}, std::integral_constant<int, kGemvSegK>{});
+  };
   switch (B) {  // exact row counts: the kernel stages and writes exactly B rows
-    MG_GEMV_CASE(1) MG_GEMV_CASE(2) MG_GEMV_CASE(3) MG_GEMV_CASE(4)
-    MG_GEMV_CASE(5) MG_GEMV_CASE(6) MG_GEMV_CASE(7) MG_GEMV_CASE(8)
+    case 1: rows(std::integral_constant<int, 1>{}); break;
+    case 2: rows(std::integral_constant<int, 2>{}); break;
+    case 3: rows(std::integral_constant<int, 3>{}); break;
+    case 4: rows(std::integral_constant<int, 4>{}); break;
+    case 5: rows(std::integral_constant<int, 5>{}); break;
+    case 6: rows(std::integral_constant<int, 6>{}); break;
+    case 7: rows(std::integral_constant<int, 7>{}); break;
+    case 8: rows(std::integral_constant<int, 8>{}); break;
     default: break;
   }
-#undef MG_GEMV_CASE
-#undef MG_GEMV_LAUNCH_LONG
-#undef MG_GEMV_LAUNCH
 }
 
 }  // namespace mg

@@ -258,6 +258,21 @@ class _GpuCache:
         self.C, self.G, self.bf, self.model = ext(), G, bf16_weights(model), model
         return self
 
+    def _route(self, rows):
+        """The GEMM a decode step of ``rows`` rows runs its projections on (``_lin``'s names).
+        Up to 8 rows go through the skinny GEMM (gemv.hip): at M = rows the MFMA GEMM has one row
+        tile and walks K latency-bound.  The widest row is the MLP output projection's, 4 D <=
+        8192: every preset up to gpt2-xl (6400); the LayerNorm'ed projections and the LM head have
+        K = D <= 2048, inside the kernel's 4096 for fused LayerNorm and wide outputs.  9..64 rows:
+        the rows GEMM (gemm_rows.hip) streams each weight matrix once with the rows as MFMA
+        operands; more rows, a wider model, or ``_ROWS_GEMM`` off: the MFMA GEMM."""
+        K = 4 * self.model.config.n_embed
+        if self.C.gemv_supported(rows, K):
+            return "gemv"
+        if _ROWS_GEMM and rows >= 9 and self.C.gemm_rows_supported(rows, K):
+            return "rows"
+        return "mfma"
+
     def _lin(self, route, inp, w, b, epi, resid=None, ld=0, ln=None, am=None):
         """epi(LN(inp) @ w^T + b) with ``ln`` = a LayerNorm module applied first, on the GEMM that
         ``route`` names: ``"gemv"`` the skinny GEMM (gemv.hip, up to 8 decode rows; the LayerNorm is
@@ -353,18 +368,7 @@ class _GpuCache:
         C, bf = self.C, self.bf
         tr, cfg = self.model.transformer, self.model.config
         B, D, H = tok.shape[0], cfg.n_embed, cfg.n_head
-        # decode rows (B <= 8) go through the skinny GEMM (gemv.hip): at M = B the MFMA GEMM has
-        # one row tile and walks K latency-bound.  The widest row is the MLP output projection's,
-        # 4 D <= 8192: every preset up to gpt2-xl (6400); the LayerNorm'ed projections and the LM
-        # head have K = D <= 2048, inside the kernel's 4096 for fused LayerNorm and wide outputs
-        # 9..64 rows: the rows GEMM (gemm_rows.hip) streams each weight matrix once with the rows
-        # as MFMA operands; more rows, or _ROWS_GEMM off: the MFMA GEMM
-        if C.gemv_supported(B, 4 * D):
-            route = "gemv"
-        elif _ROWS_GEMM and B >= 9 and C.gemm_rows_supported(B, 4 * D):
-            route = "rows"
-        else:
-            route = "mfma"
+        route = self._route(B)
         x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
                             pos_stride).view(B, D)
         x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part,
@@ -542,7 +546,7 @@ class _GpuCache:
 
         def make():
             dev = tok.device
-            fused = self.C.gemv_supported(B, 4 * cfg.n_embed) and V > 8192
+            fused = self._route(B) == "gemv" and V > 8192
             st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
                   "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
                   "part": (torch.zeros(B, self.C.gemv_argmax_groups(V, B), dtype=torch.long, device=dev)
@@ -832,7 +836,7 @@ class _GpuCache:
         tr, cfg = self.model.transformer, self.model.config
         D, H, V = cfg.n_embed, cfg.n_head, cfg.vocab_size
         R = self.B * K
-        if not C.gemv_supported(R, 4 * D):  # R <= 8 rows of at most 8192 columns (gemv.hip)
+        if self._route(R) != "gemv":  # R <= 8 rows of at most 8192 columns (gemv.hip)
             raise RuntimeError(f"speculative decoding: {R} rows of width {4 * D} do not fit the skinny GEMM")
 
         def step():

@@ -24,5 +24,6 @@ for blk in re.split(r"\n  - ", meta)[1:]:
     g = lambda k: (re.search(rf"\.{k}:\s+(\d+)", blk) or [None, "?"])[1]
     body = bodies.get(name.group(1), "")
     counts = " ".join(f"{c}={body.count(c)}" for c in cnt)
-    print(f"{name.group(1)[18:88]:70s} vgpr={g('vgpr_count')} agpr={g('agpr_count')} "
-          f"spill={g('vgpr_spill_count')} | {counts}")
+    print(f"{name.group(1)[18:88]:70s} vgpr={g('vgpr_count')} agpr={g('agpr_count')} sgpr={g('sgpr_count')} "
+          f"spill={g('vgpr_spill_count')} priv={g('private_segment_fixed_size')} "
+          f"lds={g('group_segment_fixed_size')} | {counts}")

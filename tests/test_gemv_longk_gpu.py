@@ -8,10 +8,15 @@ kernel took before as well (which pins the restatement to the kernel) and at the
 tolerance (atol 2e-2, rtol 2e-2).  The inputs and the lane sums of a shape are computed once and
 shared by the tests of that shape.
 
+The wide path (N > 8192: 16 lanes per output column, a capped grid striding over 16-column blocks) is
+pinned the same way against the restatement at 16 lanes, and its fused argmax against the first
+index of the maximum of the stored row.
+
 The binding allocates y itself, so sentinel margins cannot be put around it.  Stores next to y are
 looked for in two ways instead: ``guarded`` (NaN margins around every input; the residual is one) and
 a y that lands on a block just filled with the sentinel, whose pad columns N..ldy-1 must keep it."""
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -32,6 +37,11 @@ NEW_SHAPES = [(1, 1280, 5120),   # gpt2-large
               (5, 23, 4104),     # one chunk over a segment, K no multiple of 512, N no multiple of 4
               (2, 7, 4608),      # a segment and one full round of the 64 lanes
               (8, 8192, 5120)]   # the last N on the one-column-per-wave path
+WIDE_SHAPES = [(3, 8200, 64),     # 513 column blocks on a grid capped at 512: one workgroup strides to a second
+               (1, 16400, 64),    # the B <= 2 cap of 1024, with a second item; N no multiple of 16
+               (8, 8208, 1032),   # two K segments, the second holding a single chunk
+               (5, 8193, 4096)]   # the longest row of the wide path; one column in the last block
+_I64_MIN = -(1 << 63)
 
 
 def _bf(*shape, scale=1.0, seed=0):
@@ -48,7 +58,8 @@ def _case(B, N, K):
     """Inputs on the device (left unchanged) and the folded lane sums of the restatement."""
     x, w = _bf(B, K, seed=K + B), _bf(N, K, scale=0.05, seed=K + N + 1)
     bias, resid = _bf(N, seed=K + 2), _bf(B, N, seed=K + 3)
-    sums = O.fold(O.lane_sums(_np(x), _np(w)))
+    lanes = O.WIDE_LANES if N > O.WIDE_N else O.LANES
+    sums = O.fold(O.lane_sums(_np(x), _np(w), lanes), lanes)
     return {"x": x.to(DEV), "w": w.to(DEV), "bias": bias.to(DEV), "resid": resid.to(DEV), "sums": sums,
             "bias_np": _np(bias), "resid_np": _np(resid)}
 
@@ -86,14 +97,17 @@ def test_long_rows_equal_the_restatement(B, N, K):
     _check_epilogues(B, N, K)
 
 
-@pytest.mark.parametrize("epi", [0, 3])
-def test_padded_leading_dimension(epi):
-    """ldy = 24 > N = 23: columns 0..22 are the ldy = N result, and the pad column keeps what the
-    block held before -- y is allocated on a block this test has just filled with the sentinel and
-    freed (the caching allocator hands the same block back; asserted)."""
-    B, N, K = 5, 23, 4104
+@pytest.mark.parametrize("B,N,K", WIDE_SHAPES, ids=lambda v: str(v))
+def test_wide_path_equals_the_restatement(B, N, K):
+    """N > 8192: 16 lanes per column, grid-strided; the same chain at 16 lanes, bit for bit."""
+    C = ext()
+    if "MINGPT_GEMV_WIDE_GRID" not in os.environ:  # the shapes do what their comments say
+        assert C.gemv_argmax_groups(8200, 3) == 512 and C.gemv_argmax_groups(16400, 1) == 1024
+    _check_epilogues(B, N, K)
+
+
+def _check_padded(B, N, K, ld, epi):
     C, c = ext(), _case(B, N, K)
-    ld = 24
     resid = None
     if epi == 3:
         resid = torch.zeros(B, ld, dtype=BF, device=DEV)
@@ -110,6 +124,46 @@ def test_padded_leading_dimension(epi):
     assert y.shape == (B, ld) and y.data_ptr() == ptr, "y did not land on the sentinel block: nothing was checked"
     assert np.array_equal(_bits(y[:, :N]), want_bits)
     assert (y[:, N:].contiguous().view(-1).view(torch.uint8) == SENTINEL_BYTE).all(), "a pad column was written"
+
+
+@pytest.mark.parametrize("epi", [0, 3])
+def test_padded_leading_dimension(epi):
+    """ldy = 24 > N = 23: columns 0..22 are the ldy = N result, and the pad column keeps what the
+    block held before -- y is allocated on a block this test has just filled with the sentinel and
+    freed (the caching allocator hands the same block back; asserted)."""
+    _check_padded(5, 23, 4104, 24, epi)
+
+
+@pytest.mark.parametrize("epi", [0, 3])
+def test_wide_padded_leading_dimension(epi):
+    """The wide path at one chunk per row, ldy = 8208 > N = 8200: the pad columns keep the sentinel."""
+    _check_padded(2, 8200, 8, 8208, epi)
+
+
+def test_wide_fused_argmax():
+    """gemv with am_part at (3, 8200, 64), 512 workgroups: after the host reduction generation.py
+    applies to the last step's keys (unsigned max, 0xFFFFFFFF - low word) every row gives the FIRST
+    index of the maximum of its stored bf16 logits.  Row 0's maximum ties between columns of two
+    different workgroups (two equal weight rows), row 1's sits in the last, partly filled column
+    block (the second item of workgroup 0); am_pos advances by one; y is the plain call's."""
+    B, N, K = 3, 8200, 64
+    C, c = ext(), _case(B, N, K)
+    G = C.gemv_argmax_groups(N, B)
+    w = c["w"].clone()
+    w[100] = w[5000] = 0.5 * c["x"][0]   # column blocks 6 and 312: different workgroups whatever the grid
+    w[N - 1] = 0.5 * c["x"][1]
+    plain = C.gemv(c["x"], w, 0, None, None, 0)
+    part = torch.full((B, G), -1, dtype=torch.long, device=DEV)  # every entry must be written
+    pos = torch.full((1,), 7, dtype=torch.int32, device=DEV)
+    y = C.gemv(c["x"], w, 0, None, None, 0, None, None, 1e-5, part, pos)
+    assert bit_equal(y, plain)
+    assert int(pos.item()) == 8
+    rows = _np(y[:, :N])
+    want = rows.argmax(axis=1)  # numpy: the first index of the maximum
+    assert want[0] == 100 and rows[0, 100] == rows[0, 5000] and want[1] == N - 1, "the case is not what it says"
+    k = (part ^ _I64_MIN).max(dim=1).values ^ _I64_MIN
+    got = (0xFFFFFFFF - (k & 0xFFFFFFFF)).cpu().numpy()
+    assert np.array_equal(got, want), f"argmax {got.tolist()}, first maximum at {want.tolist()}"
 
 
 @pytest.mark.parametrize("N,K", [(100, 6400), (23, 4104)])

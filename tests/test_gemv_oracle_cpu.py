@@ -25,6 +25,19 @@ def test_within_bound_of_the_real_dot_product(B, N, K):
     assert (err <= tol).all()
 
 
+@pytest.mark.parametrize("B,N,K", [(1, 24, 64), (2, 7, 8), (8, 9, 1032), (5, 10, 4096), (3, 9, 3072), (4, 5, 520)],
+                         ids=lambda v: str(v))
+def test_wide_restatement_within_bound_of_the_real_dot_product(B, N, K):
+    """The wide path's 16 lanes per column (K <= 4096 there), under the bound at L = 16."""
+    rng = np.random.default_rng(K + B)
+    x, w = _bf16(rng, B, K), _bf16(rng, N, K, scale=0.05)
+    _, y = O.gemv(x, w, 0, lanes=O.WIDE_LANES)
+    ref, tol = O.bound(x, w, O.WIDE_LANES)
+    err = np.abs(y.astype(np.float64) - ref)
+    print(f"worst error {float((err / tol).max()):.3f} of the allowed")
+    assert (err <= tol).all()
+
+
 def test_epilogues_add_in_fp32_and_round_once():
     """Bias and residual enter as single fp32 adds after the fold: two more roundings to half an ulp
     of a value that |dot| + |bias| + |resid| bounds, doubled, on top of the dot product's bound."""
@@ -59,6 +72,34 @@ def test_lane_and_chunk_order():
     assert O.lane_sums(x, w)[0, 0, 2] == 0.0
     x[0, [16, 17, 512 + 16]] = [2.0 ** 24, -2.0 ** 24, 1.0]
     assert O.lane_sums(x, w)[0, 0, 2] == 1.0
+
+
+def test_wide_lane_and_chunk_order():
+    """16 lanes: column c belongs to lane (c % 128) // 8, rounds of 128 columns in ascending order
+    across the 1024-column segments; the fold is the xor tree over 1, 2, 4, 8."""
+    K = 2048
+    w = np.ones((1, K), dtype=np.float32)
+    x = np.zeros((1, K), dtype=np.float32)
+    x[0, 8 * 5 + 3] = 7.0
+    x[0, 128 + 8 * 5] = 11.0
+    x[0, 1024 + 8 * 5 + 1] = 17.0
+    x[0, 8 * 9] = 13.0
+    acc = O.lane_sums(x, w, 16)[0, 0]
+    assert acc.shape == (16,) and acc[5] == 35.0 and acc[9] == 13.0 and acc.sum() == 48.0
+    x[:] = 0.0
+    x[0, [16, 17, 1024 + 16]] = [1.0, 2.0 ** 24, -2.0 ** 24]  # lane 2, across a segment: (1 + 2^24) - 2^24 = 0
+    assert O.lane_sums(x, w, 16)[0, 0, 2] == 0.0
+    x[0, [16, 17, 1024 + 16]] = [2.0 ** 24, -2.0 ** 24, 1.0]
+    assert O.lane_sums(x, w, 16)[0, 0, 2] == 1.0
+    acc = np.zeros((1, 1, 16), dtype=np.float32)
+    acc[0, 0, :4] = [2.0 ** 24, 1.0, 1.0, -2.0 ** 24]  # pairs first: (2^24 + 1 -> 2^24) + (1 - 2^24) = 1
+    assert O.fold(acc, 16)[0, 0] == 1.0
+    rng = np.random.default_rng(1)
+    a = rng.standard_normal((2, 3, 16)).astype(np.float32)
+    s = a.copy()
+    for o in (1, 2, 4, 8):
+        s = np.stack([s[..., j] + s[..., j ^ o] for j in range(16)], axis=-1)
+    assert (s == s[..., :1]).all() and np.array_equal(O.fold(a, 16), s[..., 0])
 
 
 def test_fold_is_the_xor_tree():
