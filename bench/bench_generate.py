@@ -3,7 +3,9 @@
 GPT-2 preset (--model-type, default gpt2 = 124M): this framework's ``GPT.generate`` (prefill once
 on the gfx950 kernels, then one-token steps against the KV cache with the decode-attention
 kernel) vs the reference's algorithm (``/root/reference/mingpt/model.py:322-356``: re-run the full forward over the whole prefix for
-every new token, no cache) in stock PyTorch bf16 (autocast + SDPA).  Prints one JSON line per B."""
+every new token, no cache) in stock PyTorch bf16 (autocast + SDPA).  Prints one JSON line per B.
+``--int8``: the model is snapped by ``GPT.quantize_int8_`` after it is built, so decode steps of up to 8
+rows read int8 weights (bench/bench_w8_decode.py times that against bf16, interleaved)."""
 import argparse
 import json
 import os
@@ -40,6 +42,8 @@ def ragged(model, a):
         # alternating batch sizes on it would re-allocate and re-capture inside the timed window
         solo = type(model)(model.config, verbose=False).cuda().to(torch.bfloat16).eval()
         solo.load_state_dict(model.state_dict())
+        if model.__dict__.get("_mg_w8"):  # --int8: the one-row model decodes on int8 weights too
+            solo.quantize_int8_()
         cases = {
             "a_equal_generate_batch": lambda: model.generate_batch(list(equal), a.new)[0],
             "a_equal_generate_rectangular": lambda: model.generate(equal, a.new),
@@ -224,6 +228,8 @@ def main():
     ap.add_argument("--process", action="store_true",
                     help="time generate with the logits processors off and on, greedy and seeded (this "
                          "framework only)")
+    ap.add_argument("--int8", action="store_true",
+                    help="quantize_int8_ the model after building it (weight-only int8 decode)")
     ap.add_argument("--model-type", default="gpt2", choices=["gpt2", "gpt2-medium", "gpt2-large", "gpt2-xl"],
                     help="the preset whose shape is timed, on random weights (default: gpt2, 124M)")
     a = ap.parse_args()
@@ -233,6 +239,9 @@ def main():
     cfg = GPTConfig(model_type=a.model_type, vocab_size=50257, block_size=1024)
     ours = GPT(cfg, verbose=False)
     ours = ours.cuda().to(torch.bfloat16).eval()
+    if a.int8:
+        ours.quantize_int8_()
+        a.model_type += " int8"  # the results' "model" field says so
     if a.beams:
         return beams(ours, a)
     if a.process:

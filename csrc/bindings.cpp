@@ -523,15 +523,23 @@ at::Tensor attention_bwd(const at::Tensor& qkv, const at::Tensor& out, const at:
 // gemm_rows.hip): x bf16 [..., K] and W bf16 [N, K], contiguous; ldy <= 0 means N, else ldy >= N;
 // epi 0 none, 1 bias, 2 bias + GELU, 3 bias + residual, with bias bf16 [N] when given (null
 // otherwise) and resid bf16 [M, ldy] for epi 3 (null otherwise).  How many rows and how long a row
-// an op takes is that op's own check.
+// an op takes is that op's own check.  w8: W is int8 [N, K] instead (gemv_w8), 8-byte aligned.
 struct ProjArgs {
   int64_t M, N, K, ldy;
   const bf16_t *bias, *resid;
 };
 
 ProjArgs proj_args(const char* op, const at::Tensor& x, const at::Tensor& W, int64_t epi,
-                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy) {
-  CHECK_BF16(x); CHECK_BF16(W); CHECK_CONTIG(x); CHECK_CONTIG(W);
+                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy,
+                   bool w8 = false) {
+  CHECK_BF16(x); CHECK_CONTIG(x); CHECK_CONTIG(W);
+  if (w8) {
+    CHECK_DEV(W);
+    TORCH_CHECK(W.scalar_type() == at::kChar, op, ": Wq must be int8");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(W.data_ptr()) % 8 == 0, op, ": Wq must be 8-byte aligned");
+  } else {
+    CHECK_BF16(W);
+  }
   TORCH_CHECK(W.dim() == 2 && W.size(0) >= 1 && W.size(1) >= 1, op, ": W [N, K]");
   const int64_t K = W.size(1), N = W.size(0), M = x.numel() / K;
   TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, op, ": x [..., K] against W [N, K]");
@@ -546,13 +554,18 @@ ProjArgs proj_args(const char* op, const at::Tensor& x, const at::Tensor& W, int
   return {M, N, K, ldy, bias.has_value() ? bp(*bias) : nullptr, epi == 3 ? bp(*resid) : nullptr};
 }
 
-// y[B, ldy] (ldy >= N) = epi(x[B, K] @ W[N, K]^T): the decode-time projection (gemv.hip)
-at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10::optional<at::Tensor>& bias,
-                const c10::optional<at::Tensor>& resid, int64_t ldy, const c10::optional<at::Tensor>& lnw,
-                const c10::optional<at::Tensor>& lnb, double eps, const c10::optional<at::Tensor>& am_part,
-                const c10::optional<at::Tensor>& am_pos) {
-  const ProjArgs p = proj_args("gemv", x, W, epi, bias, resid, ldy);
+// y[B, ldy] (ldy >= N) = epi(x[B, K] @ W[N, K]^T): the decode-time projection (gemv.hip).  scale
+// null: W bf16 (gemv); else W int8 with scale fp32 [N] (gemv_w8) -- one set of checks for both.
+at::Tensor gemv_any(const char* op, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, int64_t epi,
+                    const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy,
+                    const c10::optional<at::Tensor>& lnw, const c10::optional<at::Tensor>& lnb, double eps,
+                    const c10::optional<at::Tensor>& am_part, const c10::optional<at::Tensor>& am_pos) {
+  const ProjArgs p = proj_args(op, x, W, epi, bias, resid, ldy, scale != nullptr);
   const int64_t B = p.M, N = p.N, K = p.K;
+  if (scale) {
+    CHECK_F32(*scale); CHECK_CONTIG(*scale);
+    TORCH_CHECK(scale->dim() == 1 && scale->numel() == N, op, ": scale fp32 [N]");
+  }
   TORCH_CHECK(mg::gemv_supported((int)B, (int)K), "gemv: B <= 8, K % 8 == 0, K <= 8192");
   // rows staged in two segments: the one-row-per-wave path without fused LayerNorm only
   TORCH_CHECK(K <= mg::kGemvSegK || N <= 8192, "gemv: K > 4096 needs N <= 8192 (wide outputs take K <= 4096)");
@@ -578,9 +591,29 @@ at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10
     am.pos = am_pos->data_ptr<int>();
   }
   auto y = at::empty({B, p.ldy}, x.options());
-  mg::gemv(bp(x), bp(W), bp(y), (int)B, (int)N, (int)K, p.ldy, p.bias, p.resid, (int)epi, cur_stream(), bp_opt(lnw),
-           bp_opt(lnb), (float)eps, am_part.has_value() ? &am : nullptr);
+  const mg::GemvArgmax* amp = am_part.has_value() ? &am : nullptr;
+  if (scale)
+    mg::gemv_w8(bp(x), W.data_ptr<int8_t>(), fp(*scale), bp(y), (int)B, (int)N, (int)K, p.ldy, p.bias, p.resid,
+                (int)epi, cur_stream(), bp_opt(lnw), bp_opt(lnb), (float)eps, amp);
+  else
+    mg::gemv(bp(x), bp(W), bp(y), (int)B, (int)N, (int)K, p.ldy, p.bias, p.resid, (int)epi, cur_stream(), bp_opt(lnw),
+             bp_opt(lnb), (float)eps, amp);
   return y;
+}
+
+at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, int64_t epi, const c10::optional<at::Tensor>& bias,
+                const c10::optional<at::Tensor>& resid, int64_t ldy, const c10::optional<at::Tensor>& lnw,
+                const c10::optional<at::Tensor>& lnb, double eps, const c10::optional<at::Tensor>& am_part,
+                const c10::optional<at::Tensor>& am_pos) {
+  return gemv_any("gemv", x, W, nullptr, epi, bias, resid, ldy, lnw, lnb, eps, am_part, am_pos);
+}
+
+// the same on int8 weight rows Wq [N, K] with one power-of-two fp32 scale per row (the W8 rule, common.h)
+at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& Wq, const at::Tensor& scale, int64_t epi,
+                   const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy,
+                   const c10::optional<at::Tensor>& lnw, const c10::optional<at::Tensor>& lnb, double eps,
+                   const c10::optional<at::Tensor>& am_part, const c10::optional<at::Tensor>& am_pos) {
+  return gemv_any("gemv_w8", x, Wq, &scale, epi, bias, resid, ldy, lnw, lnb, eps, am_part, am_pos);
 }
 
 // y[M, ldy] (ldy >= N) = epi(x[M, K] @ W[N, K]^T) at 1 <= M <= 64 rows: the decode-time projection
@@ -1160,6 +1193,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_argmax_groups", [](int64_t N, int64_t B) { return (int64_t)mg::gemv_grid((int)N, (int)B); },
         py::arg("N"), py::arg("B"));
   m.def("gemv_supported", &mg::gemv_supported);
+  m.def("gemv_w8", &gemv_w8, py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("epi"),
+        py::arg("bias") = py::none(), py::arg("resid") = py::none(), py::arg("ldy") = 0, py::arg("lnw") = py::none(),
+        py::arg("lnb") = py::none(), py::arg("eps") = 1e-5, py::arg("am_part") = py::none(),
+        py::arg("am_pos") = py::none());
+  m.def("gemv_w8_supported", &mg::gemv_w8_supported);
   m.def("gemm_rows", &gemm_rows, py::arg("x"), py::arg("W"), py::arg("epi"), py::arg("bias") = py::none(),
         py::arg("resid") = py::none(), py::arg("ldy") = 0);
   m.def("gemm_rows_supported", &mg::gemm_rows_supported);

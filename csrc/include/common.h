@@ -411,6 +411,31 @@ MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* res
   return f2bf(v);
 }
 
+// ---------------------------------------------------------------- W8: int8 weight rows, power-of-two scales
+// Weight-only 8-bit decode (gemv_w8, gemv.hip; ops/quant.py is the rule in torch ops).  For a weight
+// matrix W [N, K] (row n = output column n) and a_n = max_k |W[n, k]|:
+//   a_n == 0: s_n = 1, q[n, :] = 0;
+//   else s_n = the smallest power of two with a_n / s_n <= 127, from the exponent of a_n alone: with
+//     a_n = m * 2^e, m in [0.5, 1) (frexp), s_n = 2^(e - 7) if m <= 127 / 128, else 2^(e - 6) -- no log2
+//     of a rounded quotient;
+//   q[n, k] = clamp(rne(W[n, k] / s_n), -127, 127) as int8: the division is exact (a power of two),
+//     the rounding is to nearest, halves to even.
+// A non-finite weight is outside the rule (ValueError on the host).  s_n is never below 2^-126 (a
+// normal fp32): a row with 0 < a_n < 2^-119 keeps |W - s q| <= s_n / 2, the exactness and the fixed point
+// below, not the two bounds that need a_n / s_n > 63.5.  Consequences:
+//   |W - s q| <= s_n / 2 < a_n / 127            (a_n / s_n > 63.5, and the clamp never acts: |W / s| <= 127)
+//   max_k |q[n, k]| >= 64 for a non-zero row    (rne of a value above 63.5)
+//   s q is exact in bf16                        (7 significant bits times a power of two)
+//   quantize(s q) == (q, s)                     (max |q| in [64, 127] gives the same s; q / 1 rounds to itself)
+// One output of gemv_w8 is  y[b, n] = proj_epilogue(s_n * sum[b, n]),  sum the bf16 kernel's chain with
+// float(q[n, k]) in place of the bf16 weight: the same lanes (64, or 16 on the wide path), the same
+// columns per lane c = 8 j + 8 L u, the same element order, the same xor fold.  Every product
+// float(q) * x is exact (at most 7 significant bits times 8).  Scaling by a power of two commutes with
+// every fp32 rounding, so s_n * sum equals the chain run on the bf16 values s_n * q[n, k], bit for
+// bit: gemv_w8(x, q, s) == gemv(x, s q).  Precondition: no fp32 intermediate of either chain (a lane
+// sum, a fold sum, s_n * sum) is subnormal or overflows -- there the two roundings differ.
+// (s_n * sum + bias may contract to one fma: the product is exact, so the result is the same.)
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Host: f(std::true_type{}) or f(std::false_type{}) for a run-time flag that is a template argument

@@ -84,6 +84,14 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
           const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw = nullptr,
           const bf16_t* lnb = nullptr, float eps = 1e-5f, const GemvArgmax* am = nullptr);
 bool gemv_nt_weights();  // weight loads non-temporal (default) or cached (MINGPT_GEMV_NT=0); gemv.hip
+// The same kernel body over int8 weight rows (the W8 rule in common.h): Wq int8 [N, K], 8-byte
+// aligned, scale fp32 [N] (powers of two); y = epilogue(scale[n] * chain(x, float(Wq[n, :]))), bit
+// for bit gemv's output on the bf16 matrix scale[n] * Wq[n, k].  Same paths, limits, fused
+// LayerNorm, epilogues and argmax as gemv.
+bool gemv_w8_supported(int B, int K);
+void gemv_w8(const bf16_t* x, const int8_t* Wq, const float* scale, bf16_t* y, int B, int N, int K, long ldy,
+             const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw = nullptr,
+             const bf16_t* lnb = nullptr, float eps = 1e-5f, const GemvArgmax* am = nullptr);
 
 // gemm_rows.hip (decode-time rows GEMM on MFMA: y[M, ldy] = epi(x[M, K] @ W[N, K]^T); the decode
 // loops use it at 9..64 rows).  gemm_rows_supported: 1 <= M <= 64, K % 8 == 0, K <= 8192; any

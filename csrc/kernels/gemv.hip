@@ -26,6 +26,11 @@
 //   LPR 64, KMAX kGemvSegK  one column per wave          N <= 8192, K <= 4096
 //   LPR 64, KMAX kGemvMaxK  long rows in segments        N <= 8192, 4096 < K <= 8192
 //   LPR 16                  wide, grid-strided + argmax  N > 8192 (K <= 4096)
+// The weight element type WT is a template argument of the one body: bf16_t (gemv) or int8_t
+// (gemv_w8: int8 rows with a power-of-two fp32 scale per row -- the W8 rule in common.h).  A lane's
+// 8-column chunk is then 8 bytes instead of 16, float(q) takes the bf16 weight's place in the same
+// chain, and the folded sum is multiplied by the row's scale (exact) before the epilogue, so the
+// output bits are the bf16 kernel's on the dequantized matrix.
 #include "common.h"
 #include "kernels.h"
 
@@ -60,13 +65,45 @@ MG_DEVICE void gemv_argmax(const GemvArgmax& am, const unsigned long long (&key)
   if (blockIdx.x == 0 && threadIdx.x == 0) *am.pos += 1;  // nothing else in this kernel reads it
 }
 
+// A lane's 8-column chunk of a weight row: 16 bytes of bf16 or 8 bytes of int8, read with the
+// default or the non-temporal policy; a chunk past K is zero.
+template <class WT>
+struct WChunk;
+template <>
+struct WChunk<bf16_t> {
+  typedef uint4 type;
+  static MG_DEVICE uint4 zero() { return make_uint4(0, 0, 0, 0); }
+  template <bool NT>
+  static MG_DEVICE uint4 ld(const bf16_t* p) { return NT ? ld16_nt(p) : ld16(p); }
+  static MG_DEVICE void unpack(const uint4& u, float (&f)[8]) { unpack8(u, f); }
+};
+template <>
+struct WChunk<int8_t> {
+  typedef uint2 type;
+  static MG_DEVICE uint2 zero() { return make_uint2(0, 0); }
+  template <bool NT>
+  static MG_DEVICE uint2 ld(const int8_t* p) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const v2u v = NT ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p)) : *reinterpret_cast<const v2u*>(p);
+    return make_uint2(v[0], v[1]);
+  }
+  // 8 x int8 -> 8 x f32 (exact), column order = byte order
+  static MG_DEVICE void unpack(const uint2& u, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f[e] = (float)(int8_t)(u.x >> (8 * e));
+      f[4 + e] = (float)(int8_t)(u.y >> (8 * e));
+    }
+  }
+};
+
 // The FMA chain of one 8-column chunk: weight chunk w against the B staged rows' chunks at xcol,
 // xcol + ldx, ...  A lane's sum is this chain over its chunks in ascending column order (e = 0..7
 // within a chunk, rows inner), whichever path runs it: tests/_gemv_oracle.py restates it.
-template <int B>
-MG_DEVICE void gemv_fma(const uint4& w, const bf16_t* xcol, int ldx, float (&acc)[B]) {
+template <int B, class WT>
+MG_DEVICE void gemv_fma(const typename WChunk<WT>::type& w, const bf16_t* xcol, int ldx, float (&acc)[B]) {
   float wf[8];
-  unpack8(w, wf);
+  WChunk<WT>::unpack(w, wf);
 #pragma unroll
   for (int b = 0; b < B; ++b) {
     float xf[8];
@@ -82,15 +119,21 @@ MG_DEVICE void gemv_fma(const uint4& w, const bf16_t* xcol, int ldx, float (&acc
 // device functions beside gemv_fma: -ffp-contract leaves to the compiler which of the LayerNorm's
 // squares fuse with their add, and that choice -- the staged bits -- changed for some B whenever
 // this code was compiled from inside another function (PERF.md 'Decode projections refactor').
-template <int B, int LPR, bool NTW, int KMAX = kGemvSegK>
+// scale: one fp32 per output column for int8 weights (the folded sum times it is the dot product
+// with the dequantized row); not read for bf16 weights.
+template <int B, int LPR, bool NTW, int KMAX = kGemvSegK, class WT = bf16_t>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
-                                                   const bf16_t* __restrict__ W,
+                                                   const WT* __restrict__ W,
                                                    bf16_t* __restrict__ y, int N, int K, long ldy,
                                                    const bf16_t* __restrict__ bias,
                                                    const bf16_t* __restrict__ resid, int epi,
                                                    const bf16_t* __restrict__ lnw,
                                                    const bf16_t* __restrict__ lnb, float eps,
-                                                   const GemvArgmax am) {
+                                                   const GemvArgmax am,
+                                                   const float* __restrict__ scale) {
+  typedef WChunk<WT> WC;
+  typedef typename WC::type wchunk_t;
+  constexpr bool W8 = std::is_same<WT, int8_t>::value;
   extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [B][K]; long rows: [B][kGemvSegK]
   constexpr bool LONGK = KMAX > kGemvSegK;
   static_assert(!LONGK || LPR == 64, "rows longer than kGemvSegK: one row per wave only");
@@ -102,13 +145,13 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
   // one row per wave: the whole row (K <= 4096: <= 8 loads per lane; LONGK: <= 16) is requested
   // before x is staged and normalised, so the weight stream's memory latency overlaps the LayerNorm's
   constexpr int NPF = LPR == 64 ? KMAX / STRIDE : 1;
-  uint4 wpf[NPF];
+  wchunk_t wpf[NPF];
   if constexpr (LPR == 64) {
-    const bf16_t* wr = W + (long)min(n, N - 1) * K;
+    const WT* wr = W + (long)min(n, N - 1) * K;
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int c = j * 8 + u * STRIDE;
-      wpf[u] = c < K ? (NTW ? ld16_nt(wr + c) : ld16(wr + c)) : make_uint4(0, 0, 0, 0);
+      wpf[u] = c < K ? WC::template ld<NTW>(wr + c) : WC::zero();
     }
   }
   if (!LONGK && lnw) {  // (LONGK: no fused LayerNorm -- a LayerNorm'ed row is at most 4096 wide)
@@ -191,8 +234,11 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     }
     if (n < N && j == 0) {
       const float bv = bias ? bf2f(bias[n]) : 0.f;
+      float sc = 1.f;
+      if constexpr (W8) sc = scale[n];
 #pragma unroll
       for (int b = 0; b < B; ++b) {
+        if constexpr (W8) acc[b] *= sc;  // a power of two: exact
         const bf16_t o = proj_epilogue(acc[b], bv, epi, resid + (long)b * ldy + n);
         y[(long)b * ldy + n] = o;
         acc[b] = bf2f(o);  // the argmax ranks the stored (bf16) logits
@@ -245,7 +291,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
         for (int u = s * UPS; u < (s + 1) * UPS; ++u) {
           const int c = j * 8 + u * STRIDE;
-          if (c < K) gemv_fma<B>(wpf[u], xs + c - s0, kGemvSegK, acc);
+          if (c < K) gemv_fma<B, WT>(wpf[u], xs + c - s0, kGemvSegK, acc);
         }
       }
     }
@@ -258,7 +304,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int c = j * 8 + u * STRIDE;
-      if (c < K) gemv_fma<B>(wpf[u], xs + c, K, acc);
+      if (c < K) gemv_fma<B, WT>(wpf[u], xs + c, K, acc);
     }
     epilogue(acc, n);
   } else {
@@ -274,18 +320,17 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     const int nrb = (N + 15) / 16;
     const int nseg = (K + 16 * 8 * 8 - 1) / (16 * 8 * 8);
     const int nit = (blockIdx.x < nrb ? (nrb - 1 - blockIdx.x) / gridDim.x + 1 : 0) * nseg;
-    auto load_item = [&](int it, uint4 (&r)[8]) {
+    auto load_item = [&](int it, wchunk_t (&r)[8]) {
       const int rb = blockIdx.x + (it / nseg) * gridDim.x, seg = it % nseg;
       const int nr = min((rb * 4 + wid) * RPW + g, N - 1);
-      const bf16_t* wr = W + (long)nr * K + seg * 1024;
+      const WT* wr = W + (long)nr * K + seg * 1024;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int c = seg * 1024 + j * 8 + u * STRIDE;
-        r[u] = c < K ? (NTW ? ld16_nt(wr + j * 8 + u * STRIDE) : ld16(wr + j * 8 + u * STRIDE))
-                     : make_uint4(0, 0, 0, 0);
+        r[u] = c < K ? WC::template ld<NTW>(wr + j * 8 + u * STRIDE) : WC::zero();
       }
     };
-    uint4 cur[8], nxt[8];
+    wchunk_t cur[8], nxt[8];
     if (nit > 0) load_item(0, cur);
     for (int it = 0; it < nit; ++it) {
       if (it + 1 < nit) load_item(it + 1, nxt);
@@ -298,7 +343,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int c = seg * 1024 + j * 8 + u * STRIDE;
-        if (c < K) gemv_fma<B>(cur[u], xs + c, K, acc);
+        if (c < K) gemv_fma<B, WT>(cur[u], xs + c, K, acc);
       }
       if (seg == nseg - 1) {
         epilogue(acc, nr);
@@ -343,9 +388,12 @@ bool gemv_nt_weights() {
   return nt != 0;
 }
 
-void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long ldy, const bf16_t* bias,
-          const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw, const bf16_t* lnb,
-          float eps, const GemvArgmax* am) {
+namespace {
+// the launch of gemv (WT bf16_t, scale null) and gemv_w8 (WT int8_t)
+template <class WT>
+void gemv_launch(const bf16_t* x, const WT* W, const float* scale, bf16_t* y, int B, int N, int K, long ldy,
+                 const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw,
+                 const bf16_t* lnb, float eps, const GemvArgmax* am) {
   const bool longk = K > kGemvSegK;  // x staged in segments of kGemvSegK columns
   const size_t smem = sizeof(bf16_t) * (size_t)B * (longk ? kGemvSegK : K);
   // one row per wave (N / 4 workgroups) up to ~8k outputs; 4 rows per wave beyond (the LM head
@@ -356,8 +404,8 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
   // the one launch: B, the path (LPR, KMAX) and the weight-load policy pick the instantiation
   auto launch = [&](auto b, auto lpr, auto kmax) {
     dispatch_bool(gemv_nt_weights(), [&](auto nt) {
-      gemv_kernel<decltype(b)::value, decltype(lpr)::value, decltype(nt)::value, decltype(kmax)::value>
-          <<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv);
+      gemv_kernel<decltype(b)::value, decltype(lpr)::value, decltype(nt)::value, decltype(kmax)::value, WT>
+          <<<grid, 256, smem, stream>>>(x, W, y, N, K, ldy, bias, resid, epi, lnw, lnb, eps, amv, scale);
     });
   };
   auto rows = [&](auto b) {
@@ -376,6 +424,21 @@ void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long
     case 8: rows(std::integral_constant<int, 8>{}); break;
     default: break;
   }
+}
+}  // namespace
+
+void gemv(const bf16_t* x, const bf16_t* W, bf16_t* y, int B, int N, int K, long ldy, const bf16_t* bias,
+          const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw, const bf16_t* lnb,
+          float eps, const GemvArgmax* am) {
+  gemv_launch<bf16_t>(x, W, nullptr, y, B, N, K, ldy, bias, resid, epi, stream, lnw, lnb, eps, am);
+}
+
+bool gemv_w8_supported(int B, int K) { return gemv_supported(B, K); }
+
+void gemv_w8(const bf16_t* x, const int8_t* Wq, const float* scale, bf16_t* y, int B, int N, int K, long ldy,
+             const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream, const bf16_t* lnw,
+             const bf16_t* lnb, float eps, const GemvArgmax* am) {
+  gemv_launch<int8_t>(x, Wq, scale, y, B, N, K, ldy, bias, resid, epi, stream, lnw, lnb, eps, am);
 }
 
 }  // namespace mg

@@ -63,6 +63,12 @@ B sequences and B * K step rows and lives beside the others (``_spec_cache``); t
 kernel, embedding, ``_blocks`` with the grouped decode attention, the plain LM head, row argmax,
 accept kernel -- is the loop ``("spec", K)`` (``_GpuCache.spec``).  The CPU path runs
 ``ops.reference.ngram_draft`` / ``spec_accept`` around one model forward per step.
+
+Weight-only int8 (``quantize_int8_``; the W8 rule in common.h): the model's projection and LM-head
+weights are snapped in place to int8 rows times power-of-two scales, so every path here computes that
+model; on a marked model ``_lin``'s ``"gemv"`` route reads the int8 twins (``w8_weights``,
+``gemv_w8``) and produces the bf16 kernel's bits.  ``_W8_DECODE`` (``MINGPT_W8_DECODE=0``) keeps the
+bf16 kernel; which kernel the steps launch is part of a state's stamp, so a flip re-captures its loops.
 """
 from __future__ import annotations
 
@@ -76,6 +82,7 @@ import torch.nn.functional as F
 
 from ..ops import reference as R
 from ..ops.grads import before_use
+from ..ops.quant import dequantize_rows, quantize_rows
 
 
 def _sample(logits, temperature, do_sample, top_k, top_p=None):
@@ -159,6 +166,81 @@ def bf16_weights(model):
     return get
 
 
+def _w8_named_weights(model):
+    """(name, weight) of every matrix the W8 path covers: the blocks' four projections and the LM head
+    (the tied ``wte``)."""
+    for i, blk in enumerate(model.transformer.h):
+        for sub in ("attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj"):
+            yield f"transformer.h.{i}.{sub}.weight", blk.get_submodule(sub).weight
+    yield "lm_head.weight", model.lm_head.weight
+
+
+def w8_weights(model):
+    """int8 twins of the weights the skinny GEMM reads (the W8 rule in common.h), cached on the model.
+
+    ``get(w)`` returns ``(q int8 [N, K], s float32 [N])`` or None.  A twin is built on first use and
+    kept under the weight's (storage pointer, in-place version) stamp.  When the stamp changes the
+    weight is quantized again, and the twin is kept only if the weight still equals its own
+    dequantized twin exactly (a model snapped by ``quantize_int8_``); otherwise that weight takes the
+    bf16 kernel from then on -- a later optimizer step or ``load_state_dict`` makes decode slower,
+    never wrong (``quantize_int8_`` starts over).  K no multiple of 8: None."""
+    cache = model.__dict__.setdefault("_mg_w8_weights", {})
+
+    def get(w: torch.Tensor):
+        if w.dim() != 2 or w.shape[1] % 8:
+            return None
+        stamp = (w.data_ptr(), w._version)
+        ent = cache.get(id(w))
+        if ent is not None and (ent[1] is None or ent[0] == stamp):
+            return ent[1]
+        twin = None
+        try:
+            q, s = quantize_rows(w)
+            if torch.equal(dequantize_rows(q, s, w.dtype), w.detach()):
+                twin = (q.contiguous(), s.contiguous())
+        except ValueError:  # a non-finite weight or another dtype: the bf16 kernel's business
+            pass
+        cache[id(w)] = (stamp, twin)
+        return twin
+
+    return get
+
+
+def w8_status(model):
+    """Per covered weight name: True (an int8 twin is live), False (the weight left the W8 path: it no
+    longer equals a dequantized twin) or None (no decode step has asked for it yet)."""
+    cache = model.__dict__.get("_mg_w8_weights", {})
+    out = {}
+    for name, w in _w8_named_weights(model):
+        ent = cache.get(id(w))
+        out[name] = None if ent is None else ent[1] is not None
+    return out
+
+
+@torch.no_grad()
+def quantize_int8_(model):
+    """Snap ``model`` in place to int8-representable weights (the W8 rule in common.h,
+    ``ops.quant.quantize_rows``): every block's ``c_attn``, attention ``c_proj``, ``mlp.c_fc`` and
+    ``mlp.c_proj`` weight and ``lm_head.weight`` become s_n q[n, k], one power-of-two scale per output
+    row.  ``lm_head.weight`` is the tied ``wte``, so the token embedding is snapped with it.  Biases,
+    LayerNorms and ``wpe`` are untouched.  Every path (CPU, ``use_cache=False``, prefill, the rows and
+    MFMA GEMMs) then computes the snapped model; GPU decode steps of up to 8 rows read the int8 twins
+    (``gemv_w8``) and produce the same bits.  The model is marked (``_mg_w8``).  Idempotent.  Returns
+    {weight name: the largest |W - s q| / a_n over its rows} (0.0 on a snapped model; < 1 / 127)."""
+    report = {}
+    for name, w in _w8_named_weights(model):
+        q, s = quantize_rows(w)
+        d = dequantize_rows(q, s, w.dtype)
+        a = w.float().abs().amax(dim=1)
+        err = (w.float() - d.float()).abs().amax(dim=1) / torch.where(a > 0, a, torch.ones_like(a))
+        report[name] = float(err.max())
+        if not torch.equal(d, w):
+            w.copy_(d)
+    model.__dict__.get("_mg_w8_weights", {}).clear()  # weights that had left the W8 path start over
+    model.__dict__["_mg_w8"] = True
+    return report
+
+
 def _capture(fn):
     """(graph, fn()) with fn's launches captured into a new hipGraph.  Python's cyclic garbage is
     collected first and the collector stays off until the capture ends: a decode state and its
@@ -182,6 +264,9 @@ _GRAPH_DECODE = True  # set False to launch the decode step eagerly
 # decode steps of 9..64 rows run their projections on the rows GEMM (gemm_rows.hip); False
 # (MINGPT_ROWS_GEMM=0) sends them to the MFMA GEMM as more than 64 rows go
 _ROWS_GEMM = os.environ.get("MINGPT_ROWS_GEMM", "1") != "0"
+# a model marked by quantize_int8_ runs its skinny-GEMM projections on the int8 twins (gemv_w8: the
+# same bits from half the weight bytes); False (MINGPT_W8_DECODE=0) keeps them on the bf16 kernel
+_W8_DECODE = os.environ.get("MINGPT_W8_DECODE", "1") != "0"
 
 
 class _Loop:
@@ -222,7 +307,7 @@ class _GpuCache:
         from ..ops import gemm as G
 
         model.config.check_gpu_support()
-        self.C, self.G, self.bf = ext(), G, bf16_weights(model)
+        self.C, self.G, self.bf, self.w8 = ext(), G, bf16_weights(model), w8_weights(model)
         self.model = model
         self.tmax = tmax
         B = idx.size(0) if rows is None else rows
@@ -241,7 +326,7 @@ class _GpuCache:
         self.dec_part = torch.empty(self.C.attention_decode_part_floats(B, H, D // H),
                                     device=idx.device, dtype=torch.float32)
         self.dec_cnt = torch.zeros(B * H, device=idx.device, dtype=torch.int32)
-        self.stamp = _weight_stamp(model)
+        self.stamp = self._stamp()
         self._loops = {}  # the device-side token loops (_Loop) by name, built on first use
         if rows is None:
             self.prefill(idx, last)
@@ -255,7 +340,7 @@ class _GpuCache:
 
         model.config.check_gpu_support()
         self = cls.__new__(cls)
-        self.C, self.G, self.bf, self.model = ext(), G, bf16_weights(model), model
+        self.C, self.G, self.bf, self.w8, self.model = ext(), G, bf16_weights(model), w8_weights(model), model
         return self
 
     def _route(self, rows):
@@ -288,8 +373,13 @@ class _GpuCache:
         code = {"none": 0, "bias": 1, "gelu": 2, "resid": 3}[epi]
         if route == "gemv":
             lw, lb = (bf(ln.weight), bf(ln.bias)) if ln is not None else (None, None)
+            tw = self.w8(w) if self._w8_on() else None  # (q, s): the int8 twin of a snapped weight
             if am is not None:
+                if tw is not None:
+                    return C.gemv_w8(inp, tw[0], tw[1], code, None, None, ld, lw, lb, eps, am[0], am[1])
                 return C.gemv(inp, bf(w), code, None, None, ld, lw, lb, eps, am[0], am[1])
+            if tw is not None:
+                return C.gemv_w8(inp, tw[0], tw[1], code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
             return C.gemv(inp, bf(w), code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
         if ln is not None:
             inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
@@ -375,8 +465,17 @@ class _GpuCache:
                                                               self.dec_cnt, pos_stride), route)
         return self._head(x, route, am=(am_part, pos) if am_part is not None else None)
 
+    def _w8_on(self):
+        """The skinny-GEMM projections read int8 twins: the model is marked and the switch is on."""
+        return _W8_DECODE and self.model.__dict__.get("_mg_w8", False)
+
+    def _stamp(self):
+        # the weights' stamp and which skinny GEMM the steps launch: a loop captured for one kernel
+        # is never replayed for the other
+        return _weight_stamp(self.model), self._w8_on()
+
     def _fresh(self):
-        st = _weight_stamp(self.model)
+        st = self._stamp()
         if st != self.stamp:  # a weight moved or changed: captured pointers / bf16 copies are stale
             self.stamp = st
             self._loops.clear()

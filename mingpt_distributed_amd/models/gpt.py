@@ -280,6 +280,15 @@ class GPT(nn.Module):
         return generate_speculative(self, idx, max_new_tokens, draft_len=draft_len, ngram=ngram,
                                     return_stats=return_stats)
 
+    def quantize_int8_(self):
+        """Snap the projections' and the LM head's weights in place to int8 rows times power-of-two
+        scales (``generation.quantize_int8_``; the tied ``wte`` is snapped with ``lm_head.weight``), so
+        GPU decode steps of up to 8 rows read int8 weights and every path computes the same model.
+        Returns the per-weight relative rounding error."""
+        from .generation import quantize_int8_
+
+        return quantize_int8_(self)
+
     @torch.no_grad()
     def score(self, idx, lengths=None):
         """Per-token log-probabilities of given sequences, float32 [B, T]: ``out[b, j]`` is the

@@ -27,6 +27,10 @@ by ``score / n_generated ** a``.
 suffix the draft looks up) -- the text of ``--greedy``, in fewer steps -- and prints the steps taken
 and the mean tokens per step.
 
+``--int8`` snaps the model to int8-representable weights after loading (``GPT.quantize_int8_``: int8
+rows times power-of-two scales; on a GPU the decode steps then read int8 weights) and prints the largest
+relative rounding error.
+
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
 """
@@ -77,6 +81,9 @@ def main(argv=None):
                     help="greedy decoding of one prompt with n-gram drafts of this many tokens (1..7) per step")
     ap.add_argument("--ngram", type=int, default=3,
                     help="with --speculative: the longest suffix (1..4) the draft looks up in the text so far")
+    ap.add_argument("--int8", action="store_true",
+                    help="weight-only int8: snap the projections and the LM head to int8 rows with power-of-two "
+                         "scales (GPT.quantize_int8_) before generating")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -88,6 +95,9 @@ def main(argv=None):
     else:
         model = GPT.from_pretrained(a.model_type, source=a.weights)
     model.to(dev).eval()
+    if a.int8:
+        report = model.quantize_int8_()
+        print(f"(int8 weights: {len(report)} matrices snapped, largest |W - s q| / max|row| {max(report.values()):.5f})")
 
     tok = None
     try:
