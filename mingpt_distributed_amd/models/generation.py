@@ -1,74 +1,32 @@
-"""Autoregressive generation with a KV cache.
+"""Autoregressive generation with a KV cache: ``generate``, ``generate_batch``, ``generate_beam``,
+``generate_speculative`` and ``score``.  What each computes is documented on the function; the rules
+(sampling, log-probabilities, processors, beams, drafts, W8) are in common.h and ``ops.reference``.
 
-Semantics follow the reference ``GPT.generate`` (``/root/reference/mingpt/model.py:322-356``):
-crop the context to ``block_size``, logits of the last position / temperature, optional top-k
-masking to -inf, softmax, multinomial sample or greedy top-1, append.  The reference re-runs the
-full forward over the prefix for every token (defect D32); here the prompt is prefilled once and
-each new token attends to cached keys/values.
+Layout of this file, top to bottom:
 
-GPU path: the prefill runs the gfx950 kernels and keeps each layer's qkv GEMM output as the cache
-([B, Tmax, 3D] rows); each decode step runs LN / GEMM / decode-attention kernels on B rows and
-appends K/V inside the attention kernel.  CPU path: the same algorithm in plain PyTorch.  When the
-sequence outgrows ``block_size`` the window slides and the cache is rebuilt from the cropped
-context (exactly the reference's cropping semantics).
+* ``_sample``, ``_CpuCache``: the CPU path -- the same algorithm in plain PyTorch, and the executable
+  definition of the semantics (the ``_cpu`` halves of the entry points further down).
+* ``bf16_weights``, ``w8_weights``, ``w8_status``, ``quantize_int8_``: per-model weight twins.
+* ``_Loop``: one device-side token loop -- eager warm-up, captured once as a hipGraph, replayed.
+* ``_Params``: an 8-word device parameter block (``_sample_words``, ``_ragged_words``, ``_proc_words``).
+* ``_Body``: the step bodies' plumbing -- ``_route`` / ``_lin`` (which GEMM a projection runs on),
+  ``_blocks``, ``_head``, ``_prompt``.  ``score`` needs nothing else.
+* ``_GpuCache(_Body)``: one decode state -- KV caches, workspaces, the weights' stamp, the two step
+  bodies (``prefill``, ``_decode``) and every token loop as a closure around ``_decode`` that ends with
+  the loop's own tail.  A model keeps up to three (``_state_for``): ``_mg_decode_cache``,
+  ``_mg_beam_cache`` (B * W rows) and ``_mg_spec_cache`` (B sequences, B * K step rows).
+* the word builders, ``_state_for``, then one section per entry point: checks, host loop, GPU half.
 
-GPU host code: ``_GpuCache.prefill`` and ``_GpuCache._decode`` are the two step bodies (embedding,
-``_blocks``, ``_head``).  Every device-side token loop (``step``, ``greedy``, ``sample``, ``ragged``)
-is a closure around ``_decode`` that ends with the loop's own tail, driven by one ``_Loop`` (eager
-warm-up, capture once as a hipGraph, replay); the loops of a state live in ``_GpuCache._loops``.
+Who owns what.  A loop in ``_loops`` owns its graph and, for the rectangular loops, its ``tok`` /
+``pos`` / ``seq`` (``_tok_state``); a weight change or a W8 flip (``_stamp``) drops every loop.  The
+decode state owns what outlives them: the caches, the ragged / beam / spec states (allocated on first
+use) and the three parameter blocks, whose pointers the captured steps bake in.
 
-Sampling: ``seed=None`` is the reference's recipe on torch's global generator (``_sample``).  With a
-seed the draw is counter-based Gumbel-max (``ops.reference.sample_gumbel``; on the GPU the sample
-kernel inside a device-side token loop, ``_GpuCache.sample``): reproducible per (seed, column, row).
-
-Ragged batches (``generate_batch``): prompts of different lengths, right-padded, decoded together;
-each row has its own position and finished flag in device memory (``_GpuCache.ragged``), stops at
-its own stop token, and computes what the single-prompt path computes for that row alone.
-
-Log-probabilities (``return_logprobs=True``, ``score``): the model's log-softmax of a token given
-its prefix (temperature 1, before top-k / top-p; the rule in common.h).  The device loops compute it
-inside the captured step -- the plain LM head, the lse kernel (``logits_lse``), then the pick kernel
-writing the number beside the token -- in loops of their own (``"greedy_lp"``, ``"sample_lp"``,
-``("ragged_lp", greedy)``), so the plain loops launch what they always did.  Greedy with
-log-probabilities does not go through the LM head's fused argmax: carrying the number through the
-argmax keys would need the previous step's {m, lnz} in the next step's embedding kernel and a host
-epilogue for the last token; its step is the ragged greedy step on equal positions instead, which
-ranks the same stored bf16 logits with the first index on ties.  Host loops use
-``ops.reference.token_logprob``.
-
-Logits processors (``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
-``no_repeat_ngram_size`` on ``generate`` / ``generate_batch``; the rule in common.h): an edit of the
-stored logits from the token history -- the context the model saw -- before anything picks from
-them.  On the device loops the process kernel (``logits_process``) runs right after the LM head inside
-the captured step, reads the history from the loop's own ``seq`` buffer (which therefore holds the
-window's context before a run) and its settings from a device parameter block (``_proc_params``), in
-loops of their own (``"sample_proc"``, ``"greedy_proc"``, ``("ragged_proc", greedy)`` and their
-``_lp`` forms): with every argument off nothing changes and no loop is added.  Greedy with a processor
-on is ``_greedy_lp``'s construction -- the LM head's fused argmax cannot see edited logits.  A window's
-first token is picked after one eager launch over the prefill logits (``process_prefill``).  Host
-loops use ``ops.reference.process_logits``.
-
-Beam search (``generate_beam``; the rule in common.h): W beams per prompt, scored by the running fp32
-sum of those log-probabilities.  The decode state has B * W rows and lives beside the plain one
-(``_beam_cache``), the prompt is prefilled once per prompt and broadcast, and the step -- ``_decode``
-at one batch-wide position, the row kernel, the merge, the in-place reorder of every layer's KV
-cache by parent beam -- is the loop ``("beam", W)`` (``_GpuCache.beam``).  The token history is never
-permuted: the sequences are rebuilt from the per-step parent / token histories at the end.  The CPU
-path runs ``ops.reference.beam_step`` on ``_CpuCache``.
-
-Speculative greedy decoding (``generate_speculative``; the rule in common.h): K = draft_len + 1 rows
-per sequence and step -- the last committed token and an n-gram (prompt-lookup) draft -- at K
-consecutive positions of one KV cache, keeping what the model's own argmax confirms.  The state has
-B sequences and B * K step rows and lives beside the others (``_spec_cache``); the step -- draft
-kernel, embedding, ``_blocks`` with the grouped decode attention, the plain LM head, row argmax,
-accept kernel -- is the loop ``("spec", K)`` (``_GpuCache.spec``).  The CPU path runs
-``ops.reference.ngram_draft`` / ``spec_accept`` around one model forward per step.
-
-Weight-only int8 (``quantize_int8_``; the W8 rule in common.h): the model's projection and LM-head
-weights are snapped in place to int8 rows times power-of-two scales, so every path here computes that
-model; on a marked model ``_lin``'s ``"gemv"`` route reads the int8 twins (``w8_weights``,
-``gemv_w8``) and produces the bf16 kernel's bits.  ``_W8_DECODE`` (``MINGPT_W8_DECODE=0``) keeps the
-bf16 kernel; which kernel the steps launch is part of a state's stamp, so a flip re-captures its loops.
+Loop keys (``_key``): ``"step"``; ``"greedy"`` (the LM head's fused argmax, or torch's on a small
+vocabulary) and ``"sample"`` (one batch-wide position, ``sample_logits``), each also as ``_lp`` (the
+lse kernel before the pick), ``_proc`` (the process kernel after the LM head) and ``_proc_lp``, the
+greedy ones on the ragged greedy pick (``_greedy_picked``); ``("ragged" | "ragged_lp" |
+"ragged_proc" | "ragged_proc_lp", greedy)``; ``("beam", W)``; ``("spec", K)``.
 """
 from __future__ import annotations
 
@@ -293,55 +251,39 @@ class _Loop:
                 self.logits = self.step()
 
 
-class _GpuCache:
-    """KV caches ([B, Tmax, 3D] qkv rows per layer) plus the captured decode steps (``_loops``) of
-    one model at one batch size.  Kept on the model across ``generate`` calls (``_gpu_cache``): a later call
-    with the same batch re-prefills into the same buffers and replays the same hipGraphs, unless
-    a weight changed storage or version since the capture (then the graphs are re-captured)."""
+class _Params:
+    """An 8-word int32 device parameter block (``dev``: captured steps bake its pointer in) and the
+    words last uploaded to it."""
 
-    def __init__(self, model, idx, tmax, last=None, rows=None):
-        """``rows`` (beam search): a state of that many decode rows whose layers' caches are one
-        stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks every layer in one
-        launch), not prefilled here -- ``idx`` only names the device."""
+    def __init__(self, device):
+        self.dev = torch.zeros(8, dtype=torch.int32, device=device)
+        self.words = None
+
+    def set(self, words, always=False):
+        """Upload ``words`` unless they are the block's already -- a host-to-device copy waits for the
+        queued replays to drain -- and return ``dev``.  ``always``: for a block that a kernel writes.
+        The sampled step advances the draw counter in word 2 on the device, so the record here is
+        stale after the first replay and every call has to upload."""
+        if always or self.words != list(words):
+            self.dev.copy_(torch.tensor(words, dtype=torch.int32))
+            self.words = list(words)
+        return self.dev
+
+
+class _Body:
+    """The step bodies' plumbing for one model (``_lin``, ``_blocks``, ``_head``, ``_prompt``) without
+    KV caches, workspaces or loops: all that ``score`` needs, and the base of a decode state."""
+
+    def __init__(self, model):
         from ..ops._ext import ext
         from ..ops import gemm as G
 
         model.config.check_gpu_support()
-        self.C, self.G, self.bf, self.w8 = ext(), G, bf16_weights(model), w8_weights(model)
-        self.model = model
-        self.tmax = tmax
-        B = idx.size(0) if rows is None else rows
-        cfg = model.config
-        D = cfg.n_embed
-        self.B = B
-        if rows is None:
-            self.caches = [torch.empty(B, tmax, 3 * D, device=idx.device, dtype=torch.bfloat16)
-                           for _ in range(cfg.n_layer)]
-        else:
-            self.kv = torch.empty(cfg.n_layer, B, tmax, 3 * D, device=idx.device, dtype=torch.bfloat16)
-            self.caches = list(self.kv.unbind(0))
-        # decode-attention workspace owned by this state (split partials + per-(b, h) counters
-        # that the kernel leaves zero): the captured graphs bake these pointers in
-        H = cfg.n_head
-        self.dec_part = torch.empty(self.C.attention_decode_part_floats(B, H, D // H),
-                                    device=idx.device, dtype=torch.float32)
-        self.dec_cnt = torch.zeros(B * H, device=idx.device, dtype=torch.int32)
-        self.stamp = self._stamp()
-        self._loops = {}  # the device-side token loops (_Loop) by name, built on first use
-        if rows is None:
-            self.prefill(idx, last)
-
-    @classmethod
-    def body_only(cls, model):
-        """The step bodies' plumbing (``_prompt``, ``_blocks``, ``_head``) without KV caches,
-        workspaces or loops: ``score`` runs one forward and never decodes."""
-        from ..ops._ext import ext
-        from ..ops import gemm as G
-
-        model.config.check_gpu_support()
-        self = cls.__new__(cls)
         self.C, self.G, self.bf, self.w8, self.model = ext(), G, bf16_weights(model), w8_weights(model), model
-        return self
+
+    def _w8_on(self):
+        """The skinny-GEMM projections read int8 twins: the model is marked and the switch is on."""
+        return _W8_DECODE and self.model.__dict__.get("_mg_w8", False)
 
     def _route(self, rows):
         """The GEMM a decode step of ``rows`` rows runs its projections on (``_lin``'s names).
@@ -374,13 +316,8 @@ class _GpuCache:
         if route == "gemv":
             lw, lb = (bf(ln.weight), bf(ln.bias)) if ln is not None else (None, None)
             tw = self.w8(w) if self._w8_on() else None  # (q, s): the int8 twin of a snapped weight
-            if am is not None:
-                if tw is not None:
-                    return C.gemv_w8(inp, tw[0], tw[1], code, None, None, ld, lw, lb, eps, am[0], am[1])
-                return C.gemv(inp, bf(w), code, None, None, ld, lw, lb, eps, am[0], am[1])
-            if tw is not None:
-                return C.gemv_w8(inp, tw[0], tw[1], code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
-            return C.gemv(inp, bf(w), code, bf(b) if b is not None else None, resid, ld, lw, lb, eps)
+            kernel, wt = (C.gemv, (bf(w),)) if tw is None else (C.gemv_w8, tw)
+            return kernel(inp, *wt, code, bf(b) if b is not None else None, resid, ld, lw, lb, eps, *(am or ()))
         if ln is not None:
             inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
         if route == "rows":
@@ -412,9 +349,9 @@ class _GpuCache:
         return self._lin(route, x_last, m.lm_head.weight, None, "none", ld=(V + 7) // 8 * 8,
                          ln=m.transformer.ln_f, am=am)
 
-    def _prompt(self, idx, keep=True):
-        """The blocks' output [B, T, D] for the prompt idx [B, T] on the MFMA GEMM path; ``keep``:
-        every layer's qkv rows go into the cache."""
+    def _prompt(self, idx, keep=None):
+        """The blocks' output [B, T, D] for the prompt idx [B, T] on the MFMA GEMM path; ``keep(i,
+        qkv)`` is handed every layer's qkv rows [B, T, 3D] (a decode state's cache)."""
         C, bf = self.C, self.bf
         tr, cfg = self.model.transformer, self.model.config
         B, T = idx.shape
@@ -422,13 +359,60 @@ class _GpuCache:
         x = C.embedding_fwd(idx.contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0).view(B * T, D)
 
         def attend(i, qkv):
-            if keep and self.caches[i].size(0) == B:
-                self.caches[i][:, :T].copy_(qkv.view(B, T, 3 * D))
-            elif keep:  # a beam state: the prompt's rows go to each of its beams
-                self.caches[i].view(B, -1, self.tmax, 3 * D)[:, :, :T].copy_(qkv.view(B, 1, T, 3 * D))
+            if keep is not None:
+                keep(i, qkv.view(B, T, 3 * D))
             return C.attention_fwd(qkv, B, T, H, 0.0, 0)[0]
 
         return self._blocks(x, attend, "mfma").view(B, T, D)
+
+
+class _GpuCache(_Body):
+    """One decode state: KV caches ([B, Tmax, 3D] qkv rows per layer) plus the captured decode steps
+    (``_loops``) of one model at one batch size.  Kept on the model across calls (``_state_for``): a
+    later ``generate`` with the same batch re-prefills into the same buffers and replays the same
+    hipGraphs, unless a weight changed storage or version since the capture (then the graphs are
+    re-captured)."""
+
+    def __init__(self, model, idx, tmax, last=None, rows=None):
+        """``rows`` (beam search, speculative decoding): a state of that many decode rows whose
+        layers' caches are one stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks
+        every layer in one launch), not prefilled here -- ``idx`` only names the device."""
+        super().__init__(model)
+        self.tmax, self.dev = tmax, idx.device
+        B = idx.size(0) if rows is None else rows
+        cfg = model.config
+        D = cfg.n_embed
+        self.B = B
+        self.kv = None
+        if rows is None:
+            self.caches = [torch.empty(B, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
+                           for _ in range(cfg.n_layer)]
+        else:
+            self.kv = torch.empty(cfg.n_layer, B, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
+            self.caches = list(self.kv.unbind(0))
+        # decode-attention workspace owned by this state (split partials + per-(b, h) counters
+        # that the kernel leaves zero): the captured graphs bake these pointers in
+        H = cfg.n_head
+        self.dec_part = torch.empty(self.C.attention_decode_part_floats(B, H, D // H),
+                                    device=self.dev, dtype=torch.float32)
+        self.dec_cnt = torch.zeros(B * H, device=self.dev, dtype=torch.int32)
+        self.stamp = self._stamp()
+        self._loops = {}  # the device-side token loops (_Loop) by key, built on first use
+        # what outlives the loops: the sample, ragged-pick and process kernels' parameter blocks, and
+        # the ragged / beam (by W) / speculative (by K) states, allocated on first use
+        self._sparams, self._rparams, self._pparams = (_Params(self.dev) for _ in range(3))
+        self._rstate, self._bstate, self._sstate = None, {}, {}
+        self.logits = None
+        if rows is None:
+            self.prefill(idx, last)
+
+    def _keep(self, i, qkv):
+        """Layer i's qkv rows [B, T, 3D] of a prompt into its cache."""
+        B, T, D3 = qkv.shape
+        if self.caches[i].size(0) == B:
+            self.caches[i][:, :T].copy_(qkv)
+        else:  # a beam state: the prompt's rows go to each of its beams
+            self.caches[i].view(B, -1, self.tmax, D3)[:, :, :T].copy_(qkv.view(B, 1, T, D3))
 
     def prefill(self, idx, last=None):
         """Run the prompt idx [B, T] on the MFMA GEMM path, keep every layer's qkv rows as the
@@ -436,7 +420,7 @@ class _GpuCache:
         those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
         cfg = self.model.config
         B = idx.size(0)
-        x = self._prompt(idx)
+        x = self._prompt(idx, self._keep)
         if last is not None:  # right-padded prefill: row b's hidden state at its own last token
             x = x[torch.arange(B, device=x.device), last]
         else:
@@ -465,10 +449,6 @@ class _GpuCache:
                                                               self.dec_cnt, pos_stride), route)
         return self._head(x, route, am=(am_part, pos) if am_part is not None else None)
 
-    def _w8_on(self):
-        """The skinny-GEMM projections read int8 twins: the model is marked and the switch is on."""
-        return _W8_DECODE and self.model.__dict__.get("_mg_w8", False)
-
     def _stamp(self):
         # the weights' stamp and which skinny GEMM the steps launch: a loop captured for one kernel
         # is never replayed for the other
@@ -489,11 +469,45 @@ class _GpuCache:
         return self._loops[key]
 
     @staticmethod
-    def _seed(st, tok, pos):
-        """Point a rectangular loop's device state at token ``tok`` [B, 1] at position ``pos``."""
+    def _key(base, proc, logprobs):
+        """The key of a picked loop: ``base``, ``_proc`` with the process kernel in its step, ``_lp``
+        with the lse kernel."""
+        return base + ("_proc" if proc else "") + ("_lp" if logprobs else "")
+
+    def _tok_state(self, per_row, cols, lp, tok=None, pos=0):
+        """The device state of a token loop: ``tok`` int64 [B, 1] (the newest token, the next step's
+        input), ``pos`` int32 (its position: [B] with ``per_row``, beside a finished flag ``done``
+        int32 [B]; else [1] for the batch), ``seq`` int64 [B, cols] (the tokens by column) and with
+        ``lp`` their log-probabilities ``lp`` float32 [B, cols]; ``hpos``: ``_decode``'s."""
+        B = self.B if tok is None else tok.shape[0]
+        zeros = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.dev)
+        st = {"tok": zeros(B, 1, dtype=torch.long) if tok is None else tok.clone(),
+              "pos": torch.full((B if per_row else 1,), pos, dtype=torch.int32, device=self.dev),
+              "seq": zeros(B, cols, dtype=torch.long), "hpos": max(pos, 1)}
+        if per_row:
+            st["done"] = zeros(B, dtype=torch.int32)
+        if lp:
+            st["lp"] = zeros(B, cols, dtype=torch.float32)
+        return st
+
+    @staticmethod
+    def _seed(st, tok, pos, ctx=None):
+        """Point a rectangular loop's device state at token ``tok`` [B, 1] at position ``pos``.
+        ``ctx`` [B, pos] (the processors are on), the window's context: ``seq`` holds it in columns
+        0 .. pos - 1 and ``tok`` at column pos, since the process kernel reads the history from there."""
         st["tok"].copy_(tok)
         st["pos"].fill_(pos)
         st["hpos"] = max(pos, 1)
+        if ctx is not None:
+            st["seq"][:, :pos].copy_(ctx)
+            st["seq"][:, pos:pos + 1].copy_(tok)
+
+    @staticmethod
+    def _picked(st, pos, n, logprobs):
+        """What a run of n steps from position ``pos`` left in ``seq``: the new tokens [B, n], with
+        ``logprobs`` (tokens, lp [B, n])."""
+        toks = st["seq"][:, pos + 1:pos + 1 + n]
+        return (toks, st["lp"][:, pos + 1:pos + 1 + n]) if logprobs else toks
 
     def step(self, tok, pos):
         """One decode step with token ``tok`` [B, 1] at position ``pos``, over static token /
@@ -522,30 +536,18 @@ class _GpuCache:
         launch, and a state that owns an ``lp`` buffer from an earlier call does not pass it."""
         return (self.C.logits_lse(logits, V), st["lp"]) if logprobs else (None, None)
 
-    def _proc_params(self, words):
-        """The device parameter block of the process kernel (``_proc_words``), owned by this state:
-        the captured steps that apply the processors bake the pointer in.  An unchanged block is not
-        uploaded again, as for ``_ragged_params``."""
-        p = self.__dict__.get("_pparams")
-        if p is None:
-            p = self._pparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
-            self._pwords = None
-        if self._pwords != list(words):
-            p.copy_(torch.tensor(words, dtype=torch.int32))
-            self._pwords = list(words)
-        return p
-
     def _process(self, logits, st, pos_stride, done=None):
         """The process kernel on a step's ``logits`` in place: row b's history is columns 0 ..
-        pos[b] of the state's own ``seq``, which the step's pick kernel extends."""
+        pos[b] of the state's own ``seq``, which the step's pick kernel extends.  Its settings are
+        this state's process block (``_proc_words``), set by the caller."""
         self.C.logits_process(logits, self.model.config.vocab_size, st["seq"][:, :self.tmax], st["pos"], pos_stride,
-                              done, self._pparams)
+                              done, self._pparams.dev)
 
     def process_prefill(self, ctx, proc):
         """Edit the prefill logits in place with the processors ``proc`` (``_proc_words``) over the
         context ``ctx`` [B, L] they were computed from: one eager launch before a window's first pick."""
         pos = torch.full((1,), ctx.size(1) - 1, dtype=torch.int32, device=ctx.device)
-        self.C.logits_process(self.logits, self.model.config.vocab_size, ctx, pos, 0, None, self._proc_params(proc))
+        self.C.logits_process(self.logits, self.model.config.vocab_size, ctx, pos, 0, None, self._pparams.set(proc))
 
     def _ragged_step(self, st, greedy, logprobs, proc=False):
         """The decode step over per-row state ``st`` (``pos``, ``done``, ``tok``, ``seq``, ``params``,
@@ -564,78 +566,42 @@ class _GpuCache:
 
         return step
 
-    def greedy_proc(self, tok, pos, n, proc, ctx, logprobs=False):
-        """``greedy`` with the logits processors ``proc`` (``_proc_words``) on: the n new tokens [B,
-        n], with ``logprobs`` (tokens, lp).  The LM head's fused argmax cannot see edited logits, so
-        this is ``_greedy_lp``'s construction -- the ragged greedy step on equal positions over a
-        state of its own, no stop token -- with the process kernel in front of the pick: loops
-        ``"greedy_proc"`` / ``"greedy_proc_lp"``.  ``ctx`` [B, pos] is the window's context: the
-        state's ``seq`` holds it in columns 0 .. pos - 1 and ``tok`` at column pos before the run,
-        since the kernel reads the history from there."""
-        assert pos + n <= self.tmax
-        B = tok.shape[0]
-        self._proc_params(proc)
+    def _greedy_picked(self, tok, pos, n, logprobs, proc, ctx):
+        """``greedy`` with log-probabilities and / or the logits processors ``proc`` (``_proc_words``,
+        with the window's context ``ctx``): loops ``"greedy_lp"``, ``"greedy_proc"``,
+        ``"greedy_proc_lp"``.  Not the LM head's fused argmax, whose keys have no room for the number
+        and which cannot see edited logits, but the ragged greedy step (``_ragged_step``) on equal
+        positions over a state of its own, with no stop token.  Both rank the stored bf16 logits
+        with the first index on ties.  ``seq`` / ``lp`` are one column longer than the ragged
+        state's: the pick kernel keeps the position below the last column, and a window's last
+        token sits at column tmax."""
+        on = proc is not None
+        if on:
+            self._pparams.set(proc)
 
         def make():
-            dev = tok.device
-            st = {"tok": tok.clone(), "pos": torch.full((B,), pos, dtype=torch.int32, device=dev),
-                  "done": torch.zeros(B, dtype=torch.int32, device=dev),
-                  "seq": torch.zeros(B, self.tmax + 2, dtype=torch.long, device=dev),
-                  "params": torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=dev)}
-            if logprobs:
-                st["lp"] = torch.zeros(B, self.tmax + 2, dtype=torch.float32, device=dev)
-            return _Loop(self._ragged_step(st, True, logprobs, proc=True), st)
+            st = self._tok_state(True, self.tmax + 2, logprobs, tok, pos)
+            st["params"] = torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=self.dev)
+            return _Loop(self._ragged_step(st, True, logprobs, proc=on), st)
 
-        lp = self._loop("greedy_proc_lp" if logprobs else "greedy_proc", make)
-        st = lp.state
-        st["tok"].copy_(tok)  # after the loop is built: its warm-up step moved the state
-        st["pos"].fill_(pos)
-        st["seq"][:, :pos].copy_(ctx)
-        st["seq"][:, pos:pos + 1].copy_(tok)
+        lp = self._loop(self._key("greedy", on, logprobs), make)
+        self._seed(lp.state, tok, pos, ctx if on else None)  # again: the warm-up step moved the state
         lp.run(n)
-        toks = st["seq"][:, pos + 1:pos + 1 + n]
-        return (toks, st["lp"][:, pos + 1:pos + 1 + n]) if logprobs else toks
+        return self._picked(lp.state, pos, n, logprobs)
 
-    def _greedy_lp(self, tok, pos, n):
-        """``greedy`` with log-probabilities: (tokens [B, n], lp [B, n]).  A loop of its own
-        (``"greedy_lp"``) on the ragged greedy step with log-probabilities (``_ragged_step``: the
-        plain LM head, the lse kernel and the ragged greedy pick kernel) over a state of its own,
-        with every row at the same position and no stop token -- not the fused argmax of the LM
-        head, whose keys have no room for the number.  Both rank the stored bf16 logits with the
-        first index on ties.  ``seq`` / ``lp`` are one column longer than the ragged state's: the
-        pick kernel keeps the position below the last column, and a window's last token sits at
-        column tmax."""
-        B = tok.shape[0]
-
-        def make():
-            dev = tok.device
-            st = {"tok": tok.clone(), "pos": torch.full((B,), pos, dtype=torch.int32, device=dev),
-                  "done": torch.zeros(B, dtype=torch.int32, device=dev),
-                  "seq": torch.zeros(B, self.tmax + 2, dtype=torch.long, device=dev),
-                  "lp": torch.zeros(B, self.tmax + 2, dtype=torch.float32, device=dev),
-                  "params": torch.tensor(_ragged_words(0, 1.0, None, None), dtype=torch.int32, device=dev)}
-            return _Loop(self._ragged_step(st, True, True), st)
-
-        lp = self._loop("greedy_lp", make)
-        st = lp.state
-        st["tok"].copy_(tok)  # after the loop is built: its warm-up step moved the state
-        st["pos"].fill_(pos)
-        lp.run(n)
-        return st["seq"][:, pos + 1:pos + 1 + n], st["lp"][:, pos + 1:pos + 1 + n]
-
-    def greedy(self, tok, pos, n, logprobs=False):
+    def greedy(self, tok, pos, n, logprobs=False, proc=None, ctx=None):
         """n greedy decode steps starting with token ``tok`` [B, 1] at position ``pos``: the step
         takes its input token and position from device buffers that its own kernels advance (the
         fused argmax of ``_decode`` when the rows fit the skinny GEMM -- B <= 8, 4 * n_embed <= 8192
         -- and V > 8192; otherwise the argmax in torch).  Returns the n
         new tokens [B, n] (positions pos + 1 .. pos + n); with ``logprobs`` also their
-        log-probabilities [B, n] (``_greedy_lp``)."""
+        log-probabilities [B, n], and with ``proc`` the argmax of the processed rows
+        (``_greedy_picked``)."""
         assert pos + n <= self.tmax
-        if logprobs:
-            return self._greedy_lp(tok, pos, n)
+        if logprobs or proc is not None:
+            return self._greedy_picked(tok, pos, n, logprobs, proc, ctx)
         B = tok.shape[0]
-        cfg = self.model.config
-        V = cfg.vocab_size
+        V = self.model.config.vocab_size
 
         def seed(st):
             self._seed(st, tok, pos)
@@ -644,12 +610,10 @@ class _GpuCache:
                 st["part"][:, :1].copy_(-1 - tok)  # bits 0xffffffff_(0xffffffff - tok)
 
         def make():
-            dev = tok.device
             fused = self._route(B) == "gemv" and V > 8192
-            st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
-                  "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
-                  "part": (torch.zeros(B, self.C.gemv_argmax_groups(V, B), dtype=torch.long, device=dev)
-                           if fused else None)}
+            st = self._tok_state(False, self.tmax + 1, False, tok, pos)
+            st["part"] = (torch.zeros(B, self.C.gemv_argmax_groups(V, B), dtype=torch.long, device=self.dev)
+                          if fused else None)
             seed(st)
             if fused:
                 return _Loop(lambda: self._decode(st["tok"], st["pos"], st["hpos"], am_part=st["part"],
@@ -670,53 +634,38 @@ class _GpuCache:
         seed(st)  # again: the warm-up step moved the state
         lp.run(n)
         if st["part"] is None:
-            return st["seq"][:, pos + 1:pos + 1 + n]
+            return self._picked(st, pos, n, False)
         # the last step's token is still in its LM-head keys: reduce them here (unsigned max =
         # signed max after flipping the top bit; low word = 0xffffffff - column)
         k = (st["part"] ^ _I64_MIN).max(dim=1).values ^ _I64_MIN
         last = 0xFFFFFFFF - (k & 0xFFFFFFFF)
         return torch.cat([st["seq"][:, pos + 1:pos + n], last.view(B, 1)], dim=1)
 
-    def _sample_params(self, words):
-        """The device parameter block of the sample kernel, owned by the sampled loop (its
-        captured step bakes the pointer in) and used by ``sample_prefill``, set to ``words``
-        (``_sample_words``)."""
-        p = self.__dict__.get("_sparams")
-        if p is None:
-            p = self._sparams = torch.zeros(8, dtype=torch.int32, device=self.caches[0].device)
-        p.copy_(torch.tensor(words, dtype=torch.int32))
-        return p
-
     def sample_prefill(self, words):
         """The token [B] drawn from the prefill logits (the first token of a context window)."""
-        return self.C.sample_logits(self.logits, self.model.config.vocab_size, self._sample_params(words))
+        return self.C.sample_logits(self.logits, self.model.config.vocab_size, self._sparams.set(words, always=True))
 
     def sample(self, tok, pos, n, words, logprobs=False, proc=None, ctx=None):
         """n sampled decode steps starting with token ``tok`` [B, 1] at position ``pos``: each step
         is the plain LM head followed by the sample kernel, which writes the next token into the
         buffer the next step's embedding reads and advances the device position and draw counter.
-        Seed, temperature, top-k and top-p live in the device parameter block (``words``), so the one
-        captured step serves every call.  Returns the n new tokens [B, n] (positions pos + 1 ..
-        pos + n).  ``logprobs``: a loop of its own (``"sample_lp"``) with the lse kernel between the
-        LM head and the sampler, which writes each token's log-probability beside it; returns
-        (tokens, lp [B, n]).  ``proc`` (``_proc_words``; with ``ctx`` [B, pos], the window's context):
-        loops of their own again (``"sample_proc"`` / ``"sample_proc_lp"``) with the process kernel
-        right after the LM head; it reads the history from the loop's ``seq``, which therefore holds
-        ``ctx`` in columns 0 .. pos - 1 and ``tok`` at column pos before the run."""
+        Seed, temperature, top-k and top-p live in the device parameter block (``words``,
+        ``_sample_words``), so the one captured step serves every call; the kernel advances the
+        block's draw counter, so every call uploads it.  Returns the n new tokens [B, n] (positions
+        pos + 1 .. pos + n).  ``logprobs``: a loop of its own (``"sample_lp"``) with the lse kernel
+        between the LM head and the sampler, which writes each token's log-probability beside it;
+        returns (tokens, lp [B, n]).  ``proc`` (``_proc_words``; with ``ctx`` [B, pos], the window's
+        context): loops of their own again (``"sample_proc"`` / ``"sample_proc_lp"``) with the process
+        kernel right after the LM head."""
         assert pos + n <= self.tmax
-        B = tok.shape[0]
         V = self.model.config.vocab_size
         on = proc is not None
         if on:
-            self._proc_params(proc)
+            self._pparams.set(proc)
 
         def make():
-            dev = tok.device
-            st = {"tok": tok.clone(), "pos": torch.full((1,), pos, dtype=torch.int32, device=dev),
-                  "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev), "hpos": max(pos, 1)}
-            if logprobs:
-                st["lp"] = torch.zeros(B, self.tmax + 1, dtype=torch.float32, device=dev)
-            params = self._sample_params(words)
+            st = self._tok_state(False, self.tmax + 1, logprobs, tok, pos)
+            params = self._sparams.set(words, always=True)
 
             def step():
                 logits = self._decode(st["tok"], st["pos"], st["hpos"])
@@ -728,15 +677,11 @@ class _GpuCache:
 
             return _Loop(step, st)
 
-        lp = self._loop(("sample_proc" if on else "sample") + ("_lp" if logprobs else ""), make)
-        self._seed(lp.state, tok, pos)
-        if on:
-            lp.state["seq"][:, :pos].copy_(ctx)
-            lp.state["seq"][:, pos:pos + 1].copy_(tok)
-        self._sample_params(words)
+        lp = self._loop(self._key("sample", on, logprobs), make)
+        self._seed(lp.state, tok, pos, ctx if on else None)
+        self._sparams.set(words, always=True)
         lp.run(n)
-        toks = lp.state["seq"][:, pos + 1:pos + 1 + n]
-        return (toks, lp.state["lp"][:, pos + 1:pos + 1 + n]) if logprobs else toks
+        return self._picked(lp.state, pos, n, logprobs)
 
     # ----------------------------------------------------------------- ragged batches
     def ragged_state(self):
@@ -745,24 +690,10 @@ class _GpuCache:
         the row's newest token), ``done`` int32 [B], ``tok`` int64 [B, 1] (the newest token, the
         next step's input), ``seq`` int64 [B, tmax + 1] and the pick kernels' own parameter block
         ``params``."""
-        st = self.__dict__.get("_rstate")
-        if st is None:
-            dev, B = self.caches[0].device, self.B
-            st = self._rstate = {"pos": torch.zeros(B, dtype=torch.int32, device=dev),
-                                 "done": torch.zeros(B, dtype=torch.int32, device=dev),
-                                 "tok": torch.zeros(B, 1, dtype=torch.long, device=dev),
-                                 "seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev),
-                                 "params": torch.zeros(8, dtype=torch.int32, device=dev)}
-            self._rwords = None  # the words last uploaded to params (_ragged_params)
-        return st
-
-    def _ragged_params(self, st, words):
-        """Set the ragged parameter block, which the pick kernels only read and nothing else
-        writes: an unchanged block is not uploaded again (a host-to-device copy waits for the
-        queued replays to drain)."""
-        if self._rwords != list(words):
-            st["params"].copy_(torch.tensor(words, dtype=torch.int32))
-            self._rwords = list(words)
+        if self._rstate is None:
+            self._rstate = self._tok_state(True, self.tmax + 1, False)
+            self._rstate["params"] = self._rparams.dev
+        return self._rstate
 
     def ragged_start(self, idx, lengths, words, greedy, logprobs=False, proc=None):
         """Point the ragged state at a prefilled right-padded batch ``idx`` [B, Tp] with ``lengths``
@@ -781,10 +712,10 @@ class _GpuCache:
         st["seq"][:, :idx.size(1)].copy_(idx)
         st["pos"].copy_(lengths - 1)
         st["done"].zero_()
-        self._ragged_params(st, words)
+        self._rparams.set(words)
         logits = self.logits  # [B, V] view of the padded [B, ld] buffer the LM head wrote
         if proc is not None:
-            self._proc_params(proc)
+            self._pparams.set(proc)
             self._process(logits, st, 1, st["done"])
         self.C.pick_ragged(logits, logits.size(1), st["params"], st["pos"], st["done"], st["tok"], st["seq"],
                            greedy, *self._lp_args(logits, logits.size(1), st, logprobs))
@@ -806,10 +737,10 @@ class _GpuCache:
         ``("ragged_proc_lp", greedy)``) with the process kernel right after the LM head, reading each
         row's history from ``seq``."""
         st = self.ragged_state()
-        self._ragged_params(st, words)
+        self._rparams.set(words)
         on = proc is not None
         if on:
-            self._proc_params(proc)
+            self._pparams.set(proc)
         step = self._ragged_step(st, greedy, logprobs, proc=on)
 
         def warm():  # with every row marked finished the step is idempotent: the state the caller
@@ -818,8 +749,7 @@ class _GpuCache:
             step()
             st["done"].copy_(done)
 
-        key = ("ragged_proc" if on else "ragged") + ("_lp" if logprobs else "")
-        self._loop((key, greedy), lambda: _Loop(step, st, warm)).run(n)
+        self._loop((self._key("ragged", on, logprobs), greedy), lambda: _Loop(step, st, warm)).run(n)
         return st
 
     # ----------------------------------------------------------------- beam search
@@ -831,9 +761,9 @@ class _GpuCache:
         ``score`` fp32, ``fin`` / ``len`` / ``parent`` int32 [R], the row kernel's candidates and
         ``lse``, and the per-step histories ``hparent`` / ``htok`` (int32 [B, W, tmax + 1]) and
         ``hscore`` (fp32), indexed by the column of the step's token in the sequence."""
-        states = self.__dict__.setdefault("_bstate", {})
+        states = self._bstate
         if W not in states:
-            dev, R = self.caches[0].device, self.B
+            dev, R = self.dev, self.B
             assert R % W == 0
             i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
             f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
@@ -881,7 +811,7 @@ class _GpuCache:
         """Prefill the B prompts idx [B, T] once: every layer's qkv rows go to the W beams of their
         prompt (``_prompt``), and the last position's padded logits [B, ld] come back W times over,
         [B * W, ld] -- the input of the first beam step."""
-        x = self._prompt(idx)[:, -1]
+        x = self._prompt(idx, self._keep)[:, -1]
         full = self._head(x.contiguous(), "mfma")
         self.logits = full[:, :self.model.config.vocab_size]
         return full.repeat_interleave(W, dim=0)
@@ -908,9 +838,9 @@ class _GpuCache:
         rows ``tok`` int64 [B * K, 1] / ``pos_rows`` int32 [B * K] / ``has`` int32 [B] / ``g`` int32
         [B * K], the statistics ``steps`` int32 [B] and ``hist`` int32 [B, K + 1], and the grouped
         decode attention's workspace for B * K rows."""
-        states = self.__dict__.setdefault("_sstate", {})
+        states = self._sstate
         if K not in states:
-            dev, B, cfg = self.caches[0].device, self.B, self.model.config
+            dev, B, cfg = self.dev, self.B, self.model.config
             H = cfg.n_head
             i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
             states[K] = {"seq": torch.zeros(B, self.tmax + 1, dtype=torch.long, device=dev), "pos": i32(B),
@@ -974,14 +904,18 @@ class _GpuCache:
 _I64_MIN = -(1 << 63)
 
 
+def _f32_bits(v):
+    """float32(v) as the int32 word of a parameter block."""
+    return struct.unpack("<i", struct.pack("<f", v))[0]
+
+
 def _sample_words(seed, draw, temperature, top_k, top_p=None):
     """The sample kernel's parameter block as 8 int32: seed low / high word, draw counter,
     float32(1 / temperature) as bits, top_k (0: off), 0, float32(top_p) as bits (0: off), 0."""
     s32 = lambda x: ((x & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
-    inv_t = struct.unpack("<i", struct.pack("<f", 1.0 / temperature))[0]
     p = R.sample_top_p(top_p)
-    p_bits = 0 if p is None else struct.unpack("<i", struct.pack("<f", p))[0]
-    return [s32(seed), s32(seed >> 32), s32(draw), inv_t, min(int(top_k or 0), 0x7FFFFFFF), 0, p_bits, 0]
+    return [s32(seed), s32(seed >> 32), s32(draw), _f32_bits(1.0 / temperature), min(int(top_k or 0), 0x7FFFFFFF),
+            0, 0 if p is None else _f32_bits(p), 0]
 
 
 _PROC_HIST_MAX = 4096  # history entries the process kernel stages (kernels.h kProcHistMax)
@@ -991,9 +925,8 @@ def _proc_words(repetition_penalty, presence_penalty, frequency_penalty, no_repe
     """The process kernel's parameter block as 8 int32 (the rule in common.h, 'Logits processors'):
     float32(repetition_penalty), float32(1 / repetition_penalty), float32(presence_penalty) and
     float32(frequency_penalty) as bits, no_repeat_ngram_size, 0, 0, 0."""
-    bits = lambda v: struct.unpack("<i", struct.pack("<f", v))[0]
     vals = R.process_values(repetition_penalty, presence_penalty, frequency_penalty)
-    return [bits(v) for v in vals] + [int(no_repeat_ngram_size), 0, 0, 0]
+    return [_f32_bits(v) for v in vals] + [int(no_repeat_ngram_size), 0, 0, 0]
 
 
 def _processors(who, model, kernel, repetition_penalty, presence_penalty, frequency_penalty, no_repeat_ngram_size):
@@ -1021,15 +954,50 @@ def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
     return w
 
 
-def _gpu_cache(model, idx, tmax, last=None):
-    """The model's decode state for this batch size (re-prefilled), or a new one."""
-    c = model.__dict__.get("_mg_decode_cache")
-    if c is not None and c.B == idx.size(0) and c.tmax == tmax and c.caches[0].device == idx.device:
+def _state_for(model, slot, idx, tmax, rows=None, last=None):
+    """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, or beside it ``_mg_beam_cache``
+    / ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain
+    loops and their graphs alone -- or a new one when the device, the rows or ``tmax`` differ.  The
+    plain state comes back prefilled with ``idx`` (``last``: ``_GpuCache.prefill``); the others are
+    prefilled by their callers, after the loop is built."""
+    c = model.__dict__.get(slot)
+    if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
+        c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows)
+    elif rows is None:
         c.prefill(idx, last)
-        return c
-    c = _GpuCache(model, idx, tmax, last)
-    model.__dict__["_mg_decode_cache"] = c
     return c
+
+
+def _replay(run, n, flags, eos_token):
+    """``run(k)`` for n captured steps in all; returns the steps taken.  With a stop token (without
+    one nothing finishes early) and ``_EARLY_EXIT`` the device's finished ``flags`` are read every
+    ``_EXIT_EVERY`` steps, and the rest is left out once every one is set."""
+    check, left = _EARLY_EXIT and eos_token is not None, n
+    while left > 0:
+        k = min(left, _EXIT_EVERY) if check else left
+        run(k)
+        left -= k
+        if check and left > 0 and bool(flags.all()):
+            break
+    return n - left
+
+
+def _check_entry(who, model, max_new_tokens, idx=None, longest=None):
+    """ValueError unless ``idx`` is a rectangular int64 prompt batch (or, for ragged prompts, given
+    their ``longest``), ``max_new_tokens`` >= 0 and both fit ``block_size``; returns int(max_new_tokens)."""
+    what, T = "longest prompt", longest
+    if longest is None:
+        if not (torch.is_tensor(idx) and idx.dim() == 2 and idx.dtype == torch.long and idx.size(0) >= 1
+                and idx.size(1) >= 1):
+            raise ValueError(f"{who}: idx must be an int64 [B, T] tensor with B, T >= 1")
+        what, T = "prompt", idx.size(1)
+    n, bs = int(max_new_tokens), model.block_size
+    if n < 0:
+        raise ValueError(f"{who}: max_new_tokens must be >= 0, got {max_new_tokens}")
+    if T + n > bs:
+        raise ValueError(f"{who}: {what} ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
+                         f"point has no sliding window")
+    return n
 
 
 @torch.no_grad()
@@ -1117,17 +1085,14 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
                                                          proc=pwords, ctx=ctx)
         else:
             first = lambda c, T, ctx: c.logits.argmax(-1)
-            if proc is None:
-                loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs)
-            else:
-                loop = lambda c, tok, L, n, T, ctx: c.greedy_proc(tok, L, n, pwords, ctx, logprobs=return_logprobs)
+            loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs, proc=pwords, ctx=ctx)
         return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
         if cache is None or T > bs:
             idx_cond = idx if T <= bs else idx[:, -bs:]
-            cache = _gpu_cache(model, idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond)
+            cache = _state_for(model, "_mg_decode_cache", idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond)
             cache.pos = idx_cond.size(1)
             logits = cache.logits
         logits = edit(logits, idx[:, max(0, T - bs):])
@@ -1169,7 +1134,7 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
-        cache = _gpu_cache(model, ctx, bs)
+        cache = _state_for(model, "_mg_decode_cache", ctx, bs)
         if proc is not None:
             cache.process_prefill(ctx, proc)
         tok = first(cache, T, ctx)
@@ -1254,14 +1219,10 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     replayed back to back (``_GpuCache.ragged``): per-row positions and finished flags live in
     device memory.  On the CPU each row runs through the cache path on its own."""
     rows, device = _ragged_prompts(prompts)
-    V, bs = model.config.vocab_size, model.block_size
+    V = model.config.vocab_size
     lens = [r.numel() for r in rows]
     B, Lmax = len(rows), max(lens)
-    if max_new_tokens < 0:
-        raise ValueError(f"generate_batch: max_new_tokens must be >= 0, got {max_new_tokens}")
-    if Lmax + max_new_tokens > bs:
-        raise ValueError(f"generate_batch: longest prompt ({Lmax}) + max_new_tokens ({max_new_tokens}) exceeds "
-                         f"block_size ({bs}); this entry point has no sliding window")
+    _check_entry("generate_batch", model, max_new_tokens, longest=Lmax)
     _check_token_ids("generate_batch", V, torch.cat(rows), pad_token, eos_token)
     R.check_sample_args(temperature, top_k, top_p)
     proc, pwords = _processors("generate_batch", model, device.type == "cuda", repetition_penalty, presence_penalty,
@@ -1313,18 +1274,12 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     at the generated positions) as a third result.  ``proc`` (``_proc_words``): the loops with the
     process kernel in front of the pick, the first pick included."""
     B, Lmax = idx.shape
-    cache = _gpu_cache(model, idx, model.block_size, last=lengths - 1)
+    cache = _state_for(model, "_mg_decode_cache", idx, model.block_size, last=lengths - 1)
     words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
     st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs, proc=proc)
-    n = max_new_tokens - 1
-    check = _EARLY_EXIT and eos_token is not None  # without a stop token no row finishes early
-    while n > 0:
-        k = min(n, _EXIT_EVERY) if check else n
-        cache.ragged(k, words, greedy, logprobs=logprobs, proc=proc)
-        n -= k
-        if check and n > 0 and bool(st["done"].all()):
-            break
+    _replay(lambda k: cache.ragged(k, words, greedy, logprobs=logprobs, proc=proc), max_new_tokens - 1, st["done"],
+            eos_token)
     out_len = st["pos"].long() + 1
     W = Lmax + max_new_tokens
     cols = torch.arange(W, device=idx.device).view(1, W)
@@ -1379,21 +1334,13 @@ def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Op
     rebuilt at the end from the per-step parent / token histories.  On the CPU the same loop runs
     ``ops.reference.beam_step`` on ``_CpuCache``."""
     who = "generate_beam"
-    if not (torch.is_tensor(idx) and idx.dim() == 2 and idx.dtype == torch.long and idx.size(0) >= 1
-            and idx.size(1) >= 1):
-        raise ValueError(f"{who}: idx must be an int64 [B, T] tensor with B, T >= 1")
-    V, bs = model.config.vocab_size, model.block_size
+    n = _check_entry(who, model, max_new_tokens, idx)
+    V, W = model.config.vocab_size, int(num_beams)
     B, T = idx.shape
-    W, n = int(num_beams), int(max_new_tokens)
-    if n < 0:
-        raise ValueError(f"{who}: max_new_tokens must be >= 0, got {max_new_tokens}")
     if not 1 <= W <= _BEAM_MAX:
         raise ValueError(f"{who}: num_beams must be in 1..{_BEAM_MAX}, got {num_beams}")
     if W > V:
         raise ValueError(f"{who}: num_beams ({W}) exceeds the vocabulary size ({V})")
-    if T + n > bs:
-        raise ValueError(f"{who}: prompt ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
-                         f"point has no sliding window")
     _check_token_ids(who, V, idx, pad_token, eos_token)
     a = float(length_penalty)
     device = idx.device
@@ -1449,17 +1396,6 @@ def _generate_beam_cpu(model, idx, n, W, eos_token, pad_token):
     return torch.stack(hparent, dim=2), torch.stack(htok, dim=2), lens, s.float()
 
 
-def _beam_cache(model, idx, W, tmax):
-    """The model's beam decode state of B * W rows, kept beside (not in place of) the plain decode
-    state: beam calls leave the plain loops and their graphs alone."""
-    rows = idx.size(0) * W
-    c = model.__dict__.get("_mg_beam_cache")
-    if c is None or c.B != rows or c.tmax != tmax or c.caches[0].device != idx.device:
-        c = _GpuCache(model, idx, tmax, rows=rows)
-        model.__dict__["_mg_beam_cache"] = c
-    return c
-
-
 def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token):
     """The GPU half of ``generate_beam``: build (once) the beam loop of the B * W-row state, prefill
     the B prompts, take the first beam step on the prefill's logits, then replay the captured step
@@ -1468,18 +1404,10 @@ def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token):
     padding (``_beam_backtrack``), so stopping changes no result.  Returns the host histories of
     the steps taken, the lengths [B, W] and the scores [B, W]."""
     B, T = idx.shape
-    cache = _beam_cache(model, idx, W, model.block_size)
+    cache = _state_for(model, "_mg_beam_cache", idx, model.block_size, rows=B * W)
     loop = cache.beam(W)  # before the prefill: building it runs a warm-up step
     st = cache.beam_start(W, T, cache.beam_prefill(idx, W), eos_token, pad_token)
-    left, steps = n - 1, 1
-    check = _EARLY_EXIT and eos_token is not None
-    while left > 0:
-        k = min(left, _EXIT_EVERY) if check else left
-        loop.run(k)
-        left -= k
-        steps += k
-        if check and left > 0 and bool(st["fin"].all()):
-            break
+    steps = 1 + _replay(loop.run, n - 1, st["fin"], eos_token)
     hparent, htok = st["hparent"][:, :, T:T + steps].cpu(), st["htok"][:, :, T:T + steps].cpu()
     return hparent, htok, st["len"].view(B, W).long(), st["score"].view(B, W).clone()
 
@@ -1519,14 +1447,8 @@ def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ng
     the same rule runs through ``ops.reference.ngram_draft`` / ``spec_accept`` and one model forward
     over the extended sequence per step."""
     who = "generate_speculative"
-    if not (torch.is_tensor(idx) and idx.dim() == 2 and idx.dtype == torch.long and idx.size(0) >= 1
-            and idx.size(1) >= 1):
-        raise ValueError(f"{who}: idx must be an int64 [B, T] tensor with B, T >= 1")
-    V, bs = model.config.vocab_size, model.block_size
-    B, T = idx.shape
-    n = int(max_new_tokens)
-    if n < 0:
-        raise ValueError(f"{who}: max_new_tokens must be >= 0, got {max_new_tokens}")
+    n = _check_entry(who, model, max_new_tokens, idx)
+    B = idx.size(0)
     if int(draft_len) != draft_len or not 1 <= int(draft_len) <= _SPEC_ROWS_MAX - 1:
         raise ValueError(f"{who}: draft_len must be in 1..{_SPEC_ROWS_MAX - 1}, got {draft_len}")
     K = int(draft_len) + 1
@@ -1535,10 +1457,7 @@ def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ng
                          f"at most {_SPEC_ROWS_MAX}")
     if int(ngram) != ngram or not 1 <= int(ngram) <= _SPEC_NGRAM_MAX:
         raise ValueError(f"{who}: ngram must be in 1..{_SPEC_NGRAM_MAX}, got {ngram}")
-    if T + n > bs:
-        raise ValueError(f"{who}: prompt ({T}) + max_new_tokens ({n}) exceeds block_size ({bs}); this entry "
-                         f"point has no sliding window")
-    _check_token_ids(who, V, idx)
+    _check_token_ids(who, model.config.vocab_size, idx)
     before_use(*model.parameters())
     if n == 0:
         out = idx.clone()
@@ -1585,23 +1504,13 @@ def _generate_speculative_cpu(model, idx, n, K, ngram):
     return out, steps, hist
 
 
-def _spec_cache(model, idx, tmax):
-    """The model's speculative decode state of B sequences, kept beside (not in place of) the plain
-    and beam states: speculative calls leave their loops and graphs alone."""
-    c = model.__dict__.get("_mg_spec_cache")
-    if c is None or c.B != idx.size(0) or c.tmax != tmax or c.caches[0].device != idx.device:
-        c = _GpuCache(model, idx, tmax, rows=idx.size(0))
-        model.__dict__["_mg_spec_cache"] = c
-    return c
-
-
 def _generate_speculative_gpu(model, idx, n, K, ngram):
     """The GPU half of ``generate_speculative``: build (once per (B, K)) the speculative loop, prefill
     the prompts and take the first token from the prefill logits as ``generate`` does, then replay
     the captured step in rounds of ceil((end - min p) / K) -- the fewest steps that could finish --
     reading the positions back after each round, until every sequence has reached ``end``."""
     B, T = idx.shape
-    cache = _spec_cache(model, idx, model.block_size)
+    cache = _state_for(model, "_mg_spec_cache", idx, model.block_size, rows=B)
     loop = cache.spec(K)  # before the prefill: building it runs a warm-up step
     cache.prefill(idx)
     st = cache.spec_start(K, idx, cache.logits.argmax(-1), n, ngram)
@@ -1668,9 +1577,8 @@ def score(model, idx, lengths=None):
         lp = R.token_logprob(logits[:, :-1], tokens[:, 1:])
         out[:, 1:] = torch.where(valid, lp, torch.zeros_like(lp))
         return out
-    c = _GpuCache.body_only(model)
-    D = model.config.n_embed
-    x = c._prompt(tokens, keep=False).view(B * T, D)
+    c = _Body(model)
+    x = c._prompt(tokens).view(B * T, model.config.n_embed)
     targets = torch.full((B, T), -1, dtype=torch.long, device=device)  # row (b, t) predicts column t + 1
     targets[:, :-1] = torch.where(valid, tokens[:, 1:], targets[:, 1:])
     targets = targets.view(B * T)
