@@ -1,4 +1,5 @@
-"""MFMA GEMM (csrc/kernels/gemm.hip) vs fp32 PyTorch, all layouts and epilogues, tail shapes."""
+"""MFMA GEMM (csrc/kernels/gemm.hip) vs fp32 PyTorch, all layouts and epilogues, tail shapes.
+Exact-integer, one-hot, fp64-bound and independence tests of the same kernels: tests/test_gemm_exact_gpu.py."""
 import pytest
 import torch
 
