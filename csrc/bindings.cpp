@@ -1132,6 +1132,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_bwd_dropout", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),
         py::arg("rstd"), py::arg("dw"), py::arg("db"), py::arg("dres"), py::arg("dz_bias"),
         py::arg("drop_p"), py::arg("drop_seed"));
+  // read-only: the number of blocks layernorm_bwd launches (tests pick M past the capped grid with it)
+  m.def("layernorm_bwd_grid", &mg::ln_bwd_grid, py::arg("M"), py::arg("D"), py::arg("drop"));
   m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe"), py::arg("p"),
         py::arg("seed"), py::arg("pos_dev") = py::none(), py::arg("am_part") = py::none(),
         py::arg("seq") = py::none(), py::arg("pos_stride") = 0);

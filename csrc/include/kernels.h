@@ -19,6 +19,9 @@ void layernorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const flo
                    float* workspace, int M, int D, hipStream_t stream, bf16_t* dz = nullptr,
                    float* dzb = nullptr, float p = 0.f, uint64_t seed = 0);
 size_t layernorm_bwd_workspace(int M, int D, bool drop);
+// blocks layernorm_bwd launches for M rows: M / 32, at least 1, at most one resident wave of blocks
+// of the instantiation (D, drop) selects; each block's waves stride over the rows
+int ln_bwd_grid(int M, int D, bool drop);
 
 // embedding.hip
 void embedding_fwd(const int64_t* idx, const bf16_t* wte, const bf16_t* wpe, bf16_t* out, int M,
