@@ -9,7 +9,7 @@
 //   layout NN: A' = A[M,K] (k contiguous), B' = B[K,N]  (n contiguous)    -> dgrad   dx = dy W
 //   layout TN: A' = A[K,M]^T (m contiguous), B' = B[K,N] (n contiguous)  -> wgrad   dW += dy^T x
 //
-// Design (see /opt/skills/guides/cdna_hip_programming.md §5):
+// Design:
 //  * v_mfma_f32_16x16x32_bf16, BK = 64, tile configs chosen per shape (pick_config):
 //      W4:   256x256 (or 256x192) tile, 4 waves (2x2) of 128x128 (128x96), 160 KiB LDS, one wave
 //            per SIMD holding the whole register file (the default for every large shape)
@@ -53,15 +53,15 @@ constexpr int BK = 64;
 constexpr int GROUP_M = MG_GROUP_M;  // row tiles per L2 group (blocks of a group share B column tiles)
 constexpr uint32_t kOOB = 0xFFFFFFF0u;
 
-template <int BM_, int BN_, int NWM_, int NWN_, int STAGES_ = 2>
+template <int BM_, int BN_, int NWM_, int NWN_>
 struct Cfg {
-  static constexpr int BM = BM_, BN = BN_, NWM = NWM_, NWN = NWN_, STAGES = STAGES_;
+  static constexpr int BM = BM_, BN = BN_, NWM = NWM_, NWN = NWN_;
   static constexpr int NW = NWM * NWN, NT = NW * 64;
   static constexpr int WTM = BM / NWM, WTN = BN / NWN;  // wave tile
   static constexpr int FM = WTM / 16, FN = WTN / 16;    // 16x16 MFMA tiles per wave
   static constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2;
   static constexpr int STAGE = A_BYTES + B_BYTES;
-  static constexpr int SMEM = STAGES * STAGE;
+  static constexpr int SMEM = 2 * STAGE;  // two-stage ring
 };
 using T128 = Cfg<128, 128, 2, 2>;
 
@@ -85,12 +85,11 @@ struct GemmArgs {
   int splits, kchunk;         // split-K (fp32-accumulate layout only): K range per split
   uint64_t a_bytes, b_bytes;  // operand sizes; each block's descriptor spans <= 4 GiB from its origin
   unsigned long long* dbg;    // MG_GEMM_STAMPS diagnostic builds only: per-wave phase timestamps
-  float* dbias;               // EPI 4: += column sums of the output (the bias gradient), or null
-  int nt_out;                 // non-temporal bf16 output stores (see gemm() below)
+  float* dbias;               // EPI 4 / 7: += column sums of the output (the bias gradient), or null
 };
 
 static unsigned long long* g_dbg = nullptr;  // MG_GEMM_STAMPS builds: stamp buffer
-static int g_variant = 0;  // 0 auto, 1 force T128, 5 force W4, 6 force W4 BN=192 (2-4: deleted configs)
+static int g_variant = 0;  // 0 auto, 1 force T128, 5 force W4, 6 force W4 BN=192
 
 // Chunk swizzle of the m/n-contiguous [64 k][256 B] half-images: rows 8 g + q (q < 4) of one
 // transposed read get 8 distinct chunk pairs (conflict-free ds_read_b64_tr_b16), and bit 2 of the
@@ -246,8 +245,8 @@ MG_DEVICE bf16x8 frag_k(const char* lds, int sb, int lane) {
 // private and a wave's LDS ops complete in order), reads them back as 8 consecutive columns per
 // lane and stores / loads side inputs with 16-byte accesses along whole wave-tile rows.
 // Work that needs the fragment layout (bias, GELU, the row-block dropout mask) runs before the
-// staging; the residual add / GELU' multiply read their side input after it, on fp32 staged values,
-// so the rounding is identical to the direct form.
+// staging; EPI 4's row-major GELU' multiply reads its side input after it, on fp32 staged values,
+// so every output is rounded to bf16 once.
 constexpr int stage_chf(int fm, int frag_row_bytes, int budget) {
   int c = fm;
   while (c > 1 && c * frag_row_bytes > budget) c >>= 1;
@@ -274,6 +273,27 @@ MG_DEVICE void store8(bf16_t* p, uint4 v, int valid) {
     if (e < valid) p[e] = (uint16_t)(w[e >> 1] >> (16 * (e & 1)));
 }
 
+// The one store of full-tile bf16 outputs (C and both GELU' planes; edge tiles keep store8's bounds
+// checks).  Non-temporal: the outputs are consumed by a later kernel, and keeping them out of
+// L2 / MALL leaves those to the GEMM operands (one-box A/B at B = 64: LM head forward 5.07 -> 4.51 ms;
+// step +1.3 % with every output > 256 MB, +0.5 % more with all of them)
+// (by value and not through common.h's st16_nt, which takes a reference: that form costs the EPI 6
+// W4 kernel, at its 512-register limit, one VGPR spill)
+MG_DEVICE void store_out16(bf16_t* p, uint4 v) {
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u*>(p));
+}
+
+// v[0..3] += / *= the four bf16 of x (fp32 math on the widened values)
+MG_DEVICE void add_bf4(float* v, uint2 x) {
+  v[0] += bf2f(x.x & 0xffffu); v[1] += bf2f(x.x >> 16);
+  v[2] += bf2f(x.y & 0xffffu); v[3] += bf2f(x.y >> 16);
+}
+MG_DEVICE void mul_bf4(float* v, uint2 x) {
+  v[0] *= bf2f(x.x & 0xffffu); v[1] *= bf2f(x.x >> 16);
+  v[2] *= bf2f(x.y & 0xffffu); v[3] *= bf2f(x.y >> 16);
+}
+
 // EPI 4 bias gradient in the staged epilogue: a lane's 8-column piece index e % PR is the same in
 // every pass when PR divides 64, so each lane keeps 8 running column sums of the fp32 outputs (before
 // their bf16 rounding: one add per element; unpacking the rounded values cost the epilogue ~2.5 us
@@ -287,7 +307,7 @@ constexpr bool staged_dbias() { return 64 % (CF::WTN / 8) == 0; }
 // immediates / one add per piece), and the LDS reads go out G at a time ahead of their stores.
 // Read-then-store per piece waited out each ds_read's latency before its store: 4.1-5.0k of the
 // W4 tile's ~8k epilogue cycles at K = 768 (tools/gemm_stamps.hip with -DMG_GEMM_EPI_STAMPS).
-template <int EPI, int S, int CHF, int PR, int IT, bool NT>
+template <int EPI, int S, int CHF, int PR, int IT>
 MG_DEVICE void staged_copy_out(const GemmArgs& args, const char* st, int mr, int nw, int lane) {
   constexpr int RPI = 64 / PR, G = 8;
   static_assert(IT % G == 0, "pieces per lane must be a multiple of the read group");
@@ -297,7 +317,6 @@ MG_DEVICE void staged_copy_out(const GemmArgs& args, const char* st, int mr, int
   bf16_t* gc = reinterpret_cast<bf16_t*>(args.C) + off0;
   bf16_t* ga = EPI == 2 ? args.aux + off0 : nullptr;
   const long rs = (long)RPI * args.ldc;
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int g0 = 0; g0 < IT; g0 += G) {
     uint4 y[G], z[EPI == 2 ? G : 1];
@@ -309,30 +328,24 @@ MG_DEVICE void staged_copy_out(const GemmArgs& args, const char* st, int mr, int
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       const long o = (long)(g0 + u) * rs;
-      if constexpr (NT) {
-        __builtin_nontemporal_store(v4u{y[u].x, y[u].y, y[u].z, y[u].w}, reinterpret_cast<v4u*>(gc + o));
-        if constexpr (EPI == 2)
-          __builtin_nontemporal_store(v4u{z[u].x, z[u].y, z[u].z, z[u].w}, reinterpret_cast<v4u*>(ga + o));
-      } else {
-        *reinterpret_cast<uint4*>(gc + o) = y[u];
-        if constexpr (EPI == 2) *reinterpret_cast<uint4*>(ga + o) = z[u];
-      }
+      store_out16(gc + o, y[u]);
+      if constexpr (EPI == 2) store_out16(ga + o, z[u]);
     }
   }
 }
 
-// Whole-tile fp32-staged output with a bf16 side input (EPI 3: + residual, EPI 4: x GELU'), same
-// addressing as staged_copy_out; the fp32 pieces are read G at a time ahead of their math and
-// stores.  The side input `sd` was loaded for the whole pass before the staging.
-template <class CF, int EPI, int S, int PR, int IT, bool NT>
+// Whole-tile fp32-staged output of EPI 4 (x the row-major GELU' side input, + the bias gradient's
+// column sums), same addressing as staged_copy_out; the fp32 pieces are read G at a time ahead of
+// their math and stores.  The side input `sd` was loaded for the whole pass before the staging.
+template <int S, int PR, int IT>
 MG_DEVICE void staged_side_out(const GemmArgs& args, const char* st, const uint4 (&sd)[IT], int mr, int nw,
                                int lane, float (&cs)[8]) {
-  constexpr int RPI = 64 / PR, G = 2;  // 4 spilled at EPI 4 (the pass's side input holds 64 VGPRs)
+  static_assert(64 % PR == 0, "a lane keeps one piece column (the condition of staged_dbias)");
+  constexpr int RPI = 64 / PR, G = 2;  // 4 spilled (the pass's side input holds 64 VGPRs)
   const int r0 = lane / PR, p = lane % PR;
   const char* lrow = st + r0 * S + p * 32;
   bf16_t* gc = reinterpret_cast<bf16_t*>(args.C) + (long)(mr + r0) * args.ldc + nw + p * 8;
   const long rs = (long)RPI * args.ldc;
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int g0 = 0; g0 < IT; g0 += G) {
     float4 a[G], b[G];
@@ -344,23 +357,15 @@ MG_DEVICE void staged_side_out(const GemmArgs& args, const char* st, const uint4
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       float v[8] = {a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y, b[u].z, b[u].w};
-      if constexpr (EPI != 7) {  // EPI 7: GELU' was applied in the fragment layout, before the staging
-        const uint4 sv = sd[g0 + u];
-        const uint32_t w[4] = {sv.x, sv.y, sv.z, sv.w};
+      const uint4 sv = sd[g0 + u];
+      mul_bf4(v, make_uint2(sv.x, sv.y));
+      mul_bf4(v + 4, make_uint2(sv.z, sv.w));
+      // column sums (fp32, before the bf16 rounding).  -ffp-contract=fast leaves to the compiler
+      // which of these adds fuse with their multiply, so the sums' last bits follow the build
+      // (PERF.md, "Training GEMM epilogue refactor")
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float s = bf2f((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-          v[k] = EPI == 3 ? v[k] + s : v[k] * s;
-        }
-      }
-      if constexpr ((EPI == 4 || EPI == 7) && staged_dbias<CF>()) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) cs[k] += v[k];
-      }
-      const uint4 y = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-      bf16_t* dst = gc + (long)(g0 + u) * rs;
-      if constexpr (NT) __builtin_nontemporal_store(v4u{y.x, y.y, y.z, y.w}, reinterpret_cast<v4u*>(dst));
-      else *reinterpret_cast<uint4*>(dst) = y;
+      for (int k = 0; k < 8; ++k) cs[k] += v[k];
+      store_out16(gc + (long)(g0 + u) * rs, pack8(v));
     }
   }
 }
@@ -368,14 +373,13 @@ MG_DEVICE void staged_side_out(const GemmArgs& args, const char* st, const uint4
 template <class CF, int EPI, bool F32, int S, int CHF, int PR, int IT, bool CHECK>
 MG_DEVICE void staged_rows(const GemmArgs& args, const char* st, const uint4 (&sd)[F32 ? IT : 1], int mr,
                            int nw, int nlim, int lane, float (&cs)[8]) {
+  static_assert(F32 == (EPI == 4), "the fp32 staging is EPI 4's");
   if constexpr (!F32 && !CHECK && 64 % PR == 0 && IT % 8 == 0) {
-    if (args.nt_out) staged_copy_out<EPI, S, CHF, PR, IT, true>(args, st, mr, nw, lane);
-    else staged_copy_out<EPI, S, CHF, PR, IT, false>(args, st, mr, nw, lane);
+    staged_copy_out<EPI, S, CHF, PR, IT>(args, st, mr, nw, lane);
     return;
   }
-  if constexpr (EPI == 4 && !CHECK && 64 % PR == 0 && IT % 2 == 0) {
-    if (args.nt_out) staged_side_out<CF, EPI, S, PR, IT, true>(args, st, sd, mr, nw, lane, cs);
-    else staged_side_out<CF, EPI, S, PR, IT, false>(args, st, sd, mr, nw, lane, cs);
+  if constexpr (F32 && !CHECK && 64 % PR == 0 && IT % 2 == 0) {
+    staged_side_out<S, PR, IT>(args, st, sd, mr, nw, lane, cs);
     return;
   }
 #pragma unroll
@@ -388,14 +392,10 @@ MG_DEVICE void staged_rows(const GemmArgs& args, const char* st, const uint4 (&s
       const float4 a = *reinterpret_cast<const float4*>(row + p * 32);
       const float4 b = *reinterpret_cast<const float4*>(row + p * 32 + 16);
       float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      const uint32_t w[4] = {sd[it].x, sd[it].y, sd[it].z, sd[it].w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float s = bf2f((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-        if constexpr (EPI != 7) v[k] = EPI == 3 ? v[k] + s : v[k] * s;
-      }
-      y = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-      if constexpr ((EPI == 4 || EPI == 7) && staged_dbias<CF>()) {  // column sums (fp32, before the bf16 rounding)
+      mul_bf4(v, make_uint2(sd[it].x, sd[it].y));  // x GELU'
+      mul_bf4(v + 4, make_uint2(sd[it].z, sd[it].w));
+      y = pack8(v);
+      if constexpr (staged_dbias<CF>()) {  // column sums (fp32, before the bf16 rounding)
         if constexpr (CHECK) {
           const bool ok = m < args.M;
 #pragma unroll
@@ -410,24 +410,30 @@ MG_DEVICE void staged_rows(const GemmArgs& args, const char* st, const uint4 (&s
     }
     const long off = (long)m * args.ldc + n;
     if constexpr (!CHECK) {
-      if (args.nt_out) {  // streamed output far larger than the caches: non-temporal
-        typedef unsigned v4u __attribute__((ext_vector_type(4)));
-        __builtin_nontemporal_store(v4u{y.x, y.y, y.z, y.w},
-                                    reinterpret_cast<v4u*>(reinterpret_cast<bf16_t*>(args.C) + off));
-        if constexpr (EPI == 2) {
-          const uint4 g = *reinterpret_cast<const uint4*>(row + CHF * 16 * S + p * 16);
-          __builtin_nontemporal_store(v4u{g.x, g.y, g.z, g.w}, reinterpret_cast<v4u*>(args.aux + off));
-        }
-      } else {
-        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(args.C) + off) = y;
-        if constexpr (EPI == 2)
-          *reinterpret_cast<uint4*>(args.aux + off) = *reinterpret_cast<const uint4*>(row + CHF * 16 * S + p * 16);
-      }
+      store_out16(reinterpret_cast<bf16_t*>(args.C) + off, y);
+      if constexpr (EPI == 2)
+        store_out16(args.aux + off, *reinterpret_cast<const uint4*>(row + CHF * 16 * S + p * 16));
     } else if (m < args.M && n < nlim) {
       store8(reinterpret_cast<bf16_t*>(args.C) + off, y, nlim - n);
       if constexpr (EPI == 2)
         store8(args.aux + off, *reinterpret_cast<const uint4*>(row + CHF * 16 * S + p * 16), nlim - n);
     }
+  }
+}
+
+// Last step of every bias-gradient form.  Each wave has written its wave tile's WTN column sums to
+// red[wm][wn * WTN ..] (red = smem as float [NWM][BN]); the NWM row-waves meet here, then one atomic
+// per tile column, 64 contiguous floats per wave-instruction (atomics with a few active lanes each
+// run at a small fraction of that)
+template <class CF>
+MG_DEVICE void dbias_fold(const GemmArgs& args, const char* smem, int n0) {
+  const float* red = reinterpret_cast<const float*>(smem);
+  __syncthreads();
+  for (int c = threadIdx.x; c < CF::BN; c += CF::NT) {
+    float t = 0.f;
+#pragma unroll
+    for (int r = 0; r < CF::NWM; ++r) t += red[r * CF::BN + c];
+    if (n0 + c < args.N) atomicAdd(args.dbias + n0 + c, t);
   }
 }
 
@@ -535,10 +541,7 @@ MG_DEVICE void epilogue_staged(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN
       for (int j = 0; j < CF::FN; ++j) {
         const int n = nb + j * 16;
         float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        if constexpr (EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6) {
-          v[0] += bf2f(bs[j].x & 0xffffu); v[1] += bf2f(bs[j].x >> 16);
-          v[2] += bf2f(bs[j].y & 0xffffu); v[3] += bf2f(bs[j].y >> 16);
-        }
+        if constexpr (EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6) add_bf4(v, bs[j]);
         const int col = j * 16 + (lane >> 4) * 4;
         if constexpr (EPI == 6) {  // y = GELU(z) staged; GELU'(z) straight to its fragment-ordered plane
           f32x2 y0, y1, g0, g1;
@@ -547,16 +550,10 @@ MG_DEVICE void epilogue_staged(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN
           v[0] = y0.x; v[1] = y0.y; v[2] = y1.x; v[3] = y1.y;
           gq[(j & 1) * 2] = pack2(g0.x, g0.y);
           gq[(j & 1) * 2 + 1] = pack2(g1.x, g1.y);
-          if (j & 1) {
-            typedef unsigned v4u __attribute__((ext_vector_type(4)));
-            __builtin_nontemporal_store(v4u{gq[0], gq[1], gq[2], gq[3]},
-                                        reinterpret_cast<v4u*>(frag_aux + (i * CF::FN + j - 1) * 256));
-          }
+          if (j & 1) store_out16(frag_aux + (i * CF::FN + j - 1) * 256, make_uint4(gq[0], gq[1], gq[2], gq[3]));
         }
         if constexpr (EPI == 7) {  // x GELU'(z) in the fragment layout (fp32 product, as EPI 4)
-          const uint2 gx = rsd[i & 1][j];
-          v[0] *= bf2f(gx.x & 0xffffu); v[1] *= bf2f(gx.x >> 16);
-          v[2] *= bf2f(gx.y & 0xffffu); v[3] *= bf2f(gx.y >> 16);
+          mul_bf4(v, rsd[i & 1][j]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) csf[j * 4 + e] += v[e];  // fp32, before the rounding
         }
@@ -570,9 +567,7 @@ MG_DEVICE void epilogue_staged(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN
         }
         if constexpr (EPI == 3) {
           if (args.thr) rowdrop4(v, dkey, m, n, args.N, args.thr, args.scale);  // common.h
-          const uint2 rv = rsd[i & 1][j];
-          v[0] += bf2f(rv.x & 0xffffu); v[1] += bf2f(rv.x >> 16);
-          v[2] += bf2f(rv.y & 0xffffu); v[3] += bf2f(rv.y >> 16);
+          add_bf4(v, rsd[i & 1][j]);
         }
         if constexpr (F32)
           *reinterpret_cast<float4*>(row + col * 4) = make_float4(v[0], v[1], v[2], v[3]);
@@ -597,8 +592,7 @@ MG_DEVICE void epilogue_staged(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN
   if constexpr (EPI == 7) {
     if (args.dbias) {
       // the 16 lanes of a column group (lane bits 0-3 = rows) fold by transposing shuffles: lane
-      // (r, g) ends with sums 2 r, 2 r + 1 of its 4 FN values ([j][4]: fragment j, column 4 g + e);
-      // the NWM row-waves meet in LDS, then one atomic per tile column
+      // (r, g) ends with sums 2 r, 2 r + 1 of its 4 FN values ([j][4]: fragment j, column 4 g + e)
       constexpr int NV = 4 * CF::FN;
       static_assert(NV == 32, "fragment-layout fold: 8 fragments per wave-tile row");
 #pragma unroll
@@ -612,203 +606,171 @@ MG_DEVICE void epilogue_staged(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN
           csf[i2] = keep + __shfl_xor(send, M, 64);
         }
       }
-      float* red = reinterpret_cast<float*>(smem);  // [NWM][BN], over the staging regions
+      float* red = reinterpret_cast<float*>(smem) + wm * CF::BN + wn * CF::WTN;  // over the staging regions
       __syncthreads();  // every wave's staged reads are done
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int idx = 2 * (lane & 15) + t, j = idx / 4, e = idx % 4;
-        red[wm * CF::BN + wn * CF::WTN + 16 * j + 4 * (lane >> 4) + e] = csf[t];
+        red[16 * j + 4 * (lane >> 4) + e] = csf[t];
       }
-      __syncthreads();
-      for (int c = threadIdx.x; c < CF::BN; c += CF::NT) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < CF::NWM; ++r) t += red[r * CF::BN + c];
-        if (n0 + c < args.N) atomicAdd(args.dbias + n0 + c, t);
-      }
+      dbias_fold<CF>(args, smem, n0);
     }
   }
   if constexpr (EPI == 4 && staged_dbias<CF>()) {
     if (args.dbias) {  // kernel argument: uniform over the workgroup
-      // lanes sharing a piece index (lane % PR) fold by shuffles, the NWM row-waves through LDS,
-      // then one atomic per tile column with 64 contiguous floats per wave-instruction
+      // lanes sharing a piece index (lane % PR) fold by shuffles
 #pragma unroll
       for (int k = 0; k < 8; ++k)
 #pragma unroll
         for (int o = PR; o < 64; o <<= 1) cs[k] += __shfl_xor(cs[k], o, 64);
-      float* red = reinterpret_cast<float*>(smem);  // [NWM][BN], over the staging regions
+      float* red = reinterpret_cast<float*>(smem) + wm * CF::BN + wn * CF::WTN;  // over the staging regions
       __syncthreads();  // every wave's staged reads are done
       if (lane < PR) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) red[wm * CF::BN + wn * CF::WTN + lane * 8 + k] = cs[k];
+        for (int k = 0; k < 8; ++k) red[lane * 8 + k] = cs[k];
       }
-      __syncthreads();
-      for (int c = threadIdx.x; c < CF::BN; c += CF::NT) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < CF::NWM; ++r) t += red[r * CF::BN + c];
-        if (n0 + c < args.N) atomicAdd(args.dbias + n0 + c, t);
-      }
+      dbias_fold<CF>(args, smem, n0);
     }
   }
 }
 
-// Shared epilogue: lane holds acc[i][j] = C[m0+wm*WTM+16i+(lane&15)][n0+wn*WTN+16j+4(lane>>4) .. +3].
-// LDSW: LDS bytes each wave may use for the staged form (the K-loop's buffers are free by then).
-template <class CF, int EPI, bool OUTF32, int LDSW>
-MG_DEVICE void epilogue(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN], int m0, int n0, int wm,
-                        int wn, int wid, int lane, char* smem, unsigned long long* est = nullptr) {
-  if constexpr (!OUTF32) {
-    if ((EPI != 4 && EPI != 7) || !args.dbias || staged_dbias<CF>()) {
-      epilogue_staged<CF, EPI, LDSW>(args, acc, m0, n0, wm, wn, wid, lane, smem, est);
-      return;
-    }
-  }
-  if constexpr (OUTF32) {
-    if (args.splits > 1) {
-      // split-K: fp32 atomics into C.  Each wave stages its tile through LDS 32 rows at a time
-      // (row stride WTN+4 floats: conflict-free ds_write_b128), then every atomic
-      // wave-instruction adds WTN contiguous floats of one row (256 B: the full-rate shape).
-      constexpr int RS = CF::WTN + 4;
-      float* ct = reinterpret_cast<float*>(smem) + wid * 32 * RS;
-      float* C = reinterpret_cast<float*>(args.C);
+// ---- The two epilogues that do not go through the LDS staging.  In both, a lane holds
+// acc[i][j] = C[m0+wm*WTM+16i+(lane&15)][n0+wn*WTN+16j+4(lane>>4) .. +3] and loads its side input
+// (fp32 C / GELU') for all FN column groups of row m before any use, so a tile pays ~FM load
+// latencies instead of FM x FN serialised round trips.
+
+// fp32 accumulate (TN: the main-grad buffer): C += acc, by atomics under split-K, else read-modify-write
+template <class CF>
+MG_DEVICE void epilogue_f32acc(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN], int m0, int n0, int wm,
+                               int wn, int wid, int lane, char* smem) {
+  float* C = reinterpret_cast<float*>(args.C);
+  if (args.splits > 1) {
+    // split-K: fp32 atomics into C.  Each wave stages its tile through LDS 32 rows at a time
+    // (row stride WTN+4 floats: conflict-free ds_write_b128), then every atomic
+    // wave-instruction adds WTN contiguous floats of one row (256 B: the full-rate shape).
+    constexpr int RS = CF::WTN + 4;
+    float* ct = reinterpret_cast<float*>(smem) + wid * 32 * RS;
 #pragma unroll
-      for (int pass = 0; pass < CF::FM / 2; ++pass) {
+    for (int pass = 0; pass < CF::FM / 2; ++pass) {
 #pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
+      for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
-          for (int j = 0; j < CF::FN; ++j)
-            *reinterpret_cast<f32x4*>(ct + (ii * 16 + (lane & 15)) * RS + j * 16 + (lane >> 4) * 4) =
-                acc[pass * 2 + ii][j];
-        __syncthreads();
-        for (int c = lane; c < CF::WTN; c += 64) {
-          const int n = n0 + wn * CF::WTN + c;
-          for (int r = 0; r < 32; ++r) {
-            const int m = m0 + wm * CF::WTM + pass * 32 + r;
-            if (m < args.M && n < args.N) atomicAdd(C + (long)m * args.ldc + n, ct[r * RS + c]);
-          }
+        for (int j = 0; j < CF::FN; ++j)
+          *reinterpret_cast<f32x4*>(ct + (ii * 16 + (lane & 15)) * RS + j * 16 + (lane >> 4) * 4) =
+              acc[pass * 2 + ii][j];
+      __syncthreads();
+      for (int c = lane; c < CF::WTN; c += 64) {
+        const int n = n0 + wn * CF::WTN + c;
+        for (int r = 0; r < 32; ++r) {
+          const int m = m0 + wm * CF::WTM + pass * 32 + r;
+          if (m < args.M && n < args.N) atomicAdd(C + (long)m * args.ldc + n, ct[r * RS + c]);
         }
-        __syncthreads();
       }
-      return;
+      __syncthreads();
+    }
+    return;
+  }
+  const int nb = n0 + wn * CF::WTN + (lane >> 4) * 4;
+#pragma unroll
+  for (int i = 0; i < CF::FM; ++i) {
+    const int m = m0 + wm * CF::WTM + i * 16 + (lane & 15);
+    if (m >= args.M) continue;
+    float* crow = C + (long)m * args.ldc;
+    float4 cold[CF::FN];
+#pragma unroll
+    for (int j = 0; j < CF::FN; ++j) {
+      const int n = nb + j * 16;
+      if (n < args.N) cold[j] = *reinterpret_cast<const float4*>(crow + n);
+    }
+#pragma unroll
+    for (int j = 0; j < CF::FN; ++j) {
+      const int n = nb + j * 16;
+      if (n >= args.N) continue;
+      float4 c = cold[j];
+      c.x += acc[i][j][0]; c.y += acc[i][j][1]; c.z += acc[i][j][2]; c.w += acc[i][j][3];
+      *reinterpret_cast<float4*>(crow + n) = c;
     }
   }
-  // ---- epilogue: lane holds C[m][n..n+3].  Side inputs are loaded a whole row group at a time
-  // (bias once per lane; resid / aux / fp32 C for all FN column groups of row m before any use), so a
-  // tile pays ~FM load latencies instead of FM x FN serialised round trips.
-  const int nlim = (EPI == 0 && !OUTF32) ? (int)args.ldc : args.N;
+}
+
+// bf16 output of EPI 4 with the bias gradient on a wave tile where staged_dbias is false (the 128x96
+// one of W4-192): 8-byte stores straight from the fragment layout, and the column sums are those of
+// the stored, bf16-rounded values -- the staged form sums the fp32 values before their rounding, so
+// the two are not interchangeable bit for bit.
+template <class CF, int EPI>
+MG_DEVICE void epilogue_direct_dbias(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN], int m0, int n0,
+                                     int wm, int wn, int lane, char* smem) {
+  static_assert(EPI == 4 && !staged_dbias<CF>(), "fallback of EPI 4 only; every other output is staged");
   const int nb = n0 + wn * CF::WTN + (lane >> 4) * 4;
-  const bf16_t* __restrict__ bias = args.bias;
-  const uint32_t dkey = EPI == 3 ? rowdrop_key(eff_seed(args.seed, args.sofs)) : 0u;  // dropout key
-  uint2 bs[CF::FN];
-  float csum[EPI == 4 ? CF::FN : 1][4];  // EPI 4 bias gradient: this lane's column partial sums
+  float csum[CF::FN][4];  // this lane's column partial sums
 #pragma unroll
-  for (int j = 0; j < (EPI == 4 ? CF::FN : 1); ++j)
+  for (int j = 0; j < CF::FN; ++j)
 #pragma unroll
     for (int c = 0; c < 4; ++c) csum[j][c] = 0.f;
-#pragma unroll
-  for (int j = 0; j < CF::FN; ++j) {
-    bs[j] = make_uint2(0u, 0u);
-    if constexpr (EPI == 1 || EPI == 2 || EPI == 3)
-      if (bias && nb + j * 16 < nlim) bs[j] = *reinterpret_cast<const uint2*>(bias + nb + j * 16);
-  }
 #pragma unroll
   for (int i = 0; i < CF::FM; ++i) {
     const int m = m0 + wm * CF::WTM + i * 16 + (lane & 15);
     if (m >= args.M) continue;
     const long rowoff = (long)m * args.ldc;
-    uint2 side[CF::FN];
-    float4 cold[OUTF32 ? CF::FN : 1];
+    uint2 side[CF::FN];  // aux = GELU'(z) stored by the forward's EPI 2
 #pragma unroll
     for (int j = 0; j < CF::FN; ++j) {
       const int n = nb + j * 16;
-      if (n >= nlim) continue;
-      if constexpr (OUTF32) {
-        cold[j] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(args.C) + rowoff + n);
-      } else if constexpr (EPI == 3) {
-        side[j] = *reinterpret_cast<const uint2*>(args.resid + rowoff + n);
-      } else if constexpr (EPI == 4) {
-        side[j] = *reinterpret_cast<const uint2*>(args.aux + rowoff + n);
-      }
+      if (n < args.N) side[j] = *reinterpret_cast<const uint2*>(args.aux + rowoff + n);
     }
 #pragma unroll
     for (int j = 0; j < CF::FN; ++j) {
       const int n = nb + j * 16;
-      if (n >= nlim) continue;
+      if (n >= args.N) continue;
       float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      const long off = rowoff + n;
-      if constexpr (OUTF32) {
-        float4 c = cold[j];
-        c.x += v[0]; c.y += v[1]; c.z += v[2]; c.w += v[3];
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(args.C) + off) = c;
-      } else {
-        if constexpr (EPI == 1 || EPI == 2 || EPI == 3) {
-          v[0] += bf2f(bs[j].x & 0xffffu); v[1] += bf2f(bs[j].x >> 16);
-          v[2] += bf2f(bs[j].y & 0xffffu); v[3] += bf2f(bs[j].y >> 16);
-        }
-        if constexpr (EPI == 2) {  // y = GELU(z); aux <- GELU'(z) for the backward (one multiply there)
-          float gd[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float sg = gelu_sigmoid(v[r]);
-            gd[r] = gelu_grad_from(v[r], sg);
-            v[r] *= sg;
-          }
-          *reinterpret_cast<uint2*>(args.aux + off) = make_uint2(pack2(gd[0], gd[1]), pack2(gd[2], gd[3]));
-        }
-        if constexpr (EPI == 3) {
-          if (args.thr) rowdrop4(v, dkey, m, n, args.N, args.thr, args.scale);  // common.h
-          v[0] += bf2f(side[j].x & 0xffffu); v[1] += bf2f(side[j].x >> 16);
-          v[2] += bf2f(side[j].y & 0xffffu); v[3] += bf2f(side[j].y >> 16);
-        }
-        if constexpr (EPI == 4) {  // aux = GELU'(z) stored by the forward's EPI 2
-          v[0] *= bf2f(side[j].x & 0xffffu); v[1] *= bf2f(side[j].x >> 16);
-          v[2] *= bf2f(side[j].y & 0xffffu); v[3] *= bf2f(side[j].y >> 16);
-        }
-        const uint2 packed = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-        if constexpr (EPI == 4) {  // bias gradient of the stored (bf16-rounded) values
-          csum[j][0] += bf2f(packed.x & 0xffffu); csum[j][1] += bf2f(packed.x >> 16);
-          csum[j][2] += bf2f(packed.y & 0xffffu); csum[j][3] += bf2f(packed.y >> 16);
-        }
-        *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(args.C) + off) = packed;
-      }
+      mul_bf4(v, side[j]);
+      const uint2 packed = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+      add_bf4(csum[j], packed);
+      *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(args.C) + rowoff + n) = packed;
     }
   }
-  if constexpr (EPI == 4) {
-    if (args.dbias) {
-      // sum the 16 rows of each fragment column (lane & 15) by shuffles, the NWM row-waves through
-      // LDS, then one full-width atomic pass over the tile's columns (64 contiguous floats per
-      // wave-instruction: atomics with a few active lanes each run at a small fraction of that)
-      float* cs = reinterpret_cast<float*>(smem);  // [NWM][BN]
+  // sum the 16 rows of each fragment column (lane & 15) by shuffles
+  float* red = reinterpret_cast<float*>(smem) + wm * CF::BN + wn * CF::WTN;
 #pragma unroll
-      for (int j = 0; j < CF::FN; ++j)
+  for (int j = 0; j < CF::FN; ++j)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float t = csum[j][c];
-          t += __shfl_xor(t, 1, 64);
-          t += __shfl_xor(t, 2, 64);
-          t += __shfl_xor(t, 4, 64);
-          t += __shfl_xor(t, 8, 64);
-          if ((lane & 15) == 0) cs[wm * CF::BN + wn * CF::WTN + j * 16 + (lane >> 4) * 4 + c] = t;
-        }
-      __syncthreads();
-      for (int c = threadIdx.x; c < CF::BN; c += CF::NT) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < CF::NWM; ++r) t += cs[r * CF::BN + c];
-        if (n0 + c < args.N) atomicAdd(args.dbias + n0 + c, t);
-      }
+    for (int c = 0; c < 4; ++c) {
+      float t = csum[j][c];
+      t += __shfl_xor(t, 1, 64);
+      t += __shfl_xor(t, 2, 64);
+      t += __shfl_xor(t, 4, 64);
+      t += __shfl_xor(t, 8, 64);
+      if ((lane & 15) == 0) red[j * 16 + (lane >> 4) * 4 + c] = t;
     }
+  dbias_fold<CF>(args, smem, n0);
+}
+
+// Which epilogue a kernel runs.  LDSW: LDS bytes each wave may use for the staged form (the
+// K-loop's buffers are free by then).
+template <class CF, int EPI, bool OUTF32, int LDSW>
+MG_DEVICE void epilogue(const GemmArgs& args, f32x4 (&acc)[CF::FM][CF::FN], int m0, int n0, int wm,
+                        int wn, int wid, int lane, char* smem, unsigned long long* est = nullptr) {
+  if constexpr (OUTF32) {
+    static_assert(EPI == 0, "the fp32-accumulate output has no fused epilogue");
+    epilogue_f32acc<CF>(args, acc, m0, n0, wm, wn, wid, lane, smem);
+  } else if constexpr (EPI == 4 && !staged_dbias<CF>()) {
+    // the one runtime choice (a kernel argument: uniform over the grid): W4-192 asked for dbias
+    if (args.dbias) epilogue_direct_dbias<CF, EPI>(args, acc, m0, n0, wm, wn, lane, smem);
+    else epilogue_staged<CF, EPI, LDSW>(args, acc, m0, n0, wm, wn, wid, lane, smem, est);
+  } else {
+    static_assert(EPI != 7 || staged_dbias<CF>(), "EPI 7 folds its column sums in the staged form");
+    epilogue_staged<CF, EPI, LDSW>(args, acc, m0, n0, wm, wn, wid, lane, smem, est);
   }
 }
 
-template <class CF, bool AK, bool BKC, int EPI, bool OUTF32>
-__global__ __launch_bounds__(CF::NT, 2) void gemm_kernel(const GemmArgs args) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wm = wid / CF::NWN, wn = wid % CF::NWN;
-
-  // XCD-aware bijective remap, then split index, then GROUP_M swizzle over output tiles
+// blockIdx.x -> output tile origin and split-K index: XCD-aware bijective remap (consecutive
+// block ids go to different XCDs; each XCD gets a contiguous range of work items), then the split
+// index, then the GROUP_M swizzle over output tiles
+struct TileAt {
+  int m0, n0, split;
+};
+template <int BM, int BN>
+MG_DEVICE TileAt tile_at(const GemmArgs& args) {
   const int nblk = args.tiles_m * args.tiles_n * args.splits;
   const int orig = blockIdx.x;
   const int xcd = orig & 7, q8 = nblk >> 3, r8 = nblk & 7;
@@ -821,7 +783,17 @@ __global__ __launch_bounds__(CF::NT, 2) void gemm_kernel(const GemmArgs args) {
   const int gm = min(args.tiles_m - first_m, GROUP_M);
   const int pid_m = first_m + (wg % group) % gm;
   const int pid_n = (wg % group) / gm;
-  const int m0 = pid_m * CF::BM, n0 = pid_n * CF::BN;
+  return {pid_m * BM, pid_n * BN, split};
+}
+
+template <class CF, bool AK, bool BKC, int EPI, bool OUTF32>
+__global__ __launch_bounds__(CF::NT, 2) void gemm_kernel(const GemmArgs args) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wm = wid / CF::NWN, wn = wid % CF::NWN;
+
+  const TileAt at = tile_at<CF::BM, CF::BN>(args);
+  const int m0 = at.m0, n0 = at.n0, split = at.split;
 
   f32x4 acc[CF::FM][CF::FN];
 #pragma unroll
@@ -835,7 +807,7 @@ __global__ __launch_bounds__(CF::NT, 2) void gemm_kernel(const GemmArgs args) {
   Stager<BKC, CF::BN, CF::NW> stb;
   sta.init(args.A, args.a_bytes, args.lda, m0, args.a_ext, kbeg, args.ka, kbeg + args.kchunk, wid, lane);
   stb.init(args.B, args.b_bytes, args.ldb, n0, args.b_ext, kbeg, args.kb, kbeg + args.kchunk, wid, lane);
-  static_assert(CF::STAGES == 2 && CF::SMEM <= 65536, "two-stage ring with 16-bit stage offsets");
+  static_assert(CF::SMEM <= 65536, "two-stage ring with 16-bit stage offsets");
   // prologue: tile 0 in flight
   if (nk > 0) {
     sta.stage(smem, 0);
@@ -994,18 +966,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs args) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
-  const int nblk = args.tiles_m * args.tiles_n * args.splits;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nblk >> 3, r8 = nblk & 7;
-  const int wgs = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int ntiles = args.tiles_m * args.tiles_n;
-  const int split = wgs / ntiles;
-  const int wg = wgs % ntiles;
-  const int group = GROUP_M * args.tiles_n;
-  const int first_m = (wg / group) * GROUP_M;
-  const int gm = min(args.tiles_m - first_m, GROUP_M);
-  const int m0 = (first_m + (wg % group) % gm) * 256;
-  const int n0 = ((wg % group) / gm) * BN;
+  const TileAt at = tile_at<256, BN>(args);
+  const int m0 = at.m0, n0 = at.n0, split = at.split;
 
 #ifdef MG_GEMM_STAMPS
   // diagnostic builds: [0..5] segments of K-tile MG_GEMM_STAMPS (phase A issue | wait | barrier |
@@ -1163,42 +1125,41 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs args) {
 #undef W4_KSTAMP
 }
 
+// Shared by both launchers: the tile grid of bm x bn tiles, split-K for the fp32-accumulate layout
+// (slots concurrent blocks, ovh as set_split) and, once per kernel instantiation (attr_set is the
+// caller's static), the dynamic-LDS limit.  Returns the grid size.
+static int plan_launch(GemmArgs& a, int bm, int bn, bool outf32, int slots, int ovh, const void* kernel,
+                       int smem, bool& attr_set) {
+  a.tiles_m = cdiv(a.M, bm);
+  a.tiles_n = cdiv(a.N, bn);
+  a.splits = 1;
+  a.kchunk = cdiv(a.K, BK) * BK;
+  if (outf32) set_split(a, slots, ovh);
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr_set = true;
+  }
+  return a.tiles_m * a.tiles_n * a.splits;
+}
+
 template <int BN, bool AK, bool BKC, int EPI, bool OUTF32>
 void launch_w4(GemmArgs a, hipStream_t stream) {
   if constexpr (BN != 256 && !BKC) {
     launch_w4<256, AK, BKC, EPI, OUTF32>(a, stream);
   } else {
-    a.tiles_m = cdiv(a.M, 256);
-    a.tiles_n = cdiv(a.N, BN);
-    a.splits = 1;
-    a.kchunk = cdiv(a.K, BK) * BK;
-    if (OUTF32) set_split(a, 256, 6);
-    const int tiles = a.tiles_m * a.tiles_n * a.splits;
-    const int grid = tiles;
     static bool attr_set = false;
-    if (!attr_set) {
-      hipFuncSetAttribute((const void*)gemm_w4_kernel<BN, AK, BKC, EPI, OUTF32>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4<BN>::SMEM);
-      attr_set = true;
-    }
+    const int grid = plan_launch(a, 256, BN, OUTF32, 256, 6, (const void*)gemm_w4_kernel<BN, AK, BKC, EPI, OUTF32>,
+                                 W4<BN>::SMEM, attr_set);
     gemm_w4_kernel<BN, AK, BKC, EPI, OUTF32><<<grid, 256, W4<BN>::SMEM, stream>>>(a);
   }
 }
 
 template <class CF, bool AK, bool BKC, int EPI, bool OUTF32>
 void launch(GemmArgs a, hipStream_t stream) {
-  a.tiles_m = cdiv(a.M, CF::BM);
-  a.tiles_n = cdiv(a.N, CF::BN);
-  a.splits = 1;
-  a.kchunk = cdiv(a.K, BK) * BK;
-  if (OUTF32) set_split(a, 256 * (CF::SMEM <= 80 * 1024 ? 2 : 1), 2 + CF::BM * CF::BN / 16384);
-  const int grid = a.tiles_m * a.tiles_n * a.splits;
   static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_kernel<CF, AK, BKC, EPI, OUTF32>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    attr_set = true;
-  }
+  const int grid = plan_launch(a, CF::BM, CF::BN, OUTF32, 256 * (CF::SMEM <= 80 * 1024 ? 2 : 1),
+                               2 + CF::BM * CF::BN / 16384, (const void*)gemm_kernel<CF, AK, BKC, EPI, OUTF32>,
+                               CF::SMEM, attr_set);
   gemm_kernel<CF, AK, BKC, EPI, OUTF32><<<grid, CF::NT, CF::SMEM, stream>>>(a);
 }
 
@@ -1283,10 +1244,6 @@ void gemm(int layout, int epi, const bf16_t* A, const bf16_t* B, void* C, long l
   a.tiles_m = a.tiles_n = a.splits = 1;
   a.kchunk = K;
   a.dbg = g_dbg;
-  // bf16 outputs are written non-temporally: they are consumed by a later kernel, and keeping them
-  // out of L2 / MALL leaves those to the GEMM operands (one-box A/B at B = 64: LM head forward
-  // 5.07 -> 4.51 ms; step +1.3 % with every output > 256 MB, +0.5 % more with all of them)
-  a.nt_out = 1;
   if (layout == 0) {
     if (epi == 0) dispatch<true, true, 0, false>(a, stream);
     else if (epi == 1) dispatch<true, true, 1, false>(a, stream);
