@@ -681,6 +681,93 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// The int8 KV cache of one layer (kernels.h): kq int8 [B, 2, H, Tmax, hd], ks fp32 [B, 2, H, Tmax]
+void kv8_cache_args(const char* op, const at::Tensor& kq, const at::Tensor& ks, int64_t B, int64_t H, int64_t hd) {
+  CHECK_DEV(kq); CHECK_CONTIG(kq); CHECK_F32(ks); CHECK_CONTIG(ks);
+  TORCH_CHECK(kq.scalar_type() == at::kChar, op, ": kq must be int8");
+  TORCH_CHECK(kq.dim() == 5 && kq.size(0) == B && kq.size(1) == 2 && kq.size(2) == H && kq.size(4) == hd,
+              op, ": kq must be [B, 2, H, Tmax, hd]");
+  TORCH_CHECK(ks.dim() == 4 && ks.size(0) == B && ks.size(1) == 2 && ks.size(2) == H && ks.size(3) == kq.size(3),
+              op, ": ks must be [B, 2, H, Tmax]");
+  TORCH_CHECK(kq.device() == ks.device(), op, ": kq and ks on different devices");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(kq.data_ptr()) % 16 == 0, op, ": kq must be 16-byte aligned");
+}
+
+// Snap the K and V thirds of qkv [B, T, 3D] in place by the KV8 rule (common.h); with kq / ks also
+// write the int8 cache's positions 0 .. T - 1
+void kv8_store(const at::Tensor& qkv, int64_t H, const c10::optional<at::Tensor>& kq,
+               const c10::optional<at::Tensor>& ks) {
+  CHECK_BF16(qkv); CHECK_CONTIG(qkv);
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) % 3 == 0, "kv8_store: qkv must be [B, T, 3D]");
+  const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(2) / 3;
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              "kv8_store: head dim must be a multiple of 8, at most 128");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "kv8_store: qkv must be 16-byte aligned");
+  const bool cache = kq.has_value() && kq->defined();
+  TORCH_CHECK(cache == (ks.has_value() && ks->defined()), "kv8_store: kq and ks go together");
+  int64_t Tmax = T;
+  if (cache) {
+    kv8_cache_args("kv8_store", *kq, *ks, B, H, D / H);
+    Tmax = kq->size(3);
+    TORCH_CHECK(T <= Tmax && kq->device() == qkv.device(), "kv8_store: T exceeds the cache's Tmax");
+  }
+  if (B * T == 0) return;
+  DevGuard g(qkv.device());
+  mg::kv8_store(bp(qkv), cache ? kq->data_ptr<int8_t>() : nullptr, cache ? fp(*ks) : nullptr, (int)B, (int)T,
+                (int)H, (int)(D / H), Tmax, cur_stream());
+}
+
+// attention_decode on the int8 cache (no group): pos / pos_dev / part / counters / pos_stride as there
+at::Tensor attention_decode_kv8(const at::Tensor& qkv_new, const at::Tensor& kq, const at::Tensor& ks, int64_t H,
+                                int64_t pos, const c10::optional<at::Tensor>& pos_dev,
+                                const c10::optional<at::Tensor>& part, const c10::optional<at::Tensor>& counters,
+                                int64_t pos_stride) {
+  CHECK_BF16(qkv_new); CHECK_CONTIG(qkv_new);
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) % 3 == 0, "attention_decode_kv8: qkv_new must be [B, 3D]");
+  const int64_t B = qkv_new.size(0), D = qkv_new.size(1) / 3;
+  TORCH_CHECK(B >= 1 && H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              "attention_decode_kv8: head dim must be a multiple of 8, at most 128");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0,
+              "attention_decode_kv8: qkv_new must be 16-byte aligned");
+  const int64_t hd = D / H;
+  kv8_cache_args("attention_decode_kv8", kq, ks, B, H, hd);
+  TORCH_CHECK(kq.device() == qkv_new.device(), "attention_decode_kv8: the cache is on another device");
+  const int64_t Tmax = kq.size(3);
+  TORCH_CHECK(pos >= 0 && pos < Tmax, "attention_decode_kv8: pos outside the cache");
+  TORCH_CHECK(Tmax <= 4096, "attention_decode_kv8: KV cache longer than 4096 positions");
+  DevGuard g(qkv_new.device());
+  auto out = at::empty({B, D}, qkv_new.options());
+  const int* pd = nullptr;
+  if (pos_dev.has_value() && pos_dev->defined()) {
+    TORCH_CHECK(pos_dev->scalar_type() == at::kInt && pos_dev->is_cuda(), "pos_dev must be int32 cuda");
+    TORCH_CHECK((pos_stride == 0 || pos_stride == 1) && pos_dev->is_contiguous() &&
+                pos_dev->numel() >= (pos_stride ? B : 1) && pos_dev->device() == qkv_new.device(),
+                "attention_decode_kv8: pos_dev int32 [1] (pos_stride 0) or [B] (pos_stride 1)");
+    pd = pos_dev->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos_stride == 0, "attention_decode_kv8: pos_stride needs pos_dev");
+  }
+  const int64_t np = (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
+  at::Tensor pt, ct;
+  if (part.has_value() && part->defined()) {
+    TORCH_CHECK(counters.has_value() && counters->defined(), "attention_decode_kv8: part without counters");
+    CHECK_F32(*part); CHECK_DEV(*counters); CHECK_CONTIG(*part); CHECK_CONTIG(*counters);
+    TORCH_CHECK(part->numel() >= np && part->device() == qkv_new.device(),
+                "attention_decode_kv8: part workspace too small");
+    TORCH_CHECK(counters->scalar_type() == at::kInt && counters->numel() >= B * H &&
+                counters->device() == qkv_new.device(), "attention_decode_kv8: counters must be int32 [B * H]");
+    pt = *part;
+    ct = *counters;
+  } else {
+    pt = at::empty({np}, qkv_new.options().dtype(at::kFloat));
+    ct = at::zeros({B * H}, qkv_new.options().dtype(at::kInt));
+  }
+  mg::attention_decode_kv8(bp(qkv_new), kq.data_ptr<int8_t>(), fp(ks), bp(out), (int)B, (int)H, (int)hd, Tmax,
+                           (int)pos, cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd,
+                           (int)pos_stride);
+  return out;
+}
+
 // ------------------------------------------------------------------------------- logits-row ops
 // The checks the one-workgroup-per-row ops (sample.hip, beam.hip) share, one per kind of argument.
 
@@ -1206,6 +1293,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);
+  m.def("kv8_store", &kv8_store, py::arg("qkv"), py::arg("H"), py::arg("kq") = py::none(),
+        py::arg("ks") = py::none());
+  m.def("attention_decode_kv8", &attention_decode_kv8, py::arg("qkv_new"), py::arg("kq"), py::arg("ks"),
+        py::arg("H"), py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
+        py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
         py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none(),
         py::arg("lse") = py::none(), py::arg("lp") = py::none());

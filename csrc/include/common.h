@@ -436,6 +436,32 @@ MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* res
 // sum, a fold sum, s_n * sum) is subnormal or overflows -- there the two roundings differ.
 // (s_n * sum + bias may contract to one fma: the product is exact, so the result is the same.)
 
+// ---------------------------------------------------------------- KV8: int8 K / V vectors, power-of-two scales
+// The int8 KV cache (kv_cache="int8" on generate and generate_batch; attention_kv8.hip;
+// ops/quant.py snap_vectors is the rule in torch ops).  A vector u[0 .. hd-1] is the K, or separately
+// the V, of one (sequence, position, layer, head): bf16 as c_attn wrote it on the GPU, the model's dtype
+// on the CPU.  With a = max |u|:
+//   a not finite (a NaN or an inf anywhere in u): s = NaN, q = 0 -- every dequantized element of the
+//     vector is NaN, so a blown-up activation stays visible and stays in its own (sequence, head);
+//   a == 0: s = 1, q = 0;
+//   otherwise the W8 rule unchanged: s from frexp of a (2^(e-7), or 2^(e-6) when m > 127/128), never
+//     below 2^-126, and q = clamp(rne(u / s), -127, 127).
+// snap(u) = s * q is exact in bf16, and snapping it again returns (q, s).  The W8 consequences hold per
+// vector (|u - s q| <= s / 2 < a / 127 and max |q| >= 64 when a >= 2^-119).
+// The KV8 model: every attention uses snap(K) and snap(V) in place of K and V -- prefill and decode, GPU
+// and CPU; Q is untouched, and a new token's own K / V are snapped for its own query too.  One model on
+// every path: the prefill snaps the prompt's K / V thirds in place before its attention (kv8_store), a
+// decode step snaps the new row (attention_decode_kv8 in LDS, or kv8_store in place with the switch
+// off).  Storage per layer: kq int8 [B, 2, H, Tmax, hd] and ks fp32 [B, 2, H, Tmax], 2 D + 8 H bytes per
+// token against the bf16 cache's 6 D (whole qkv rows).
+// float(q) * s is exact and equals the snapped bf16 value, and attention_decode_kv8 runs the bf16 kernel's
+// fma chains on it -- no scale is folded out of a sum, so there is no precondition: it equals
+// attention_decode on the snapped row over a bf16 cache of the dequantized rows bit for bit.
+// Limits: generate and generate_batch only (generate_beam, generate_speculative and score keep bf16
+// caches; use_cache=False has no cache and is a ValueError); one scale per vector, no per-channel or
+// grouped scales; int8 only, no fp8 or 4-bit; hd % 8 == 0, hd <= 128, Tmax <= 4096; the quality of
+// the KV8 model on pretrained weights is not measured.
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Host: f(std::true_type{}) or f(std::false_type{}) for a run-time flag that is a template argument

@@ -278,4 +278,19 @@ void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, 
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
                       const int* pos_dev = nullptr, int pos_stride = 0, int group = 1);
 
+// Int8 KV cache (the KV8 rule in common.h; attention_kv8.hip).  Per layer: kq int8 [B, 2, H, Tmax, hd]
+// (K then V, 16-byte aligned) and ks fp32 [B, 2, H, Tmax], one scale per (b, K | V, h, position).
+// hd % 8 == 0, hd <= 128; hd / 8 need not be a power of two.
+// kv8_store: snap the K and V thirds of qkv [B, T, 3D] in place per (b, t, head) -- the Q third is
+// not touched -- and, with kq / ks given (both or neither), write the int8 values and scales of
+// positions 0 .. T - 1 (T <= Tmax; later positions are left alone).
+void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, long Tmax, hipStream_t stream);
+// attention_decode on the int8 cache, without group: appends the rule's (q, s) of qkv_new's K/V at
+// position pos (qkv_new itself is not modified) and writes out [B, D] -- bit for bit what
+// attention_decode writes for qkv_new with its K/V thirds snapped over a bf16 cache holding the
+// dequantized rows.  part / counters / pos_dev / pos_stride and Tmax <= 4096: attention_decode's.
+void attention_decode_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, int B, int H, int hd,
+                          long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
+                          const int* pos_dev = nullptr, int pos_stride = 0);
+
 }  // namespace mg

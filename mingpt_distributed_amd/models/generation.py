@@ -13,12 +13,13 @@ Layout of this file, top to bottom:
   ``_blocks``, ``_head``, ``_prompt``.  ``score`` needs nothing else.
 * ``_GpuCache(_Body)``: one decode state -- KV caches, workspaces, the weights' stamp, the two step
   bodies (``prefill``, ``_decode``) and every token loop as a closure around ``_decode`` that ends with
-  the loop's own tail.  A model keeps up to three (``_state_for``): ``_mg_decode_cache``,
-  ``_mg_beam_cache`` (B * W rows) and ``_mg_spec_cache`` (B sequences, B * K step rows).
+  the loop's own tail.  A model keeps up to four (``_state_for``): ``_mg_decode_cache``, ``_mg_kv8_cache``
+  (``kv_cache="int8"``: the KV8 model on int8 caches), ``_mg_beam_cache`` (B * W rows) and
+  ``_mg_spec_cache`` (B sequences, B * K step rows).
 * the word builders, ``_state_for``, then one section per entry point: checks, host loop, GPU half.
 
 Who owns what.  A loop in ``_loops`` owns its graph and, for the rectangular loops, its ``tok`` /
-``pos`` / ``seq`` (``_tok_state``); a weight change or a W8 flip (``_stamp``) drops every loop.  The
+``pos`` / ``seq`` (``_tok_state``); a weight change or a W8 / KV8 flip (``_stamp``) drops every loop.  The
 decode state owns what outlives them: the caches, the ragged / beam / spec states (allocated on first
 use) and the three parameter blocks, whose pointers the captured steps bake in.
 
@@ -40,7 +41,7 @@ import torch.nn.functional as F
 
 from ..ops import reference as R
 from ..ops.grads import before_use
-from ..ops.quant import dequantize_rows, quantize_rows
+from ..ops.quant import dequantize_rows, quantize_rows, snap_vectors
 
 
 def _sample(logits, temperature, do_sample, top_k, top_p=None):
@@ -59,12 +60,16 @@ def _sample(logits, temperature, do_sample, top_k, top_p=None):
 
 # ------------------------------------------------------------------------------------ CPU
 class _CpuCache:
-    def __init__(self, model, idx):
+    def __init__(self, model, idx, kv8=False):
+        """``kv8``: the KV8 model (common.h) -- every K and V vector is snapped (``snap_vectors``) before
+        any attention reads it, in the prompt pass and in ``step``."""
         self.model = model
         self.k, self.v = [], []
+        self.snap = (lambda t: snap_vectors(t)[2]) if kv8 else (lambda t: t)
         tr = model.transformer
 
         def attend(i, q, k, v):  # the whole prompt at once: layer i's keys / values start here
+            k, v = self.snap(k), self.snap(v)
             self.k.append(k)
             self.v.append(v)
             return R.causal_attention(q, k, v, 0.0, False)
@@ -91,8 +96,8 @@ class _CpuCache:
         tr = self.model.transformer
 
         def attend(i, q, k, v):  # one new token against the layer's cached keys / values
-            self.k[i] = torch.cat([self.k[i], k], dim=2)
-            self.v[i] = torch.cat([self.v[i], v], dim=2)
+            self.k[i] = torch.cat([self.k[i], self.snap(k)], dim=2)
+            self.v[i] = torch.cat([self.v[i], self.snap(v)], dim=2)
             att = (q @ self.k[i].transpose(-1, -2)) / q.size(-1) ** 0.5
             return F.softmax(att, dim=-1) @ self.v[i]
 
@@ -225,6 +230,11 @@ _ROWS_GEMM = os.environ.get("MINGPT_ROWS_GEMM", "1") != "0"
 # a model marked by quantize_int8_ runs its skinny-GEMM projections on the int8 twins (gemv_w8: the
 # same bits from half the weight bytes); False (MINGPT_W8_DECODE=0) keeps them on the bf16 kernel
 _W8_DECODE = os.environ.get("MINGPT_W8_DECODE", "1") != "0"
+# a kv_cache="int8" state keeps int8 caches and attends with attention_decode_kv8 (attention_kv8.hip);
+# False (MINGPT_KV8_DECODE=0) runs the same KV8 model on the bf16 kernels: bf16 caches holding snapped
+# rows, kv8_store on the step's row in place, then attention_decode -- the same bits
+_KV8_DECODE = os.environ.get("MINGPT_KV8_DECODE", "1") != "0"
+_KV_CACHES = ("bf16", "int8")
 
 
 class _Loop:
@@ -373,10 +383,13 @@ class _GpuCache(_Body):
     hipGraphs, unless a weight changed storage or version since the capture (then the graphs are
     re-captured)."""
 
-    def __init__(self, model, idx, tmax, last=None, rows=None):
+    def __init__(self, model, idx, tmax, last=None, rows=None, kv8=False):
         """``rows`` (beam search, speculative decoding): a state of that many decode rows whose
         layers' caches are one stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks
-        every layer in one launch), not prefilled here -- ``idx`` only names the device."""
+        every layer in one launch), not prefilled here -- ``idx`` only names the device.
+        ``kv8`` (``kv_cache="int8"``; not with ``rows``): a state of the KV8 model (common.h).  With
+        ``_KV8_DECODE`` on its caches are ``kq`` int8 [B, 2, H, Tmax, hd] and ``ks`` float32 [B, 2, H,
+        Tmax] per layer, off they are bf16 qkv rows holding snapped K/V (``_kv8_storage``)."""
         super().__init__(model)
         self.tmax, self.dev = tmax, idx.device
         B = idx.size(0) if rows is None else rows
@@ -384,7 +397,12 @@ class _GpuCache(_Body):
         D = cfg.n_embed
         self.B = B
         self.kv = None
-        if rows is None:
+        self.kv8 = bool(kv8)
+        self.caches, self.kq, self.ks = [], [], []
+        if self.kv8:
+            assert rows is None
+            self._kv8_storage()
+        elif rows is None:
             self.caches = [torch.empty(B, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
                            for _ in range(cfg.n_layer)]
         else:
@@ -406,9 +424,44 @@ class _GpuCache(_Body):
         if rows is None:
             self.prefill(idx, last)
 
+    def _kv8_on(self):
+        """This state's decode attention is attention_decode_kv8 on int8 caches."""
+        return self.kv8 and _KV8_DECODE
+
+    def _kv8_storage(self):
+        """A KV8 state's caches for the kernel ``_KV8_DECODE`` names now: the int8 pair, or bf16 qkv
+        rows.  Called before every prefill, so a flip of the switch swaps the buffers (the other
+        kind is freed) and the next prefill fills them; ``_stamp`` drops the loops captured on the
+        old ones."""
+        cfg = self.model.config
+        B, D, H, L = self.B, cfg.n_embed, cfg.n_head, cfg.n_layer
+        if self._kv8_on():
+            self.caches = []
+            if not self.kq:
+                self.kq = [torch.empty(B, 2, H, self.tmax, D // H, device=self.dev, dtype=torch.int8)
+                           for _ in range(L)]
+                self.ks = [torch.empty(B, 2, H, self.tmax, device=self.dev, dtype=torch.float32) for _ in range(L)]
+        else:
+            self.kq, self.ks = [], []
+            if not self.caches:
+                self.caches = [torch.empty(B, self.tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
+                               for _ in range(L)]
+
+    def cache_nbytes(self):
+        """Bytes of this state's KV cache tensors."""
+        ts = [self.kv] if self.kv is not None else self.caches + self.kq + self.ks
+        return sum(t.numel() * t.element_size() for t in ts)
+
     def _keep(self, i, qkv):
-        """Layer i's qkv rows [B, T, 3D] of a prompt into its cache."""
+        """Layer i's qkv rows [B, T, 3D] of a prompt into its cache.  A KV8 state snaps their K/V thirds
+        in place first (``kv8_store``), so the prompt's own attention reads the snapped values."""
         B, T, D3 = qkv.shape
+        if self.kv8:
+            H = self.model.config.n_head
+            if self._kv8_on():
+                self.C.kv8_store(qkv, H, self.kq[i], self.ks[i])
+                return
+            self.C.kv8_store(qkv, H)
         if self.caches[i].size(0) == B:
             self.caches[i][:, :T].copy_(qkv)
         else:  # a beam state: the prompt's rows go to each of its beams
@@ -420,6 +473,8 @@ class _GpuCache(_Body):
         those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
         cfg = self.model.config
         B = idx.size(0)
+        if self.kv8:
+            self._kv8_storage()
         x = self._prompt(idx, self._keep)
         if last is not None:  # right-padded prefill: row b's hidden state at its own last token
             x = x[torch.arange(B, device=x.device), last]
@@ -445,14 +500,24 @@ class _GpuCache(_Body):
         route = self._route(B)
         x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
                             pos_stride).view(B, D)
-        x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part,
-                                                              self.dec_cnt, pos_stride), route)
+        if self._kv8_on():
+            attend = lambda i, qkv: C.attention_decode_kv8(qkv, self.kq[i], self.ks[i], H, hpos, pos, self.dec_part,
+                                                           self.dec_cnt, pos_stride)
+        elif self.kv8:  # the KV8 model on the bf16 kernel: snap the step's K/V in place, then attend
+
+            def attend(i, qkv):
+                C.kv8_store(qkv.view(B, 1, 3 * D), H)
+                return C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part, self.dec_cnt, pos_stride)
+        else:
+            attend = lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, hpos, pos, self.dec_part,
+                                                       self.dec_cnt, pos_stride)
+        x = self._blocks(x, attend, route)
         return self._head(x, route, am=(am_part, pos) if am_part is not None else None)
 
     def _stamp(self):
-        # the weights' stamp and which skinny GEMM the steps launch: a loop captured for one kernel
-        # is never replayed for the other
-        return _weight_stamp(self.model), self._w8_on()
+        # the weights' stamp, which skinny GEMM and which decode attention the steps launch: a loop
+        # captured for one kernel is never replayed for the other
+        return _weight_stamp(self.model), self._w8_on(), self._kv8_on()
 
     def _fresh(self):
         st = self._stamp()
@@ -954,15 +1019,33 @@ def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
     return w
 
 
+_STATE_SLOTS = ("_mg_decode_cache", "_mg_kv8_cache", "_mg_beam_cache", "_mg_spec_cache")
+
+
+def _kv_slot(who, kv_cache):
+    """(slot, kv8) of a ``kv_cache`` argument: ``"bf16"`` is the plain state, ``"int8"`` the KV8 state
+    kept beside it, so alternating calls rebuild neither.  ValueError for anything else."""
+    if kv_cache not in _KV_CACHES:
+        raise ValueError(f"{who}: kv_cache must be one of {_KV_CACHES}, got {kv_cache!r}")
+    return ("_mg_kv8_cache", True) if kv_cache == "int8" else ("_mg_decode_cache", False)
+
+
+def kv_cache_nbytes(model):
+    """{state slot: bytes of its KV cache tensors} for every decode state ``model`` keeps: ``_mg_decode_cache``
+    (bf16 qkv rows, 6 D bytes per token and layer), ``_mg_kv8_cache`` (``kv_cache="int8"``: 2 D + 8 H bytes),
+    ``_mg_beam_cache``, ``_mg_spec_cache``."""
+    return {slot: model.__dict__[slot].cache_nbytes() for slot in _STATE_SLOTS if model.__dict__.get(slot) is not None}
+
+
 def _state_for(model, slot, idx, tmax, rows=None, last=None):
-    """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, or beside it ``_mg_beam_cache``
-    / ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain
+    """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, or beside it ``_mg_kv8_cache``
+    (the KV8 state of ``kv_cache="int8"``) and ``_mg_beam_cache`` / ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain
     loops and their graphs alone -- or a new one when the device, the rows or ``tmax`` differ.  The
     plain state comes back prefilled with ``idx`` (``last``: ``_GpuCache.prefill``); the others are
     prefilled by their callers, after the loop is built."""
     c = model.__dict__.get(slot)
     if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
-        c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows)
+        c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows, kv8=slot == "_mg_kv8_cache")
     elif rows is None:
         c.prefill(idx, last)
     return c
@@ -1004,8 +1087,17 @@ def _check_entry(who, model, max_new_tokens, idx=None, longest=None):
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
              top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
-             presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
-    """``repetition_penalty`` (finite, > 0; 1.0 off), ``presence_penalty``, ``frequency_penalty``
+             presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
+             kv_cache: str = "bf16"):
+    """``kv_cache``: ``"bf16"`` (default: every path as it is without the argument) or ``"int8"``, the KV8
+    model (the rule in common.h, ``ops.quant.snap_vectors``): every K and V vector -- one per sequence,
+    position, layer and head -- is snapped to int8 values times one power-of-two scale before any
+    attention reads it, prompt and new tokens alike, on the GPU and the CPU; Q is untouched.  On the GPU
+    the cache is then int8 with one fp32 scale per vector, 2 D + 8 H bytes per token and layer instead of
+    6 D, read by ``attention_decode_kv8`` (``_mg_kv8_cache``, a state of its own).  Needs ``use_cache``;
+    ValueError for any other string.
+
+    ``repetition_penalty`` (finite, > 0; 1.0 off), ``presence_penalty``, ``frequency_penalty``
     (finite; 0.0 off), ``no_repeat_ngram_size`` (0 .. 8; 0 off): the logits processors (the rule in
     common.h, 'Logits processors'), applied to the stored logits before the temperature, top-k, top-p
     and the draw; greedy takes the argmax of the processed row.  A token seen c >= 1 times in the
@@ -1036,6 +1128,10 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     (seed, column, batch row, logits) only, and on the GPU the whole token loop stays on the device
     (``_GpuCache.sample``).  ``seed=None`` leaves every path as it was."""
     bs = model.block_size
+    slot, kv8 = _kv_slot("generate", kv_cache)
+    if kv8 and not use_cache:
+        raise ValueError("generate: kv_cache='int8' needs use_cache=True (without a cache there is nothing to "
+                         "quantize)")
     seeded = do_sample and seed is not None
     if seeded or (do_sample and top_p is not None):
         R.check_sample_args(temperature, top_k, top_p)
@@ -1086,13 +1182,13 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         else:
             first = lambda c, T, ctx: c.logits.argmax(-1)
             loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs, proc=pwords, ctx=ctx)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords, slot)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
         if cache is None or T > bs:
             idx_cond = idx if T <= bs else idx[:, -bs:]
-            cache = _state_for(model, "_mg_decode_cache", idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond)
+            cache = _state_for(model, slot, idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond, kv8)
             cache.pos = idx_cond.size(1)
             logits = cache.logits
         logits = edit(logits, idx[:, max(0, T - bs):])
@@ -1108,7 +1204,8 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     return done(idx)
 
 
-def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False, proc=None):
+def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False, proc=None,
+                           slot="_mg_decode_cache"):
     """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
     window's first token ``first(cache, T, ctx)`` [B], then the device-side token loop ``loop(cache,
     tok, L, n, T, ctx)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
@@ -1119,7 +1216,7 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
     (``/root/reference/mingpt/model.py:333``).  ``logprobs``: the first token gets its
     log-probability from the prefill logits (``with_logprob``), ``loop`` returns a (tokens,
-    log-probabilities) pair, and so does this."""
+    log-probabilities) pair, and so does this.  ``slot``: the decode state's (``_kv_slot``)."""
     bs = model.block_size
     B, T0 = idx.shape
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
@@ -1134,7 +1231,7 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
-        cache = _state_for(model, "_mg_decode_cache", ctx, bs)
+        cache = _state_for(model, slot, ctx, bs)
         if proc is not None:
             cache.process_prefill(ctx, proc)
         tok = first(cache, T, ctx)
@@ -1189,7 +1286,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
                    top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
                    pad_token: int = 0, top_p: Optional[float] = None, return_logprobs: bool = False,
                    repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                   no_repeat_ngram_size: int = 0):
+                   no_repeat_ngram_size: int = 0, kv_cache: str = "bf16"):
     """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``, or
     with ``return_logprobs`` ``(tokens, lengths, logprobs)``: float32 of ``tokens``' shape, entry
     [b, j] the model's log-probability of ``tokens[b, j]`` given ``tokens[b, :j]`` at every generated
@@ -1215,9 +1312,12 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     far as its history -- never the padding, never another row.  With any of them on the reported
     log-probabilities are the processed rows'.
 
+    ``kv_cache``: ``"bf16"`` or ``"int8"``, the KV8 model and the int8 cache of ``generate``.
+
     On the GPU the right-padded batch is prefilled once and the token loop is one captured step
     replayed back to back (``_GpuCache.ragged``): per-row positions and finished flags live in
     device memory.  On the CPU each row runs through the cache path on its own."""
+    slot, kv8 = _kv_slot("generate_batch", kv_cache)
     rows, device = _ragged_prompts(prompts)
     V = model.config.vocab_size
     lens = [r.numel() for r in rows]
@@ -1240,9 +1340,10 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
         return (tokens, lengths, logprobs) if return_logprobs else (tokens, lengths)
     if device.type == "cuda":
         return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
-                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs, pwords)
+                                   do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs, pwords,
+                                   slot)
     for b, r in enumerate(rows):  # the executable definition of the semantics
-        cache = _CpuCache(model, r.view(1, -1))
+        cache = _CpuCache(model, r.view(1, -1), kv8)
         logits, n = cache.logits, lens[b]
         for _ in range(max_new_tokens):
             if proc is not None:  # the history is the row's own sequence so far
@@ -1264,7 +1365,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
 
 def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
-                        pad_token, top_p=None, logprobs=False, proc=None):
+                        pad_token, top_p=None, logprobs=False, proc=None, slot="_mg_decode_cache"):
     """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
     causal attention makes every position before a row's length exact -- take row b's logits at
     column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
@@ -1272,9 +1373,9 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     ``_EXIT_EVERY`` replays; stopping early changes nothing, since a step leaves finished rows as
     they are.  ``logprobs``: the loops with the lse kernel, and the state's ``lp`` buffer (zero but
     at the generated positions) as a third result.  ``proc`` (``_proc_words``): the loops with the
-    process kernel in front of the pick, the first pick included."""
+    process kernel in front of the pick, the first pick included.  ``slot``: the decode state's."""
     B, Lmax = idx.shape
-    cache = _state_for(model, "_mg_decode_cache", idx, model.block_size, last=lengths - 1)
+    cache = _state_for(model, slot, idx, model.block_size, last=lengths - 1)
     words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
     st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs, proc=proc)

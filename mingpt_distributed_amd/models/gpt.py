@@ -220,7 +220,8 @@ class GPT(nn.Module):
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                  top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
                  top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
+                 kv_cache: str = "bf16"):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
         prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
         ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
@@ -229,32 +230,37 @@ class GPT(nn.Module):
         returns ``(idx, logprobs)``, the model's log-probability of every generated token (0.0 at
         the prompt).  ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` /
         ``no_repeat_ngram_size``: the logits processors over the context the model saw, applied to
-        the logits before everything else (1.0 / 0.0 / 0.0 / 0: off)."""
+        the logits before everything else (1.0 / 0.0 / 0.0 / 0: off).  ``kv_cache="int8"``: the KV8
+        model -- K and V vectors snapped to int8 times a power-of-two scale, an int8 cache on the GPU
+        (``generation.generate``); needs ``use_cache``."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
                         top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs,
                         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                        frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+                        frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                        kv_cache=kv_cache)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
                        top_k: Optional[int] = None, seed: Optional[int] = None,
                        eos_token: Optional[int] = None, pad_token: int = 0, top_p: Optional[float] = None,
                        return_logprobs: bool = False, repetition_penalty: float = 1.0,
-                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0):
+                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
+                       kv_cache: str = "bf16"):
         """Decode prompts of different lengths in one batch, each row stopping at ``eos_token`` or
         after ``max_new_tokens``; returns ``(tokens, lengths)`` (``generation.generate_batch``).  No
         sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``.
         ``return_logprobs``: returns ``(tokens, lengths, logprobs)``.  The logits processors
-        (``repetition_penalty`` ...) are those of ``generate``, per row over its own sequence."""
+        (``repetition_penalty`` ...) are those of ``generate``, per row over its own sequence, and so
+        is ``kv_cache``."""
         from .generation import generate_batch
 
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, do_sample=do_sample,
                               top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token, top_p=top_p,
                               return_logprobs=return_logprobs, repetition_penalty=repetition_penalty,
                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                              no_repeat_ngram_size=no_repeat_ngram_size)
+                              no_repeat_ngram_size=no_repeat_ngram_size, kv_cache=kv_cache)
 
     @torch.no_grad()
     def generate_beam(self, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,

@@ -31,6 +31,10 @@ and the mean tokens per step.
 rows times power-of-two scales; on a GPU the decode steps then read int8 weights) and prints the largest
 relative rounding error.
 
+``--kv-int8`` keeps the KV cache as int8 with one power-of-two scale per (position, layer, head) K and V
+vector (``kv_cache="int8"``, the KV8 model: every attention reads the snapped K / V) and prints the cache
+bytes; it goes with sampling, ``--greedy`` and several prompts, not with ``--beams`` or ``--speculative``.
+
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
 """
@@ -84,6 +88,9 @@ def main(argv=None):
     ap.add_argument("--int8", action="store_true",
                     help="weight-only int8: snap the projections and the LM head to int8 rows with power-of-two "
                          "scales (GPT.quantize_int8_) before generating")
+    ap.add_argument("--kv-int8", action="store_true",
+                    help="int8 KV cache: K and V vectors snapped to int8 with one power-of-two scale each "
+                         "(kv_cache='int8'); not with --beams or --speculative")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -117,6 +124,8 @@ def main(argv=None):
         ap.error("the logits processors do not go with --beams or --speculative")
     if a.speculative and (len(texts) > 1 or a.beams):
         ap.error("--speculative takes one prompt and does not go with --beams")
+    if a.kv_int8 and (a.beams or a.speculative):
+        ap.error("--kv-int8 does not go with --beams or --speculative (they keep bf16 caches)")
     if len(texts) > 1:
         return generate_many(model, tok, texts, a, dev)
     prompt = texts[0] if texts else ""
@@ -129,10 +138,11 @@ def main(argv=None):
     if a.speculative:
         return generate_speculative(model, tok, x, a)
     x = x.expand(a.num_samples, -1).contiguous()
-    kw = dict({"return_logprobs": True} if a.logprobs else {}, **proc)
+    kw = dict({"return_logprobs": True} if a.logprobs else {}, **proc, **kv_args(a))
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
                        top_k=a.top_k, seed=a.seed, top_p=a.top_p, **kw)
     y, lp = y if a.logprobs else (y, None)
+    print_kv_bytes(model, a)
     outs = []
     for i in range(a.num_samples):
         out = tok.decode(y[i].cpu().squeeze()) if tok is not None else y[i].tolist()
@@ -151,6 +161,19 @@ def process_args(a):
               frequency_penalty=a.frequency_penalty, no_repeat_ngram_size=a.no_repeat_ngram)
     off = dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, no_repeat_ngram_size=0)
     return {k: v for k, v in kw.items() if v != off[k]}
+
+
+def kv_args(a):
+    """``kv_cache="int8"`` with ``--kv-int8``, else nothing (the call is what it is without it)."""
+    return {"kv_cache": "int8"} if a.kv_int8 else {}
+
+
+def print_kv_bytes(model, a):
+    """With ``--kv-int8``: the bytes of the KV caches the model's decode states hold (GPU only)."""
+    from mingpt_distributed_amd.models.generation import kv_cache_nbytes
+
+    if a.kv_int8:
+        print(f"(KV cache bytes by decode state: {kv_cache_nbytes(model) or 'none on this device'})")
 
 
 def print_logprob(lp):
@@ -202,10 +225,11 @@ def generate_many(model, tok, texts, a, dev):
         rows = [torch.tensor([int(w) for w in t.split()] or [0], dtype=torch.long) for t in texts]
         eos = None
     rows = [r.to(dev) for r in rows for _ in range(a.num_samples)]
-    kw = dict({"return_logprobs": True} if a.logprobs else {}, **process_args(a))
+    kw = dict({"return_logprobs": True} if a.logprobs else {}, **process_args(a), **kv_args(a))
     y, n, *lp = model.generate_batch(rows, max_new_tokens=a.steps, temperature=a.temperature,
                                      do_sample=not a.greedy, top_k=a.top_k, seed=a.seed, eos_token=eos,
                                      top_p=a.top_p, **kw)
+    print_kv_bytes(model, a)
     outs = []
     for i in range(len(rows)):
         ids = y[i, :int(n[i])].cpu()
