@@ -694,9 +694,10 @@ void kv8_cache_args(const char* op, const at::Tensor& kq, const at::Tensor& ks, 
 }
 
 // Snap the K and V thirds of qkv [B, T, 3D] in place by the KV8 rule (common.h); with kq / ks also
-// write the int8 cache's positions 0 .. T - 1
+// write the int8 cache's positions 0 .. T - 1; rep = W: the cache has B * rep rows, prompt b's go to rows
+// b * rep .. b * rep + rep - 1 (the beam prefill)
 void kv8_store(const at::Tensor& qkv, int64_t H, const c10::optional<at::Tensor>& kq,
-               const c10::optional<at::Tensor>& ks) {
+               const c10::optional<at::Tensor>& ks, int64_t rep) {
   CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) % 3 == 0, "kv8_store: qkv must be [B, T, 3D]");
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(2) / 3;
@@ -705,32 +706,38 @@ void kv8_store(const at::Tensor& qkv, int64_t H, const c10::optional<at::Tensor>
   TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, "kv8_store: qkv must be 16-byte aligned");
   const bool cache = kq.has_value() && kq->defined();
   TORCH_CHECK(cache == (ks.has_value() && ks->defined()), "kv8_store: kq and ks go together");
+  TORCH_CHECK(rep >= 1 && rep <= mg::kBeamMax && (cache || rep == 1), "kv8_store: rep in 1..8, with kq / ks");
   int64_t Tmax = T;
   if (cache) {
-    kv8_cache_args("kv8_store", *kq, *ks, B, H, D / H);
+    kv8_cache_args("kv8_store", *kq, *ks, B * rep, H, D / H);
     Tmax = kq->size(3);
     TORCH_CHECK(T <= Tmax && kq->device() == qkv.device(), "kv8_store: T exceeds the cache's Tmax");
   }
   if (B * T == 0) return;
   DevGuard g(qkv.device());
   mg::kv8_store(bp(qkv), cache ? kq->data_ptr<int8_t>() : nullptr, cache ? fp(*ks) : nullptr, (int)B, (int)T,
-                (int)H, (int)(D / H), Tmax, cur_stream());
+                (int)H, (int)(D / H), Tmax, cur_stream(), (int)rep);
 }
 
-// attention_decode on the int8 cache (no group): pos / pos_dev / part / counters / pos_stride as there
+// attention_decode on the int8 cache: pos / pos_dev / part / counters / pos_stride / group as there (group =
+// K: kq / ks of B sequences, qkv_new [B * K, 3D], pos_dev int32 [B * K], the workspace for B * K rows)
 at::Tensor attention_decode_kv8(const at::Tensor& qkv_new, const at::Tensor& kq, const at::Tensor& ks, int64_t H,
                                 int64_t pos, const c10::optional<at::Tensor>& pos_dev,
                                 const c10::optional<at::Tensor>& part, const c10::optional<at::Tensor>& counters,
-                                int64_t pos_stride) {
+                                int64_t pos_stride, int64_t group) {
   CHECK_BF16(qkv_new); CHECK_CONTIG(qkv_new);
   TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) % 3 == 0, "attention_decode_kv8: qkv_new must be [B, 3D]");
+  TORCH_CHECK(group >= 1 && group <= mg::kSpecRowsMax, "attention_decode_kv8: group must be in 1..8");
+  TORCH_CHECK(group == 1 || (pos_dev.has_value() && pos_dev->defined() && pos_stride == 1),
+              "attention_decode_kv8: group > 1 needs pos_dev with pos_stride 1");
   const int64_t B = qkv_new.size(0), D = qkv_new.size(1) / 3;
+  TORCH_CHECK(B % group == 0, "attention_decode_kv8: qkv_new must hold group rows per sequence");
   TORCH_CHECK(B >= 1 && H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
               "attention_decode_kv8: head dim must be a multiple of 8, at most 128");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0,
               "attention_decode_kv8: qkv_new must be 16-byte aligned");
   const int64_t hd = D / H;
-  kv8_cache_args("attention_decode_kv8", kq, ks, B, H, hd);
+  kv8_cache_args("attention_decode_kv8", kq, ks, B / group, H, hd);
   TORCH_CHECK(kq.device() == qkv_new.device(), "attention_decode_kv8: the cache is on another device");
   const int64_t Tmax = kq.size(3);
   TORCH_CHECK(pos >= 0 && pos < Tmax, "attention_decode_kv8: pos outside the cache");
@@ -762,9 +769,9 @@ at::Tensor attention_decode_kv8(const at::Tensor& qkv_new, const at::Tensor& kq,
     pt = at::empty({np}, qkv_new.options().dtype(at::kFloat));
     ct = at::zeros({B * H}, qkv_new.options().dtype(at::kInt));
   }
-  mg::attention_decode_kv8(bp(qkv_new), kq.data_ptr<int8_t>(), fp(ks), bp(out), (int)B, (int)H, (int)hd, Tmax,
-                           (int)pos, cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd,
-                           (int)pos_stride);
+  mg::attention_decode_kv8(bp(qkv_new), kq.data_ptr<int8_t>(), fp(ks), bp(out), (int)(B / group), (int)H, (int)hd,
+                           Tmax, (int)pos, cur_stream(), fp(pt), reinterpret_cast<unsigned*>(ct.data_ptr<int>()), pd,
+                           (int)pos_stride, (int)group);
   return out;
 }
 
@@ -1067,6 +1074,41 @@ void beam_reorder(const at::Tensor& kv, int64_t W, const at::Tensor& parent, con
                    pos.data_ptr<int>(), cp, cur_stream());
 }
 
+// The cache reorder on kq int8 [L, R, 2, H, Tmax, hd] and ks fp32 [L, R, 2, H, Tmax] (one layer: L = 1;
+// layers may be a strided stack of contiguous blocks), parent int32 [R], pos int32 [1]: positions t < pos.
+// ctl (optional): its history column advances.
+void beam_reorder_kv8(const at::Tensor& kq, const at::Tensor& ks, int64_t W, const at::Tensor& parent,
+                      const at::Tensor& pos, const c10::optional<at::Tensor>& ctl) {
+  CHECK_DEV(kq); CHECK_F32(ks);
+  TORCH_CHECK(kq.scalar_type() == at::kChar, "beam_reorder_kv8: kq must be int8");
+  TORCH_CHECK(kq.dim() == 6 && kq.size(0) >= 1 && kq[0].is_contiguous() && kq.size(2) == 2,
+              "beam_reorder_kv8: kq [L, R, 2, H, Tmax, hd], every layer contiguous");
+  const int64_t L = kq.size(0), R = kq.size(1), H = kq.size(3), Tmax = kq.size(4), hd = kq.size(5);
+  TORCH_CHECK(ks.dim() == 5 && ks.size(0) == L && ks.size(1) == R && ks.size(2) == 2 && ks.size(3) == H &&
+              ks.size(4) == Tmax && ks[0].is_contiguous() && ks.device() == kq.device(),
+              "beam_reorder_kv8: ks must be [L, R, 2, H, Tmax] beside kq, every layer contiguous");
+  const int64_t lq = L > 1 ? kq.stride(0) : 0, lsc = L > 1 ? ks.stride(0) : 0;
+  TORCH_CHECK(W >= 1 && W <= mg::kBeamMax && R >= W && R % W == 0,
+              "beam_reorder_kv8: 1 <= W <= 8, R a multiple of W");
+  TORCH_CHECK(H >= 1 && hd >= 8 && hd % 8 == 0 && hd <= 128 &&
+              reinterpret_cast<uintptr_t>(kq.data_ptr()) % 16 == 0 && lq % 16 == 0 && lq >= 0 &&
+              reinterpret_cast<uintptr_t>(ks.data_ptr()) % 4 == 0 && lsc >= 0,
+              "beam_reorder_kv8: hd % 8 == 0, at most 128, and 16-byte aligned layers");
+  TORCH_CHECK(Tmax >= 1 && 2 * H * Tmax * (hd / 8 + 1) <= 0x7fffffff - 256 && R / W <= 65535 && L <= 65535,
+              "beam_reorder_kv8: cache too large for one launch");
+  const at::Device dev = kq.device();
+  dev_i32("beam_reorder_kv8", "parent", parent, R, dev);
+  dev_i32("beam_reorder_kv8", "pos", pos, 1, dev);
+  int* cp = nullptr;
+  if (ctl.has_value() && ctl->defined()) {
+    dev_i32("beam_reorder_kv8", "ctl", *ctl, mg::kBeamCtlWords, dev);
+    cp = ctl->data_ptr<int>();
+  }
+  DevGuard g(dev);
+  mg::beam_reorder_kv8(kq.data_ptr<int8_t>(), fp(ks), (int)L, lq, lsc, (int)(R / W), (int)W, (int)H, (int)Tmax,
+                       (int)hd, parent.data_ptr<int>(), pos.data_ptr<int>(), cp, cur_stream());
+}
+
 // ------------------------------------------------------------------------------- speculative decoding
 // spec.hip (kernels.h).  B sequences, K rows each; every buffer lives on seq's / the logits' device and
 // is updated in place.
@@ -1294,10 +1336,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);
   m.def("kv8_store", &kv8_store, py::arg("qkv"), py::arg("H"), py::arg("kq") = py::none(),
-        py::arg("ks") = py::none());
+        py::arg("ks") = py::none(), py::arg("rep") = 1);
   m.def("attention_decode_kv8", &attention_decode_kv8, py::arg("qkv_new"), py::arg("kq"), py::arg("ks"),
         py::arg("H"), py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
-        py::arg("counters") = py::none(), py::arg("pos_stride") = 0);
+        py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);
   m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("V"), py::arg("params"),
         py::arg("pos_dev") = py::none(), py::arg("tok") = py::none(), py::arg("seq") = py::none(),
         py::arg("lse") = py::none(), py::arg("lp") = py::none());
@@ -1317,6 +1359,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hist_tok"), py::arg("hist_score"), py::arg("pos"), py::arg("ctl"));
   m.def("beam_reorder", &beam_reorder, py::arg("kv"), py::arg("W"), py::arg("parent"), py::arg("pos"),
         py::arg("ctl") = py::none());
+  m.def("beam_reorder_kv8", &beam_reorder_kv8, py::arg("kq"), py::arg("ks"), py::arg("W"), py::arg("parent"),
+        py::arg("pos"), py::arg("ctl") = py::none());
   m.def("spec_draft", &spec_draft, py::arg("seq"), py::arg("pos"), py::arg("ctl"), py::arg("K"), py::arg("tok"),
         py::arg("pos_rows"), py::arg("has_draft"));
   m.def("spec_argmax", &spec_argmax, py::arg("logits"), py::arg("V"), py::arg("g") = py::none());

@@ -437,7 +437,7 @@ MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* res
 // (s_n * sum + bias may contract to one fma: the product is exact, so the result is the same.)
 
 // ---------------------------------------------------------------- KV8: int8 K / V vectors, power-of-two scales
-// The int8 KV cache (kv_cache="int8" on generate and generate_batch; attention_kv8.hip;
+// The int8 KV cache (kv_cache="int8" on every entry point that keeps or reads K / V; attention_kv8.hip;
 // ops/quant.py snap_vectors is the rule in torch ops).  A vector u[0 .. hd-1] is the K, or separately
 // the V, of one (sequence, position, layer, head): bf16 as c_attn wrote it on the GPU, the model's dtype
 // on the CPU.  With a = max |u|:
@@ -457,8 +457,9 @@ MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* res
 // float(q) * s is exact and equals the snapped bf16 value, and attention_decode_kv8 runs the bf16 kernel's
 // fma chains on it -- no scale is folded out of a sum, so there is no precondition: it equals
 // attention_decode on the snapped row over a bf16 cache of the dequantized rows bit for bit.
-// Limits: generate and generate_batch only (generate_beam, generate_speculative and score keep bf16
-// caches; use_cache=False has no cache and is a ValueError); one scale per vector, no per-channel or
+// The rows of a group (speculative verify rows) are snapped before any row of the group reads them, and a
+// beam reorder moves (q, s) pairs unchanged.
+// Limits: use_cache=False has no cache and is a ValueError; one scale per vector, no per-channel or
 // grouped scales; int8 only, no fp8 or 4-bit; hd % 8 == 0, hd <= 128, Tmax <= 4096; the quality of
 // the KV8 model on pretrained weights is not measured.
 

@@ -283,14 +283,35 @@ void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, 
 // hd % 8 == 0, hd <= 128; hd / 8 need not be a power of two.
 // kv8_store: snap the K and V thirds of qkv [B, T, 3D] in place per (b, t, head) -- the Q third is
 // not touched -- and, with kq / ks given (both or neither), write the int8 values and scales of
-// positions 0 .. T - 1 (T <= Tmax; later positions are left alone).
-void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, long Tmax, hipStream_t stream);
-// attention_decode on the int8 cache, without group: appends the rule's (q, s) of qkv_new's K/V at
-// position pos (qkv_new itself is not modified) and writes out [B, D] -- bit for bit what
-// attention_decode writes for qkv_new with its K/V thirds snapped over a bf16 cache holding the
-// dequantized rows.  part / counters / pos_dev / pos_stride and Tmax <= 4096: attention_decode's.
+// positions 0 .. T - 1 (T <= Tmax; later positions are left alone).  rep = W > 1 (the beam prefill): kq /
+// ks have B * rep cache rows and prompt b's (q, s) go to rows b * rep .. b * rep + rep - 1 -- one snap,
+// W stores.
+void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, long Tmax, hipStream_t stream,
+               int rep = 1);
+// attention_decode on the int8 cache: appends the rule's (q, s) of qkv_new's K/V at position pos
+// (qkv_new itself is not modified) and writes out [B, D] -- bit for bit what attention_decode writes
+// for qkv_new with its K/V thirds snapped over a bf16 cache holding the dequantized rows.  part /
+// counters / pos_dev / pos_stride and Tmax <= 4096: attention_decode's.
+// group = K > 1 (needs pos_dev, one int per row): attention_decode's grouped form on kq / ks of B
+// sequences, qkv_new [B * K, 3D], out [B * K, D], the workspace sized for B * K rows.  Row m = b * K + r
+// sits at base + r, base = pos_dev[b * K] clamped to [0, Tmax): keys j < base come from sequence b's
+// cache, keys j >= base from qkv_new row b * K + (j - base), snapped by the rule in the workgroup (rows
+// 0 .. r of the head) and never read from the cache, so the group's appends cannot race its reads.
+// Split 0 of row r appends the (q, s) of its own K/V at cache row base + r.  A row with base + r >
+// Tmax - 1 appends nothing, touches no counter and gets a zero out row.  Se, CH, the key order, the
+// rounding steps, the hand-off and the combine are the plain kernel's at that position (keys per
+// split from B sequences): out and the final cache equal K plain calls at base + r, r = 0 .. K - 1,
+// bit for bit, and out equals attention_decode(group = K) on the snapped rows over the dequantized cache.
 void attention_decode_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, int B, int H, int hd,
                           long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                          const int* pos_dev = nullptr, int pos_stride = 0);
+                          const int* pos_dev = nullptr, int pos_stride = 0, int group = 1);
+// beam_reorder on the int8 cache, in place over L layers (kq_layer / ks_layer elements apart): kq int8
+// [L, R, 2, H, Tmax, hd], ks fp32 [L, R, 2, H, Tmax], R = B * W.  For every (K | V, head), positions t <
+// min(*pos, Tmax) of beam r of a prompt become those of beam parent[r] of the same prompt, int8 bytes
+// and scale words alike ((q, s) pairs move unchanged).  Later positions, identity prompts and every
+// other byte are not touched; a parent outside [0, W) counts as identity.  ctl (optional): ctl[0]
+// advances by one.
+void beam_reorder_kv8(int8_t* kq, float* ks, int L, long kq_layer, long ks_layer, int B, int W, int H, int Tmax,
+                      int hd, const int* parent, const int* pos, int* ctl, hipStream_t stream);
 
 }  // namespace mg

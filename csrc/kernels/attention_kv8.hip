@@ -5,7 +5,10 @@
 //   attention_decode_kv8  attention.hip's split-key decode kernel with the loads swapped: keys and
 //                         values come as 8 / 16 bytes of int8 plus one fp32 scale per key, the new
 //                         token's K/V are snapped into LDS by every workgroup of the head and stored
-//                         by split 0.
+//                         by split 0.  GROUPED (group = K rows per sequence): attention.hip's grouped
+//                         form -- row r of a group sits at base + r, snaps rows 0 .. r of its group
+//                         into LDS (keys j >= base never come from the cache) and appends its own.
+//   beam_reorder_kv8      beam.hip's in-place reorder on the int8 layout: (q, s) pairs move unchanged.
 //
 // Cache layout per layer: kq int8 [B, 2, H, Tmax, hd] (K then V; the rows of a (b, h) are contiguous)
 // and ks fp32 [B, 2, H, Tmax].  A dequantized element float(q) * s is exact (7 bits times a power of
@@ -107,9 +110,10 @@ MG_DEVICE void dequant8(const uint2& u, float s, float (&f)[8]) {
 // One thread per 16-byte chunk; the dch = hd / 8 chunks of a vector sit in consecutive threads of one
 // workgroup (256 / dch whole vectors per workgroup) and meet through LDS.  Vector v = ((b * T + t) * 2
 // + w) * H + h, so consecutive threads walk consecutive addresses of the K and V thirds.
+// rep > 1 (beam prefill): the cache has B * rep rows and prompt b's (q, s) go to rows b * rep .. b * rep + rep - 1.
 __global__ __launch_bounds__(256) void kv8_store_kernel(bf16_t* __restrict__ qkv, int8_t* __restrict__ kq,
                                                         float* __restrict__ ks, long NV, int T, int H, int hd,
-                                                        long Tmax) {
+                                                        long Tmax, int rep) {
   __shared__ uint32_t cm[256];
   const int dch = hd >> 3, vpb = 256 / dch;
   const int lv = threadIdx.x / dch, c = threadIdx.x % dch;
@@ -140,60 +144,82 @@ __global__ __launch_bounds__(256) void kv8_store_kernel(bf16_t* __restrict__ qkv
   st16(src, pack8(f));  // s * q is a bf16 value: the conversion is exact
   if (kq) {
     const long b = bt / T, t = bt % T;
-    const long row = ((b * 2 + w) * H + h) * Tmax + t;
-    st8(kq + row * hd + c * 8, q8);
-    if (c == 0) ks[row] = s;
+    for (int i = 0; i < rep; ++i) {
+      const long row = (((b * rep + i) * 2 + w) * H + h) * Tmax + t;
+      st8(kq + row * hd + c * 8, q8);
+      if (c == 0) ks[row] = s;
+    }
   }
 }
 
 // ------------------------------------------------------------------------------ decode
-// attention.hip's attn_decode_kernel<false> on the int8 cache; what differs is marked KV8.
+// attention.hip's attn_decode_kernel<GROUPED> on the int8 cache; what differs is marked KV8.  GROUPED:
+// blockIdx.x / (H * S) is the row m = b * group + r; the row's group is snapped into nkv[g * 256 ..],
+// g = 0 .. r (at most 8 * 2 * hd / 8 = 256 chunk-threads: the workgroup), and keys j >= base are
+// nkv[(j - base) * 256 ..].  The plain instantiation is the code as it was.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16_t* __restrict__ qkv_new,
                                                               int8_t* __restrict__ kq, float* __restrict__ ks,
                                                               bf16_t* __restrict__ out, int H, int hd, int D,
                                                               long Tmax, int pos, const int* __restrict__ pos_dev,
                                                               float scale_log2, int S, int KPS,
                                                               float* __restrict__ part,
-                                                              unsigned* __restrict__ counters, int pos_stride) {
+                                                              unsigned* __restrict__ counters, int pos_stride,
+                                                              int group) {
   __shared__ float qs[128];
   __shared__ float sc[256];
   __shared__ float vs[256];   // KV8: the V scale of the split's key t
-  __shared__ float nkv[256];  // KV8: the new token's snapped K [0, 128) and V [128, 256) of this head
-  __shared__ uint32_t cm[32];
+  // KV8: the new token's snapped K [0, 128) and V [128, 256) of this head; GROUPED: of group row g at g * 256
+  __shared__ float nkv[GROUPED ? 8 * 256 : 256];
+  __shared__ uint32_t cm[GROUPED ? 256 : 32];
   __shared__ float red[16];
   __shared__ float acc[256 * 8];
   __shared__ int last_flag;
   const int bh = blockIdx.x / S, sp = blockIdx.x % S;
   const int b = bh / H, hh = bh % H;
-  if (pos_dev) pos = min(max(pos_dev[(long)b * pos_stride], 0), (int)Tmax - 1);
+  int base = 0, m0 = b, cb = b;  // GROUPED: the group's first position and first row; the sequence (cache row)
+  if constexpr (GROUPED) {
+    m0 = (b / group) * group;
+    cb = b / group;
+    base = min(max(pos_dev[m0], 0), (int)Tmax - 1);
+    pos = base + (b - m0);
+    if (pos > (int)Tmax - 1) {  // the whole workgroup: no room for this row
+      if (sp == 0 && threadIdx.x < hd) out[(long)b * D + hh * hd + threadIdx.x] = 0;
+      return;
+    }
+  } else {
+    if (pos_dev) pos = min(max(pos_dev[(long)b * pos_stride], 0), (int)Tmax - 1);
+  }
   const int L = pos + 1;
   const int Se = min(S, (L + KPS - 1) / KPS);
   if (sp >= Se) return;  // never counted: the last arrival is the Se-th (split 0, which appends, stays)
   const long ld = 3L * D;
   const bf16_t* qrow = qkv_new + (long)b * ld + hh * hd;
   const int dch = hd >> 3;
-  const long rowk = ((long)(b * 2) * H + hh) * Tmax, rowv = ((long)(b * 2 + 1) * H + hh) * Tmax;
+  const long rowk = ((long)(cb * 2) * H + hh) * Tmax, rowv = ((long)(cb * 2 + 1) * H + hh) * Tmax;
   // KV8: snap this step's K/V of the head into LDS (every split: row pos is never read from the
   // cache in the launch that writes it); split 0 appends the int8 row and its scale
   uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-  const int nw = threadIdx.x / dch, nc = threadIdx.x % dch;  // vector (0: K, 1: V) and chunk
-  if (threadIdx.x < 2 * dch) {
-    raw = ld16(qrow + (long)D * (1 + nw) + nc * 8);
+  const int nv = threadIdx.x / dch, nc = threadIdx.x % dch;  // vector and chunk
+  const int ng = GROUPED ? nv >> 1 : 0, nw = GROUPED ? nv & 1 : nv;  // group row; 0: K, 1: V
+  const int nsnap = (GROUPED ? 2 * (pos - base + 1) : 2) * dch;      // GROUPED: rows 0 .. r of the group
+  if (threadIdx.x < nsnap) {
+    raw = ld16(qkv_new + (long)(m0 + ng) * ld + hh * hd + (long)D * (1 + nw) + nc * 8);
     cm[threadIdx.x] = max_abs8(raw);
   }
   for (int d = threadIdx.x; d < hd; d += 256) qs[d] = bf2f(qrow[d]);
   __syncthreads();
-  if (threadIdx.x < 2 * dch) {
+  if (threadIdx.x < nsnap) {
     uint32_t a15 = 0;
-    for (int i = 0; i < dch; ++i) a15 = max(a15, cm[nw * dch + i]);
+    for (int i = 0; i < dch; ++i) a15 = max(a15, cm[nv * dch + i]);
     int ex;
     bool live;
     const float s = kv8_scale(a15, ex, live);
     float f[8];
     const uint2 q8 = kv8_quant8(raw, ex, live, s, f);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) nkv[nw * 128 + nc * 8 + e] = f[e];
-    if (sp == 0) {
+    for (int e = 0; e < 8; ++e) nkv[ng * 256 + nw * 128 + nc * 8 + e] = f[e];
+    if (sp == 0 && m0 + ng == b) {  // its own row
       const long row = (nw ? rowv : rowk) + pos;
       st8(kq + row * hd + nc * 8, q8);
       if (nc == 0) ks[row] = s;
@@ -208,8 +234,9 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16_t* __re
   if (threadIdx.x < nk) {
     const int j = k0 + threadIdx.x;
     float a = 0.f;
-    if (j == pos) {
-      for (int d = 0; d < hd; ++d) a = score_step(a, qs[d], nkv[d]);
+    if (GROUPED ? j >= base : j == pos) {
+      const float* nk_ = nkv + (GROUPED ? (j - base) * 256 : 0);
+      for (int d = 0; d < hd; ++d) a = score_step(a, qs[d], nk_[d]);
       vs[threadIdx.x] = 0.f;
     } else {
       const float sk = ks[rowk + j];
@@ -254,16 +281,17 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16_t* __re
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int j = k0 + jj + u * ngrp;
-        vv[u] = j == pos ? make_uint2(0u, 0u) : ld8(vb + (long)j * hd);
+        vv[u] = (GROUPED ? j >= base : j == pos) ? make_uint2(0u, 0u) : ld8(vb + (long)j * hd);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int t = jj + u * ngrp;
         float v8[8];
         dequant8(vv[u], vs[t], v8);
-        if (k0 + t == pos) {
+        if (GROUPED ? k0 + t >= base : k0 + t == pos) {
+          const float* nv_ = nkv + (GROUPED ? (k0 + t - base) * 256 : 0) + 128 + d8;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v8[e] = nkv[128 + d8 + e];
+          for (int e = 0; e < 8; ++e) v8[e] = nv_[e];
         }
         const float pj = sc[t];
 #pragma unroll
@@ -275,9 +303,10 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16_t* __re
     for (; jj < nk; jj += ngrp) {
       const int j = k0 + jj;
       float v8[8];
-      if (j == pos) {
+      if (GROUPED ? j >= base : j == pos) {
+        const float* nv_ = nkv + (GROUPED ? (j - base) * 256 : 0) + 128 + d8;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v8[e] = nkv[128 + d8 + e];
+        for (int e = 0; e < 8; ++e) v8[e] = nv_[e];
       } else {
         dequant8(ld8(vb + (long)j * hd), vs[jj], v8);
       }
@@ -346,25 +375,121 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const bf16_t* __re
   if (threadIdx.x == 0) __hip_atomic_store(counters + bh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ------------------------------------------------------------------------------ beam reorder
+// beam.hip's reorder on kq int8 [L, R, 2, H, Tmax, hd] and ks fp32 [L, R, 2, H, Tmax], R = B * W: for
+// prompt blockIdx.y in layer blockIdx.z, positions t < min(*pos, Tmax) of every (K | V, head) block of
+// beam r become those of beam parent[r].  A thread owns one chunk of the int8 bytes at (K | V, head, t)
+// -- CT = 16 bytes where hd % 16 == 0, else 8: a block starts at a multiple of Tmax * hd bytes, which
+// is only 8-byte aligned for hd % 16 == 8 with odd Tmax -- or one scale word (rows of Tmax words are
+// only 4-byte aligned for odd Tmax), loads it from all W beams and stores the permutation; a beam
+// that keeps its rows stores nothing.  Per (K | V, head) the items are the Tmax * cpv chunks, then the
+// Tmax scale words.
+typedef unsigned kv8_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned kv8_u2 __attribute__((ext_vector_type(2)));
+
+template <int W, typename T>
+MG_DEVICE void reorder_item(T* p, long beam_stride, const int (&par)[W]) {
+  T v[W];
+#pragma unroll
+  for (int r = 0; r < W; ++r) v[r] = p[r * beam_stride];
+#pragma unroll
+  for (int r = 0; r < W; ++r) {
+    // uniform branches over constant register indices, as in beam.hip
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+      if (q != r && par[r] == q) p[r * beam_stride] = v[q];
+    }
+  }
+}
+
+template <int W, typename CT>
+__global__ __launch_bounds__(256) void beam_reorder_kv8_kernel(int8_t* __restrict__ kq, float* __restrict__ ks,
+                                                               long kq_layer, long ks_layer, int H2, int Tmax,
+                                                               int hd, const int* __restrict__ parent,
+                                                               const int* __restrict__ pos, int* ctl,
+                                                               unsigned* err) {
+  if (ctl && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) ctl[0] += 1;
+  const int b = blockIdx.y;
+  int par[W];
+  bool ident = true;
+#pragma unroll
+  for (int r = 0; r < W; ++r) {
+    int p = parent[b * W + r];
+    MG_CHECK_INDEX(p, p >= 0 && p < W, r, err, 16u);
+    if (p < 0 || p >= W) p = r;
+    par[r] = p;
+    ident = ident && p == r;
+  }
+  if (ident) return;
+  int n = pos[0];
+  n = n < Tmax ? n : Tmax;
+  constexpr int CB = (int)sizeof(CT);
+  const int cpv = hd / CB;            // chunks per vector
+  const int per = Tmax * (cpv + 1);   // items per (K | V, head): chunks, then scale words
+  const int idx = blockIdx.x * 256 + (int)threadIdx.x;
+  const int wh = idx / per, rem = idx - wh * per;
+  if (wh >= H2) return;
+  const long blk = (long)b * W * H2 + wh;  // beam 0's (row, K | V, head) block
+  if (rem < Tmax * cpv) {
+    const int t = rem / cpv, c = rem - t * cpv;
+    if (t >= n) return;
+    int8_t* p = kq + blockIdx.z * kq_layer + (blk * Tmax + t) * hd + c * CB;
+    reorder_item<W>(reinterpret_cast<CT*>(p), (long)H2 * Tmax * hd / CB, par);
+  } else {
+    const int t = rem - Tmax * cpv;
+    if (t >= n) return;
+    reorder_item<W>(ks + blockIdx.z * ks_layer + blk * Tmax + t, (long)H2 * Tmax, par);
+  }
+}
+
+
 }  // namespace
 
 namespace mg {
 
-void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, long Tmax, hipStream_t stream) {
+void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, long Tmax, hipStream_t stream,
+               int rep) {
   const long NV = (long)B * T * 2 * H;
   const int vpb = 256 / (hd >> 3);
-  kv8_store_kernel<<<cdiv(NV, vpb), 256, 0, stream>>>(qkv, kq, ks, NV, T, H, hd, Tmax);
+  kv8_store_kernel<<<cdiv(NV, vpb), 256, 0, stream>>>(qkv, kq, ks, NV, T, H, hd, Tmax, rep);
 }
 
 void attention_decode_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, int B, int H, int hd,
                           long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
-                          const int* pos_dev, int pos_stride) {
-  // the grid, the split count and the keys per split are attention_decode's
+                          const int* pos_dev, int pos_stride, int group) {
+  // the grid, the split count and the keys per split are attention_decode's (B: sequences)
   const int S = kDecSplitsMax;
   const int kps = B * H <= 32 ? 256 : 128;
-  attn_decode_kv8_kernel<<<B * H * S, 256, 0, stream>>>(qkv_new, kq, ks, out, H, hd, H * hd, Tmax, pos, pos_dev,
-                                                        1.4426950408889634f / sqrtf((float)hd), S, kps, part,
-                                                        counters, pos_stride);
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
+  if (group > 1) {
+    attn_decode_kv8_kernel<true><<<B * group * H * S, 256, 0, stream>>>(
+        qkv_new, kq, ks, out, H, hd, H * hd, Tmax, pos, pos_dev, scale_log2, S, kps, part, counters, pos_stride, group);
+    return;
+  }
+  attn_decode_kv8_kernel<false><<<B * H * S, 256, 0, stream>>>(qkv_new, kq, ks, out, H, hd, H * hd, Tmax, pos, pos_dev,
+                                                               scale_log2, S, kps, part, counters, pos_stride, group);
+}
+
+void beam_reorder_kv8(int8_t* kq, float* ks, int L, long kq_layer, long ks_layer, int B, int W, int H, int Tmax,
+                      int hd, const int* parent, const int* pos, int* ctl, hipStream_t stream) {
+  const bool wide = hd % 16 == 0;
+  const long items = 2L * H * Tmax * (hd / (wide ? 16 : 8) + 1);
+  const dim3 grid(cdiv(items, 256), B, L);
+#define MG_BEAM_REORDER_KV8(w)                                                                                \
+  case w:                                                                                                     \
+    if (wide)                                                                                                 \
+      beam_reorder_kv8_kernel<w, kv8_u4><<<grid, 256, 0, stream>>>(kq, ks, kq_layer, ks_layer, 2 * H, Tmax, hd, \
+                                                                  parent, pos, ctl, debug_err_word());        \
+    else                                                                                                      \
+      beam_reorder_kv8_kernel<w, kv8_u2><<<grid, 256, 0, stream>>>(kq, ks, kq_layer, ks_layer, 2 * H, Tmax, hd, \
+                                                                  parent, pos, ctl, debug_err_word());        \
+    break;
+  switch (W) {
+    MG_BEAM_REORDER_KV8(1) MG_BEAM_REORDER_KV8(2) MG_BEAM_REORDER_KV8(3) MG_BEAM_REORDER_KV8(4)
+    MG_BEAM_REORDER_KV8(5) MG_BEAM_REORDER_KV8(6) MG_BEAM_REORDER_KV8(7) MG_BEAM_REORDER_KV8(8)
+    default: break;  // the binding admits 1 .. 8
+  }
+#undef MG_BEAM_REORDER_KV8
 }
 
 }  // namespace mg

@@ -13,9 +13,10 @@ Layout of this file, top to bottom:
   ``_blocks``, ``_head``, ``_prompt``.  ``score`` needs nothing else.
 * ``_GpuCache(_Body)``: one decode state -- KV caches, workspaces, the weights' stamp, the two step
   bodies (``prefill``, ``_decode``) and every token loop as a closure around ``_decode`` that ends with
-  the loop's own tail.  A model keeps up to four (``_state_for``): ``_mg_decode_cache``, ``_mg_kv8_cache``
-  (``kv_cache="int8"``: the KV8 model on int8 caches), ``_mg_beam_cache`` (B * W rows) and
-  ``_mg_spec_cache`` (B sequences, B * K step rows).
+  the loop's own tail.  A model keeps up to six (``_state_for``): ``_mg_decode_cache``, ``_mg_beam_cache``
+  (B * W rows) and ``_mg_spec_cache`` (B sequences, B * K step rows), and beside each the state of
+  ``kv_cache="int8"`` (the KV8 model on int8 caches): ``_mg_kv8_cache``, ``_mg_beam_kv8_cache`` and
+  ``_mg_spec_kv8_cache``.
 * the word builders, ``_state_for``, then one section per entry point: checks, host loop, GPU half.
 
 Who owns what.  A loop in ``_loops`` owns its graph and, for the rectangular loops, its ``tok`` /
@@ -60,9 +61,10 @@ def _sample(logits, temperature, do_sample, top_k, top_p=None):
 
 # ------------------------------------------------------------------------------------ CPU
 class _CpuCache:
-    def __init__(self, model, idx, kv8=False):
+    def __init__(self, model, idx, kv8=False, every=False):
         """``kv8``: the KV8 model (common.h) -- every K and V vector is snapped (``snap_vectors``) before
-        any attention reads it, in the prompt pass and in ``step``."""
+        any attention reads it, in the prompt pass and in ``step``.  ``every``: ``logits`` holds every
+        position's, [B, T, V] (``score`` and the speculative verify rows), not the last one's."""
         self.model = model
         self.k, self.v = [], []
         self.snap = (lambda t: snap_vectors(t)[2]) if kv8 else (lambda t: t)
@@ -74,11 +76,11 @@ class _CpuCache:
             self.v.append(v)
             return R.causal_attention(q, k, v, 0.0, False)
 
-        self.logits = self._body(tr.wte.weight[idx] + tr.wpe.weight[:idx.size(1)], attend)
+        self.logits = self._body(tr.wte.weight[idx] + tr.wpe.weight[:idx.size(1)], attend, every)
 
-    def _body(self, x, attend):
-        """Last-position logits of the blocks and the LM head on x [B, T, C]; layer i's attention
-        output is ``attend(i, q, k, v)`` ([B, H, T, hd] each)."""
+    def _body(self, x, attend, every=False):
+        """Last-position logits (``every``: all positions') of the blocks and the LM head on x [B, T, C];
+        layer i's attention output is ``attend(i, q, k, v)`` ([B, H, T, hd] each)."""
         m = self.model
         tr = m.transformer
         B, T, C = x.shape
@@ -90,7 +92,7 @@ class _CpuCache:
             y = attend(i, f(q), f(k), f(v)).transpose(1, 2).reshape(B, T, C)
             x = x + F.linear(y, blk.attn.c_proj.weight, blk.attn.c_proj.bias)
             x = x + blk.mlp(blk.ln_2(x))
-        return m.lm_head(tr.ln_f(x[:, -1]))
+        return m.lm_head(tr.ln_f(x if every else x[:, -1]))
 
     def step(self, tok, pos):
         tr = self.model.transformer
@@ -387,20 +389,20 @@ class _GpuCache(_Body):
         """``rows`` (beam search, speculative decoding): a state of that many decode rows whose
         layers' caches are one stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks
         every layer in one launch), not prefilled here -- ``idx`` only names the device.
-        ``kv8`` (``kv_cache="int8"``; not with ``rows``): a state of the KV8 model (common.h).  With
-        ``_KV8_DECODE`` on its caches are ``kq`` int8 [B, 2, H, Tmax, hd] and ``ks`` float32 [B, 2, H,
-        Tmax] per layer, off they are bf16 qkv rows holding snapped K/V (``_kv8_storage``)."""
+        ``kv8`` (``kv_cache="int8"``): a state of the KV8 model (common.h).  With ``_KV8_DECODE`` on its
+        caches are ``kq`` int8 [B, 2, H, Tmax, hd] and ``ks`` float32 [B, 2, H, Tmax] per layer, off they
+        are bf16 qkv rows holding snapped K/V (``_kv8_storage``); with ``rows`` either kind is one
+        stacked buffer with a leading layer dimension (``kqs`` / ``kss``, or ``kv``)."""
         super().__init__(model)
         self.tmax, self.dev = tmax, idx.device
         B = idx.size(0) if rows is None else rows
         cfg = model.config
         D = cfg.n_embed
         self.B = B
-        self.kv = None
-        self.kv8 = bool(kv8)
+        self.kv = self.kqs = self.kss = None
+        self.kv8, self.stacked = bool(kv8), rows is not None
         self.caches, self.kq, self.ks = [], [], []
         if self.kv8:
-            assert rows is None
             self._kv8_storage()
         elif rows is None:
             self.caches = [torch.empty(B, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
@@ -430,22 +432,31 @@ class _GpuCache(_Body):
 
     def _kv8_storage(self):
         """A KV8 state's caches for the kernel ``_KV8_DECODE`` names now: the int8 pair, or bf16 qkv
-        rows.  Called before every prefill, so a flip of the switch swaps the buffers (the other
-        kind is freed) and the next prefill fills them; ``_stamp`` drops the loops captured on the
-        old ones."""
+        rows.  Called before every prefill and before a loop is looked up (``_fresh``: the beam and
+        speculative loops are built, with a warm-up step, before their prefill), so a flip of the switch
+        swaps the buffers (the other kind is freed) and the next prefill fills them; ``_stamp`` drops
+        the loops captured on the old ones.  A ``rows`` state keeps each kind as one stacked buffer
+        (``kqs`` [L, rows, 2, H, Tmax, hd] / ``kss`` [L, rows, 2, H, Tmax], or ``kv``) and the per-layer
+        lists are views of it, so the reorder stays one launch."""
         cfg = self.model.config
         B, D, H, L = self.B, cfg.n_embed, cfg.n_head, cfg.n_layer
+        new = lambda *shape, dtype: torch.empty(*shape, device=self.dev, dtype=dtype)
         if self._kv8_on():
-            self.caches = []
-            if not self.kq:
-                self.kq = [torch.empty(B, 2, H, self.tmax, D // H, device=self.dev, dtype=torch.int8)
-                           for _ in range(L)]
-                self.ks = [torch.empty(B, 2, H, self.tmax, device=self.dev, dtype=torch.float32) for _ in range(L)]
+            self.caches, self.kv = [], None
+            if not self.kq and self.stacked:
+                self.kqs = new(L, B, 2, H, self.tmax, D // H, dtype=torch.int8)
+                self.kss = new(L, B, 2, H, self.tmax, dtype=torch.float32)
+                self.kq, self.ks = list(self.kqs.unbind(0)), list(self.kss.unbind(0))
+            elif not self.kq:
+                self.kq = [new(B, 2, H, self.tmax, D // H, dtype=torch.int8) for _ in range(L)]
+                self.ks = [new(B, 2, H, self.tmax, dtype=torch.float32) for _ in range(L)]
         else:
-            self.kq, self.ks = [], []
-            if not self.caches:
-                self.caches = [torch.empty(B, self.tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
-                               for _ in range(L)]
+            self.kq, self.ks, self.kqs, self.kss = [], [], None, None
+            if not self.caches and self.stacked:
+                self.kv = new(L, B, self.tmax, 3 * D, dtype=torch.bfloat16)
+                self.caches = list(self.kv.unbind(0))
+            elif not self.caches:
+                self.caches = [new(B, self.tmax, 3 * D, dtype=torch.bfloat16) for _ in range(L)]
 
     def cache_nbytes(self):
         """Bytes of this state's KV cache tensors."""
@@ -458,8 +469,8 @@ class _GpuCache(_Body):
         B, T, D3 = qkv.shape
         if self.kv8:
             H = self.model.config.n_head
-            if self._kv8_on():
-                self.C.kv8_store(qkv, H, self.kq[i], self.ks[i])
+            if self._kv8_on():  # a beam state: one snap, the (q, s) stored to each of the prompt's beams
+                self.C.kv8_store(qkv, H, self.kq[i], self.ks[i], self.kq[i].size(0) // B)
                 return
             self.C.kv8_store(qkv, H)
         if self.caches[i].size(0) == B:
@@ -520,6 +531,8 @@ class _GpuCache(_Body):
         return _weight_stamp(self.model), self._w8_on(), self._kv8_on()
 
     def _fresh(self):
+        if self.kv8:
+            self._kv8_storage()
         st = self._stamp()
         if st != self.stamp:  # a weight moved or changed: captured pointers / bf16 copies are stale
             self.stamp = st
@@ -850,11 +863,15 @@ class _GpuCache(_Body):
         C.beam_rows(logits, V, W, st["score"], st["fin"], st["ctl"], st["cand_tok"], st["cand_c"], st["lse"])
         C.beam_merge(W, V, st["cand_tok"], st["cand_c"], st["score"], st["fin"], st["len"], st["tok"], st["parent"],
                      st["hparent"], st["htok"], st["hscore"], st["pos"], st["ctl"])
-        if _BEAM_REORDER_PER_LAYER:
-            for i in range(self.kv.size(0)):
-                C.beam_reorder(self.kv[i:i + 1], W, st["parent"], st["pos"], st["ctl"] if i == 0 else None)
+        if self._kv8_on():  # the int8 cache: (q, s) pairs move unchanged
+            reorder = lambda sl, ctl: C.beam_reorder_kv8(self.kqs[sl], self.kss[sl], W, st["parent"], st["pos"], ctl)
         else:
-            C.beam_reorder(self.kv, W, st["parent"], st["pos"], st["ctl"])
+            reorder = lambda sl, ctl: C.beam_reorder(self.kv[sl], W, st["parent"], st["pos"], ctl)
+        if _BEAM_REORDER_PER_LAYER:
+            for i in range(self.model.config.n_layer):
+                reorder(slice(i, i + 1), st["ctl"] if i == 0 else None)
+        else:
+            reorder(slice(None), st["ctl"])
 
     def beam(self, W):
         """The beam loop of this state (``_loops[("beam", W)]``): ``_decode`` at one batch-wide
@@ -933,12 +950,23 @@ class _GpuCache(_Body):
         if self._route(R) != "gemv":  # R <= 8 rows of at most 8192 columns (gemv.hip)
             raise RuntimeError(f"speculative decoding: {R} rows of width {4 * D} do not fit the skinny GEMM")
 
+        if self._kv8_on():
+            attend = lambda i, qkv: C.attention_decode_kv8(qkv, self.kq[i], self.ks[i], H, 0, st["pos_rows"],
+                                                           st["part"], st["cnt"], 1, K)
+        elif self.kv8:  # the KV8 model on the bf16 kernel: snap the step's rows in place, then attend
+
+            def attend(i, qkv):
+                C.kv8_store(qkv.view(R, 1, 3 * D), H)
+                return C.attention_decode(qkv, self.caches[i], H, 0, st["pos_rows"], st["part"], st["cnt"], 1, K)
+        else:
+            attend = lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, 0, st["pos_rows"], st["part"],
+                                                       st["cnt"], 1, K)
+
         def step():
             C.spec_draft(st["seq"], st["pos"], st["ctl"], K, st["tok"], st["pos_rows"], st["has"])
             x = C.embedding_fwd(st["tok"], bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, st["pos_rows"], None, None,
                                 1).view(R, D)
-            x = self._blocks(x, lambda i, qkv: C.attention_decode(qkv, self.caches[i], H, 0, st["pos_rows"],
-                                                                  st["part"], st["cnt"], 1, K), "gemv")
+            x = self._blocks(x, attend, "gemv")
             logits = self._head(x, "gemv")
             C.spec_argmax(logits, V, st["g"])
             C.spec_accept(st["g"], st["tok"], st["has"], K, st["pos"], st["ctl"], st["seq"], st["steps"], st["hist"])
@@ -1019,33 +1047,39 @@ def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
     return w
 
 
-_STATE_SLOTS = ("_mg_decode_cache", "_mg_kv8_cache", "_mg_beam_cache", "_mg_spec_cache")
+_STATE_SLOTS = ("_mg_decode_cache", "_mg_kv8_cache", "_mg_beam_cache", "_mg_beam_kv8_cache", "_mg_spec_cache",
+                "_mg_spec_kv8_cache")
+# the bf16 slot of each kind of state and the KV8 slot kept beside it
+_KV8_SLOTS = {"_mg_decode_cache": "_mg_kv8_cache", "_mg_beam_cache": "_mg_beam_kv8_cache",
+              "_mg_spec_cache": "_mg_spec_kv8_cache"}
 
 
-def _kv_slot(who, kv_cache):
-    """(slot, kv8) of a ``kv_cache`` argument: ``"bf16"`` is the plain state, ``"int8"`` the KV8 state
-    kept beside it, so alternating calls rebuild neither.  ValueError for anything else."""
+def _kv_slot(who, kv_cache, slot="_mg_decode_cache"):
+    """(slot, kv8) of a ``kv_cache`` argument: ``"bf16"`` is the state ``slot`` (the plain one, or the
+    beam / speculative state), ``"int8"`` the KV8 state kept beside it, so alternating calls rebuild
+    neither and a KV8 call never touches a bf16 state or its graphs.  ValueError for anything else."""
     if kv_cache not in _KV_CACHES:
         raise ValueError(f"{who}: kv_cache must be one of {_KV_CACHES}, got {kv_cache!r}")
-    return ("_mg_kv8_cache", True) if kv_cache == "int8" else ("_mg_decode_cache", False)
+    return (_KV8_SLOTS[slot], True) if kv_cache == "int8" else (slot, False)
 
 
 def kv_cache_nbytes(model):
     """{state slot: bytes of its KV cache tensors} for every decode state ``model`` keeps: ``_mg_decode_cache``
     (bf16 qkv rows, 6 D bytes per token and layer), ``_mg_kv8_cache`` (``kv_cache="int8"``: 2 D + 8 H bytes),
-    ``_mg_beam_cache``, ``_mg_spec_cache``."""
+    ``_mg_beam_cache``, ``_mg_spec_cache`` and their KV8 states ``_mg_beam_kv8_cache``, ``_mg_spec_kv8_cache``."""
     return {slot: model.__dict__[slot].cache_nbytes() for slot in _STATE_SLOTS if model.__dict__.get(slot) is not None}
 
 
 def _state_for(model, slot, idx, tmax, rows=None, last=None):
-    """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, or beside it ``_mg_kv8_cache``
-    (the KV8 state of ``kv_cache="int8"``) and ``_mg_beam_cache`` / ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain
-    loops and their graphs alone -- or a new one when the device, the rows or ``tmax`` differ.  The
+    """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, beside it ``_mg_beam_cache`` /
+    ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain loops
+    and their graphs alone, and the KV8 state of each (``_kv_slot``) -- or a new one when the device,
+    the rows or ``tmax`` differ.  The
     plain state comes back prefilled with ``idx`` (``last``: ``_GpuCache.prefill``); the others are
     prefilled by their callers, after the loop is built."""
     c = model.__dict__.get(slot)
     if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
-        c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows, kv8=slot == "_mg_kv8_cache")
+        c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows, kv8=slot in _KV8_SLOTS.values())
     elif rows is None:
         c.prefill(idx, last)
     return c
@@ -1413,7 +1447,7 @@ def _beam_backtrack(hparent, htok, pad_token, total):
 
 @torch.no_grad()
 def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,
-                  pad_token: int = 0, length_penalty: float = 0.0):
+                  pad_token: int = 0, length_penalty: float = 0.0, kv_cache: str = "bf16"):
     """Beam search over the model's log-probabilities (the rule in common.h, 'Beam search'): keep
     the ``num_beams`` continuations of every prompt with the largest summed log-probability, step
     by step.  Returns ``(tokens, lengths, scores)``, best beam first per prompt: ``tokens`` int64
@@ -1433,8 +1467,16 @@ def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Op
     kernel, the merge, the in-place reorder of every layer's KV cache by parent beam -- is one
     captured graph replayed back to back on B * W rows (``_GpuCache.beam``); the sequences are
     rebuilt at the end from the per-step parent / token histories.  On the CPU the same loop runs
-    ``ops.reference.beam_step`` on ``_CpuCache``."""
+    ``ops.reference.beam_step`` on ``_CpuCache``.
+
+    ``kv_cache``: ``"bf16"`` (default) or ``"int8"``, the KV8 model of ``generate`` (every K and V vector
+    snapped to int8 times a power-of-two scale before any attention reads it).  On the GPU its B * W
+    rows live in int8 caches -- (2 D + 8 H) / (6 D) of the bf16 beam state's bytes -- in a state of
+    its own (``_mg_beam_kv8_cache``): the prompt is snapped once and stored to its W beams
+    (``kv8_store(rep=W)``), the step attends with ``attention_decode_kv8`` and ends with
+    ``beam_reorder_kv8``.  ValueError for any other string."""
     who = "generate_beam"
+    slot, kv8 = _kv_slot(who, kv_cache, "_mg_beam_cache")
     n = _check_entry(who, model, max_new_tokens, idx)
     V, W = model.config.vocab_size, int(num_beams)
     B, T = idx.shape
@@ -1453,9 +1495,10 @@ def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Op
     if n == 0:
         return tokens, lengths, scores
     if device.type == "cuda":
-        hparent, htok, lengths, scores = _generate_beam_gpu(model, idx.contiguous(), n, W, eos_token, int(pad_token))
+        hparent, htok, lengths, scores = _generate_beam_gpu(model, idx.contiguous(), n, W, eos_token, int(pad_token),
+                                                             slot)
     else:
-        hparent, htok, lengths, scores = _generate_beam_cpu(model, idx, n, W, eos_token, int(pad_token))
+        hparent, htok, lengths, scores = _generate_beam_cpu(model, idx, n, W, eos_token, int(pad_token), kv8)
     tokens[:, :, T:] = _beam_backtrack(hparent, htok, pad_token, n).to(device)
     if a != 0.0:
         key = scores.double() / (lengths - T).clamp(min=1).double() ** a
@@ -1465,14 +1508,14 @@ def generate_beam(model, idx, max_new_tokens: int, num_beams: int, eos_token: Op
     return tokens, lengths, scores
 
 
-def _generate_beam_cpu(model, idx, n, W, eos_token, pad_token):
+def _generate_beam_cpu(model, idx, n, W, eos_token, pad_token, kv8=False):
     """The CPU half of ``generate_beam``, the executable definition of the semantics: one
     ``_CpuCache`` of B * W rows (the prompt prefilled once per prompt and broadcast), a step of
     ``ops.reference.beam_step`` per token, the caches' rows re-gathered by parent beam.  Returns the
-    histories (``_beam_backtrack``), the lengths and the scores."""
+    histories (``_beam_backtrack``), the lengths and the scores.  ``kv8``: the KV8 model."""
     B, T = idx.shape
     V = model.config.vocab_size
-    cache = _CpuCache(model, idx)
+    cache = _CpuCache(model, idx, kv8)
     cache.k = [k.repeat_interleave(W, dim=0) for k in cache.k]
     cache.v = [v.repeat_interleave(W, dim=0) for v in cache.v]
     logits = cache.logits.repeat_interleave(W, dim=0)
@@ -1497,15 +1540,15 @@ def _generate_beam_cpu(model, idx, n, W, eos_token, pad_token):
     return torch.stack(hparent, dim=2), torch.stack(htok, dim=2), lens, s.float()
 
 
-def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token):
+def _generate_beam_gpu(model, idx, n, W, eos_token, pad_token, slot="_mg_beam_cache"):
     """The GPU half of ``generate_beam``: build (once) the beam loop of the B * W-row state, prefill
     the B prompts, take the first beam step on the prefill's logits, then replay the captured step
     n - 1 times.  With a stop token the finished flags are read every ``_EXIT_EVERY`` replays and
     the loop ends once every beam has finished -- further steps would keep the order and append
     padding (``_beam_backtrack``), so stopping changes no result.  Returns the host histories of
-    the steps taken, the lengths [B, W] and the scores [B, W]."""
+    the steps taken, the lengths [B, W] and the scores [B, W].  ``slot``: the beam state's (``_kv_slot``)."""
     B, T = idx.shape
-    cache = _state_for(model, "_mg_beam_cache", idx, model.block_size, rows=B * W)
+    cache = _state_for(model, slot, idx, model.block_size, rows=B * W)
     loop = cache.beam(W)  # before the prefill: building it runs a warm-up step
     st = cache.beam_start(W, T, cache.beam_prefill(idx, W), eos_token, pad_token)
     steps = 1 + _replay(loop.run, n - 1, st["fin"], eos_token)
@@ -1520,7 +1563,7 @@ _SPEC_NGRAM_MAX = 4  # kernels.h kSpecNgramMax
 
 @torch.no_grad()
 def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ngram: int = 3,
-                         return_stats: bool = False):
+                         return_stats: bool = False, kv_cache: str = "bf16"):
     """Greedy decoding, several tokens per step (the rule in common.h, 'Speculative greedy
     decoding'): every step guesses the next ``draft_len`` tokens of a sequence by prompt lookup --
     the continuation of the most recent earlier occurrence of its last up to ``ngram`` tokens -- runs
@@ -1546,8 +1589,14 @@ def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ng
     row argmax, accept kernel -- is one captured graph per (B, K) replayed back to back
     (``_GpuCache.spec``); the host reads the positions back once per round of replays.  On the CPU
     the same rule runs through ``ops.reference.ngram_draft`` / ``spec_accept`` and one model forward
-    over the extended sequence per step."""
+    over the extended sequence per step.
+
+    ``kv_cache``: ``"bf16"`` (default) or ``"int8"``, the KV8 model of ``generate``: the result is then
+    ``generate(model, idx, max_new_tokens, kv_cache="int8")``'s.  On the GPU the verify rows attend with
+    the grouped ``attention_decode_kv8`` on int8 caches, in a state of its own
+    (``_mg_spec_kv8_cache``).  ValueError for any other string."""
     who = "generate_speculative"
+    slot, kv8 = _kv_slot(who, kv_cache, "_mg_spec_cache")
     n = _check_entry(who, model, max_new_tokens, idx)
     B = idx.size(0)
     if int(draft_len) != draft_len or not 1 <= int(draft_len) <= _SPEC_ROWS_MAX - 1:
@@ -1565,35 +1614,37 @@ def generate_speculative(model, idx, max_new_tokens: int, draft_len: int = 3, ng
         steps = torch.zeros(B, dtype=torch.long, device=idx.device)
         hist = torch.zeros(B, K + 1, dtype=torch.long, device=idx.device)
     elif idx.is_cuda:
-        out, steps, hist = _generate_speculative_gpu(model, idx.contiguous(), n, K, int(ngram))
+        out, steps, hist = _generate_speculative_gpu(model, idx.contiguous(), n, K, int(ngram), slot)
     else:
-        out, steps, hist = _generate_speculative_cpu(model, idx, n, K, int(ngram))
+        out, steps, hist = _generate_speculative_cpu(model, idx, n, K, int(ngram), kv8)
     return (out, {"steps": steps, "emitted_hist": hist}) if return_stats else out
 
 
-def _generate_speculative_cpu(model, idx, n, K, ngram):
+def _generate_speculative_cpu(model, idx, n, K, ngram, kv8=False):
     """The CPU half of ``generate_speculative``, the executable definition of the semantics: per
     sequence and step, ``ops.reference.ngram_draft``, one model forward over the committed tokens
     extended by the draft (only the min(K, end - p) rows that can still be emitted), the argmax of
-    the rows' logits and ``ops.reference.spec_accept``.  Eval mode, as for ``score``."""
+    the rows' logits and ``ops.reference.spec_accept``.  Eval mode, as for ``score``.  ``kv8``: the
+    forward is the KV8 model's (``_CpuCache`` with every position's logits)."""
     B, T = idx.shape
     out = torch.zeros(B, T + n, dtype=torch.long, device=idx.device)
     out[:, :T] = idx
     steps = torch.zeros(B, dtype=torch.long, device=idx.device)
     hist = torch.zeros(B, K + 1, dtype=torch.long, device=idx.device)
     end = T + n - 1
+    forward = (lambda x: (_CpuCache(model, x, True, every=True).logits, None)) if kv8 else model
     was = model.training
     model.eval()
     try:
         for b in range(B):
-            logits, _ = model(idx[b:b + 1])
+            logits, _ = forward(idx[b:b + 1])
             out[b, T] = logits[0, -1].argmax()
             p = T
             while p < end:
                 rows, has = R.ngram_draft(out[b], p, K, ngram)
                 rows = rows[:min(K, end - p)]
                 x = torch.cat([out[b, :p], torch.tensor(rows, dtype=torch.long, device=idx.device)])
-                logits, _ = model(x.view(1, -1))
+                logits, _ = forward(x.view(1, -1))
                 g = logits[0, p:].argmax(dim=-1)
                 _, cnt = R.spec_accept(rows, g.tolist(), has, p, end)
                 out[b, p + 1:p + 1 + cnt] = g[:cnt]
@@ -1605,13 +1656,14 @@ def _generate_speculative_cpu(model, idx, n, K, ngram):
     return out, steps, hist
 
 
-def _generate_speculative_gpu(model, idx, n, K, ngram):
+def _generate_speculative_gpu(model, idx, n, K, ngram, slot="_mg_spec_cache"):
     """The GPU half of ``generate_speculative``: build (once per (B, K)) the speculative loop, prefill
     the prompts and take the first token from the prefill logits as ``generate`` does, then replay
     the captured step in rounds of ceil((end - min p) / K) -- the fewest steps that could finish --
-    reading the positions back after each round, until every sequence has reached ``end``."""
+    reading the positions back after each round, until every sequence has reached ``end``.  ``slot``:
+    the speculative state's (``_kv_slot``)."""
     B, T = idx.shape
-    cache = _state_for(model, "_mg_spec_cache", idx, model.block_size, rows=B)
+    cache = _state_for(model, slot, idx, model.block_size, rows=B)
     loop = cache.spec(K)  # before the prefill: building it runs a warm-up step
     cache.prefill(idx)
     st = cache.spec_start(K, idx, cache.logits.argmax(-1), n, ngram)
@@ -1627,7 +1679,7 @@ _SCORE_LOGITS_BYTES = 256 << 20  # cap on the transient bf16 logits of one LM-he
 
 
 @torch.no_grad()
-def score(model, idx, lengths=None):
+def score(model, idx, lengths=None, kv_cache: str = "bf16"):
     """Log-probabilities of given sequences: float32 [B, T], ``out[b, j]`` = the model's
     log-probability of ``idx[b, j]`` given ``idx[b, :j]`` (the rule in common.h: log-softmax at
     temperature 1) for 1 <= j < lengths[b], and 0.0 elsewhere, column 0 included.  A row's sum is
@@ -1642,7 +1694,13 @@ def score(model, idx, lengths=None):
     chunks whose transient bf16 logits stay under ``_SCORE_LOGITS_BYTES`` (256 MiB; at least one
     row), each through the lse kernel with the next tokens as targets (``logits_lse``) -- the
     [B, T, V] logits never exist at once and nothing is read back in fp32.  CPU: the model's
-    forward and ``ops.reference.token_logprob``."""
+    forward and ``ops.reference.token_logprob``.
+
+    ``kv_cache``: ``"bf16"`` (default) or ``"int8"``: the log-probabilities the KV8 model of
+    ``generate(kv_cache="int8")`` assigns -- every K and V vector snapped before any attention reads
+    it (GPU: ``kv8_store`` in place on every layer's qkv rows of the prefill body, no cache kept; CPU:
+    ``_CpuCache`` with every position's logits).  ValueError for any other string."""
+    _, kv8 = _kv_slot("score", kv_cache)
     if isinstance(idx, tuple) and lengths is None:
         prompts = idx
     elif torch.is_tensor(idx) and idx.dim() == 2:
@@ -1672,14 +1730,16 @@ def score(model, idx, lengths=None):
         was = model.training
         model.eval()
         try:
-            logits, _ = model(tokens)
+            logits = _CpuCache(model, tokens, True, every=True).logits if kv8 else model(tokens)[0]
         finally:
             model.train(was)
         lp = R.token_logprob(logits[:, :-1], tokens[:, 1:])
         out[:, 1:] = torch.where(valid, lp, torch.zeros_like(lp))
         return out
     c = _Body(model)
-    x = c._prompt(tokens).view(B * T, model.config.n_embed)
+    H = model.config.n_head
+    keep = (lambda i, qkv: c.C.kv8_store(qkv, H)) if kv8 else None  # the KV8 model: snapped in place, no cache
+    x = c._prompt(tokens, keep).view(B * T, model.config.n_embed)
     targets = torch.full((B, T), -1, dtype=torch.long, device=device)  # row (b, t) predicts column t + 1
     targets[:, :-1] = torch.where(valid, tokens[:, 1:], targets[:, 1:])
     targets = targets.view(B * T)

@@ -33,7 +33,7 @@ relative rounding error.
 
 ``--kv-int8`` keeps the KV cache as int8 with one power-of-two scale per (position, layer, head) K and V
 vector (``kv_cache="int8"``, the KV8 model: every attention reads the snapped K / V) and prints the cache
-bytes; it goes with sampling, ``--greedy`` and several prompts, not with ``--beams`` or ``--speculative``.
+bytes; it goes with sampling, ``--greedy``, ``--logprobs``, several prompts, ``--beams`` and ``--speculative``.
 
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
@@ -90,7 +90,7 @@ def main(argv=None):
                          "scales (GPT.quantize_int8_) before generating")
     ap.add_argument("--kv-int8", action="store_true",
                     help="int8 KV cache: K and V vectors snapped to int8 with one power-of-two scale each "
-                         "(kv_cache='int8'); not with --beams or --speculative")
+                         "(kv_cache='int8'), on every decoding mode")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -124,8 +124,6 @@ def main(argv=None):
         ap.error("the logits processors do not go with --beams or --speculative")
     if a.speculative and (len(texts) > 1 or a.beams):
         ap.error("--speculative takes one prompt and does not go with --beams")
-    if a.kv_int8 and (a.beams or a.speculative):
-        ap.error("--kv-int8 does not go with --beams or --speculative (they keep bf16 caches)")
     if len(texts) > 1:
         return generate_many(model, tok, texts, a, dev)
     prompt = texts[0] if texts else ""
@@ -188,7 +186,12 @@ def generate_beams(model, tok, x, a):
     best first with their summed log-probability; a beam stops at ``<|endoftext|>`` when the
     tokenizer has one."""
     eos = tok.encoder.encoder.get("<|endoftext|>") if tok is not None else None
-    y, n, scores = model.generate_beam(x, a.steps, a.beams, eos_token=eos, length_penalty=a.length_penalty)
+    from mingpt_distributed_amd.models import generation
+
+    # the module-level entry point: it takes kv_cache, GPT.generate_beam does not
+    y, n, scores = generation.generate_beam(model, x, a.steps, a.beams, eos_token=eos, length_penalty=a.length_penalty,
+                                            **kv_args(a))
+    print_kv_bytes(model, a)
     outs = []
     for w in range(a.beams):
         ids = y[0, w, :int(n[0, w])].cpu()
@@ -203,7 +206,12 @@ def generate_beams(model, tok, x, a):
 def generate_speculative(model, tok, x, a):
     """``--speculative``: greedy decoding of the one prompt x [1, T] with n-gram drafts
     (``GPT.generate_speculative``), then the verify steps taken and the mean tokens per step."""
-    y, stats = model.generate_speculative(x, a.steps, draft_len=a.speculative, ngram=a.ngram, return_stats=True)
+    from mingpt_distributed_amd.models import generation
+
+    # the module-level entry point: it takes kv_cache, GPT.generate_speculative does not
+    y, stats = generation.generate_speculative(model, x, a.steps, draft_len=a.speculative, ngram=a.ngram,
+                                               return_stats=True, **kv_args(a))
+    print_kv_bytes(model, a)
     out = tok.decode(y[0].cpu()) if tok is not None else y[0].tolist()
     print("-" * 80)
     print(out)
