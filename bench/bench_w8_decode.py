@@ -2,14 +2,17 @@
 """W8 decode against the bf16 decode of the same snapped model, interleaved in one process.
 
 Two models of a GPT-2 preset (--model-type) with the same random weights, both snapped by
-``quantize_int8_``; one keeps the mark and decodes on ``gemv_w8``, the other has it taken off and
-decodes on the bf16 ``gemv`` (the parent's kernels on the same numbers).  Each keeps its own decode
-state and captured graphs, so the timed calls alternate without a re-capture.  Per batch size of
---batches: greedy ``generate`` of --new tokens after --prompt, --reps alternating runs, median and
-range; the tokens are asserted equal.  --ragged B: one ``generate_batch`` case on B prompts spread over
---min-len .. --max-len.  --kernels: the four projection shapes of a block and the LM head alone, both
-kernels, each captured as a graph over rotating copies of the weight (so no copy is re-read from a
-cache: --rotate-mb of weights per graph), microseconds per launch and GB/s of weight bytes.
+``quantize_int8_``; one keeps the mark and decodes on ``gemv_w8`` (up to 8 rows) / ``gemm_rows_w8``
+(9..64 rows), the other has it taken off and decodes on the bf16 ``gemv`` / ``gemm_rows`` (the same
+numbers on the bf16 kernels).  Each keeps its own decode state and captured graphs, so the timed calls
+alternate without a re-capture.  Per batch size of --batches (default 1, 8, 9, 16, 32, 64): greedy
+``generate`` of --new tokens after --prompt, --reps alternating runs, median and range; the tokens are
+asserted equal.  --ragged B: one ``generate_batch`` case on B prompts spread over --min-len .. --max-len.
+--beam P,W: one ``generate_beam`` case of P prompts x W beams.  --kernels: the four projection shapes of
+a block and the LM head alone, both kernels -- the skinny GEMM up to 8 rows, the rows GEMM (without the
+LayerNorm: a launch of its own on that route) from 9 -- each captured as a graph over rotating copies of
+the weight (so no copy is re-read from a cache: --rotate-mb of weights per graph), microseconds per
+launch and GB/s of weight bytes.
 --logits: largest and RMS difference of the last-position logits before and after the snap, and the
 per-weight report.  One JSON line per result."""
 import argparse
@@ -65,8 +68,12 @@ def kernels(a, cfg):
             resid = torch.randn(B, N, generator=g).to(torch.bfloat16).cuda() if epi == 3 else None
             lw = torch.ones(K, dtype=torch.bfloat16, device="cuda") if ln else None
             lb = torch.zeros(K, dtype=torch.bfloat16, device="cuda") if ln else None
-            runs = {"bf16": lambda: [C.gemv(x, w, epi, bias, resid, ld, lw, lb, 1e-5) for w in ws],
-                    "w8": lambda: [C.gemv_w8(x, qq, s, epi, bias, resid, ld, lw, lb, 1e-5) for qq in qs]}
+            if B <= 8:
+                runs = {"bf16": lambda: [C.gemv(x, w, epi, bias, resid, ld, lw, lb, 1e-5) for w in ws],
+                        "w8": lambda: [C.gemv_w8(x, qq, s, epi, bias, resid, ld, lw, lb, 1e-5) for qq in qs]}
+            else:
+                runs = {"bf16": lambda: [C.gemm_rows(x, w, epi, bias, resid, ld) for w in ws],
+                        "w8": lambda: [C.gemm_rows_w8(x, qq, s, epi, bias, resid, ld) for qq in qs]}
             assert all(torch.equal(u[:, :N], v[:, :N]) for u, v in zip(runs["bf16"](), runs["w8"]()))
             graphs = {}
             for k, fn in runs.items():
@@ -85,7 +92,8 @@ def kernels(a, cfg):
                     torch.cuda.synchronize()
                     us[k].append(e0.elapsed_time(e1) * 1e3 / (10 * copies))
             med = {k: statistics.median(v) for k, v in us.items()}
-            print(json.dumps({"metric": "skinny GEMM us per launch, weights from HBM", "model": a.model_type, "B": B,
+            print(json.dumps({"metric": ("skinny" if B <= 8 else "rows") + " GEMM us per launch, weights from HBM",
+                              "model": a.model_type, "B": B,
                               "weight": name, "N": N, "K": K, "epi": epi, "layernorm": ln, "copies": copies,
                               "bf16_us": round(med["bf16"], 2), "w8_us": round(med["w8"], 2),
                               "bf16_GBps": round(2 * N * K / med["bf16"] / 1e3, 1),
@@ -99,18 +107,20 @@ def main():
     ap.add_argument("--model-type", default="gpt2", choices=["gpt2", "gpt2-medium", "gpt2-large", "gpt2-xl"])
     ap.add_argument("--prompt", type=int, default=32)
     ap.add_argument("--new", type=int, default=256)
-    ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--batches", default="1,8,9,16,32,64")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ragged", type=int, default=0, help="also time generate_batch on this many mixed-length prompts")
     ap.add_argument("--min-len", type=int, default=16)
     ap.add_argument("--max-len", type=int, default=256)
+    ap.add_argument("--beam", default="", help="also time generate_beam on P,W: P prompts x W beams (4,4: 16 rows)")
     ap.add_argument("--kernels", action="store_true", help="time the projection and LM-head kernels alone instead")
     ap.add_argument("--rotate-mb", type=int, default=600)
     ap.add_argument("--logits", action="store_true", help="report the logits change of the snap and the per-weight report")
     a = ap.parse_args()
-    from mingpt_distributed_amd.models import GPT, GPTConfig
+    from mingpt_distributed_amd.models import GPT, GPTConfig, generation
 
-    cfg = GPTConfig(model_type=a.model_type, vocab_size=50257, block_size=1024).resolve()
+    generation._W8_ROWS = True  # the A/B at 9..64 rows: the marked model on gemm_rows_w8 (off by default)
+    cfg =GPTConfig(model_type=a.model_type, vocab_size=50257, block_size=1024).resolve()
     if a.kernels:
         return kernels(a, cfg)
     torch.manual_seed(0)
@@ -158,6 +168,20 @@ def main():
         for k, ts in times.items():
             res[k + "_tok_s"] = round(B * a.new / statistics.median(ts), 1)
             res[k + "_tok_s_range"] = [round(B * a.new / max(ts), 1), round(B * a.new / min(ts), 1)]
+        res["w8_over_bf16"] = round(statistics.median(times["bf16"]) / statistics.median(times["w8"]), 3)
+        print(json.dumps(res), flush=True)
+    if a.beam:
+        P, W = map(int, a.beam.split(","))
+        idx = torch.randint(0, 50257, (P, a.prompt), generator=torch.Generator().manual_seed(P * W)).cuda()
+        outs, times = ab({"bf16": lambda: bf.generate_beam(idx, a.new, W)[0],
+                          "w8": lambda: w8.generate_beam(idx, a.new, W)[0]}, a.reps)
+        assert torch.equal(outs["bf16"], outs["w8"])
+        res = {"metric": "generate_beam tokens/s (one best beam per prompt), bf16 vs W8",
+               "model": f"{a.model_type} (random init)", "prompts": P, "beams": W, "rows": P * W, "prompt": a.prompt,
+               "new_tokens": a.new, "reps": a.reps, "tokens_equal": True}
+        for k, ts in times.items():
+            res[k + "_tok_s"] = round(P * a.new / statistics.median(ts), 1)
+            res[k + "_tok_s_range"] = [round(P * a.new / max(ts), 1), round(P * a.new / min(ts), 1)]
         res["w8_over_bf16"] = round(statistics.median(times["bf16"]) / statistics.median(times["w8"]), 3)
         print(json.dumps(res), flush=True)
 

@@ -33,8 +33,11 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-un
                 "-I" + os.path.join(ROOT, "csrc", "include"), "-ffp-contract=fast"]
 # per-source extras.  attention_train.hip: no SLP vectoriser -- it packs the softmax-gradient
 # multiplies into v_pk_mul/fma_f32 pairs with s_nop between them, an anti-lever beside MFMAs
-# (MI355X_MICROARCH 'price of one filler'), and the hd = 64 backward's register budget is tight
-FILE_FLAGS = {"attention_train.hip": ["-fno-slp-vectorize"]}
+# (MI355X_MICROARCH 'price of one filler'), and the hd = 64 backward's register budget is tight.
+# gemm_rows.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the int8 conversion or the
+# partial sums; the bf16 instantiations hold none either way (PERF.md 'W8 rows')
+FILE_FLAGS = {"attention_train.hip": ["-fno-slp-vectorize"],
+              "gemm_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 

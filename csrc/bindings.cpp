@@ -629,6 +629,21 @@ at::Tensor gemm_rows(const at::Tensor& x, const at::Tensor& W, int64_t epi, cons
   return y;
 }
 
+// the same on int8 weight rows Wq [N, K] with one power-of-two fp32 scale per row (the W8 rule, common.h)
+at::Tensor gemm_rows_w8(const at::Tensor& x, const at::Tensor& Wq, const at::Tensor& scale, int64_t epi,
+                        const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& resid, int64_t ldy) {
+  const ProjArgs p = proj_args("gemm_rows_w8", x, Wq, epi, bias, resid, ldy, true);
+  CHECK_F32(scale); CHECK_CONTIG(scale);
+  TORCH_CHECK(scale.dim() == 1 && scale.numel() == p.N, "gemm_rows_w8: scale fp32 [N]");
+  TORCH_CHECK(p.M <= 64 && mg::gemm_rows_w8_supported((int)p.M, (int)p.K),
+              "gemm_rows_w8: 1 <= M <= 64, K % 8 == 0, K <= 8192");
+  DevGuard g(x.device());
+  auto y = at::empty({p.M, p.ldy}, x.options());
+  mg::gemm_rows_w8(bp(x), Wq.data_ptr<int8_t>(), fp(scale), bp(y), (int)p.M, (int)p.N, (int)p.K, p.ldy, p.bias,
+                   p.resid, (int)epi, cur_stream());
+  return y;
+}
+
 // pos_dev (int32 [1] on the device, optional): the position is read by the kernel (hipGraph decode);
 // with pos_stride 1 it is int32 [B], one position per row (ragged batches)
 // part / counters (optional): the decode state's own workspace (kernels.h); without them a
@@ -1332,6 +1347,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_rows", &gemm_rows, py::arg("x"), py::arg("W"), py::arg("epi"), py::arg("bias") = py::none(),
         py::arg("resid") = py::none(), py::arg("ldy") = 0);
   m.def("gemm_rows_supported", &mg::gemm_rows_supported);
+  m.def("gemm_rows_w8", &gemm_rows_w8, py::arg("x"), py::arg("Wq"), py::arg("scale"), py::arg("epi"),
+        py::arg("bias") = py::none(), py::arg("resid") = py::none(), py::arg("ldy") = 0);
+  m.def("gemm_rows_w8_supported", &mg::gemm_rows_w8_supported);
   m.def("attention_decode", &attention_decode, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
         py::arg("pos"), py::arg("pos_dev") = py::none(), py::arg("part") = py::none(),
         py::arg("counters") = py::none(), py::arg("pos_stride") = 0, py::arg("group") = 1);

@@ -60,6 +60,13 @@ MG_DEVICE uint4 ld16_nt(const void* p) {
   const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
+// the 8-byte loads of int8 weight rows (W8: 8 columns per lane), default and non-temporal policy
+MG_DEVICE uint2 ld8(const void* p) { return *reinterpret_cast<const uint2*>(p); }
+MG_DEVICE uint2 ld8_nt(const void* p) {
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  const v2u v = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
+  return make_uint2(v[0], v[1]);
+}
 
 // hipGraph mode: a captured kernel's seed argument is an offset into a per-replay stream whose
 // counter lives in device memory (incremented inside the graph), so every replay draws new
@@ -435,6 +442,13 @@ MG_DEVICE bf16_t proj_epilogue(float acc, float bias, int epi, const bf16_t* res
 // bit: gemv_w8(x, q, s) == gemv(x, s q).  Precondition: no fp32 intermediate of either chain (a lane
 // sum, a fold sum, s_n * sum) is subnormal or overflows -- there the two roundings differ.
 // (s_n * sum + bias may contract to one fma: the product is exact, so the result is the same.)
+// One output of gemm_rows_w8 (gemm_rows.hip) is  y[m, n] = proj_epilogue(s_n * sum[m, n])  likewise: sum is
+// the bf16 kernel's -- the same MFMAs in the same wave, step and operand slot, then ((p0 + p1) + p2) + p3
+// -- with bf16(q[n, k]) (exact: 8 significant bits) in place of the bf16 weight.  Every product and every
+// accumulator of output column n carries the one factor s_n, and a power of two commutes with every
+// rounding and with the alignment of the terms inside the MFMA (it moves all their exponents alike), so
+// gemm_rows_w8(x, q, s) == gemm_rows(x, s q) bit for bit, under the same precondition: no intermediate
+// of either run (a product, an accumulator, a partial sum, s_n * sum) is subnormal or overflows.
 
 // ---------------------------------------------------------------- KV8: int8 K / V vectors, power-of-two scales
 // The int8 KV cache (kv_cache="int8" on every entry point that keeps or reads K / V; attention_kv8.hip;

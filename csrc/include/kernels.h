@@ -108,6 +108,13 @@ void gemv_w8(const bf16_t* x, const int8_t* Wq, const float* scale, bf16_t* y, i
 bool gemm_rows_supported(int M, int K);
 void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K, long ldy, const bf16_t* bias,
                const bf16_t* resid, int epi, hipStream_t stream);
+// The same kernel body over int8 weight rows (the W8 rule in common.h): Wq int8 [N, K], 8-byte
+// aligned, scale fp32 [N] (powers of two).  A lane's 8 int8 are converted exactly to the 8 bf16 of the
+// MFMA operand, and y = epilogue(scale[n] * sum): bit for bit gemm_rows's output on the bf16 matrix
+// scale[n] * Wq[n, k].  Same limits, epilogues and contract as gemm_rows.
+bool gemm_rows_w8_supported(int M, int K);
+void gemm_rows_w8(const bf16_t* x, const int8_t* Wq, const float* scale, bf16_t* y, int M, int N, int K, long ldy,
+                  const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream);
 
 // sample.hip -- one sampled token per row of bf16 logits [B, ld] (columns >= V never read; ld % 8
 // == 0, rows 16-byte aligned): exact top-k + Gumbel-max, the rule in common.h.  params (device,

@@ -23,6 +23,15 @@
 // that row's operand alone, so the bits of y[m, :] depend on x[m, :], W, bias, resid[m, :], epi, N
 // and K -- not on M, the row's slot, the other rows' contents (NaN included), or graph / eager
 // launch.  No atomics, no cross-workgroup hand-off; columns N .. ldy-1 of y are left untouched.
+//
+// gemm_rows_w8 is the same body over int8 weight rows with one power-of-two fp32 scale per row (the W8
+// rule in common.h): the weight element type WT is a template argument of the one kernel, as in gemv.hip.
+// Lane l then loads the 8 bytes q[n0 + (l & 15)][k0 + 8 (l >> 4) .. + 7], converts them exactly to 8
+// bf16 in registers (every integer of -128..127 fits bf16's 8 significant bits) once per k-step, shared by
+// the RT MFMAs of the step, and feeds them in W's operand slot, step and wave.  The wave-order sum is
+// multiplied by the column's scale before proj_epilogue: one multiply per output, none in the loop, and
+// the bits are the bf16 kernel's on the matrix s q (common.h).  A weight fragment is 2 registers per
+// step instead of 4, so the int8 load groups are deeper (kRowsU8).
 #include <cstdio>
 #include <cstdlib>
 
@@ -51,24 +60,68 @@ MG_DEVICE f32x4 rows_mfma(const uint4& a, const uint4& b, f32x4 c) {
                                                  c, 0, 0, 0);
 }
 
+// int8 rows: the deepest group that keeps the bf16 instantiation's waves per SIMD at that RT -- 6 steps
+// at 1 row tile (MG_ROWS_W8_U1, a build switch like the one above), 4 beyond (PERF.md 'W8 rows'); the k
+// order, and so the bits, do not depend on it
+#ifndef MG_ROWS_W8_U1
+#define MG_ROWS_W8_U1 6
+#endif
 template <int RT>
-struct RowsFrag {
-  uint4 w[kRowsU<RT>];
-  uint4 x[kRowsU<RT>][RT];
+constexpr int kRowsU8 = RT == 1 ? MG_ROWS_W8_U1 : 4;
+
+// A lane's 8-column fragment of a weight row as loaded (16 bytes of bf16 or 8 bytes of int8, default or
+// non-temporal policy) and as the MFMA's B operand.
+template <class WT>
+struct RowsW;
+template <>
+struct RowsW<bf16_t> {
+  typedef uint4 type;
+  template <int RT>
+  static constexpr int U = kRowsU<RT>;
+  static MG_DEVICE uint4 zero() { return make_uint4(0, 0, 0, 0); }
+  template <bool NT>
+  static MG_DEVICE uint4 ld(const bf16_t* p) { return NT ? ld16_nt(p) : ld16(p); }
+  static MG_DEVICE const uint4& operand(const uint4& w) { return w; }
+};
+template <>
+struct RowsW<int8_t> {
+  typedef uint2 type;
+  template <int RT>
+  static constexpr int U = kRowsU8<RT>;
+  static MG_DEVICE uint2 zero() { return make_uint2(0, 0); }
+  template <bool NT>
+  static MG_DEVICE uint2 ld(const int8_t* p) { return NT ? ld8_nt(p) : ld8(p); }
+  // 2 x int8 (bytes 0, 1 of u) -> 2 x bf16, exact: sign-extending byte converts and one packed round
+  static MG_DEVICE uint32_t cvt2(uint32_t u) { return pack2((float)(int8_t)u, (float)(int8_t)(u >> 8)); }
+  // 8 x int8 -> 8 x bf16, column order = byte order
+  static MG_DEVICE uint4 operand(const uint2& w) {
+    return make_uint4(cvt2(w.x), cvt2(w.x >> 16), cvt2(w.y), cvt2(w.y >> 16));
+  }
 };
 
-template <int RT, bool NTW>
+template <int RT, class WT>
+struct RowsFrag {
+  typename RowsW<WT>::type w[RowsW<WT>::template U<RT>];
+  uint4 x[RowsW<WT>::template U<RT>][RT];
+};
+
+// WT: the weight element type, bf16_t (gemm_rows; scale not read) or int8_t (gemm_rows_w8: scale is one
+// fp32 per output column).
+template <int RT, bool NTW, class WT = bf16_t>
 __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict__ x,
-                                                        const bf16_t* __restrict__ W,
+                                                        const WT* __restrict__ W,
                                                         bf16_t* __restrict__ y, int M, int N, int K, long ldy,
                                                         const bf16_t* __restrict__ bias,
-                                                        const bf16_t* __restrict__ resid, int epi) {
+                                                        const bf16_t* __restrict__ resid, int epi,
+                                                        const float* __restrict__ scale) {
+  typedef RowsW<WT> WF;
+  constexpr bool W8 = std::is_same<WT, int8_t>::value;
   __shared__ f32x4 part[4][RT][64];  // [wave][row tile][lane]: 4 KiB per row tile
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  constexpr int U = kRowsU<RT>;
+  constexpr int U = WF::template U<RT>;
   const int r = lane & 15, q = lane >> 4;
   const int n0 = blockIdx.x * 16;
-  const bf16_t* wr = W + (long)min(n0 + r, N - 1) * K;  // columns past N: a valid row, never stored
+  const WT* wr = W + (long)min(n0 + r, N - 1) * K;  // columns past N: a valid row, never stored
   const bf16_t* xr[RT];
   bool xok[RT];
 #pragma unroll
@@ -80,12 +133,12 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
   const int nstep = (K + 31) >> 5;                                   // 32-column k-steps of the row
   const int mine = wid < nstep ? (nstep - 1 - wid) / 4 + 1 : 0;      // steps w, w + 4, ...
   const int ngrp = (mine + U - 1) / U;
-  auto load_group = [&](int g, RowsFrag<RT>& f) {
+  auto load_group = [&](int g, RowsFrag<RT, WT>& f) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int c = ((g * U + u) * 4 + wid) * 32 + q * 8;  // steps past the wave's last: c >= K
       const bool ok = c < K;
-      f.w[u] = ok ? (NTW ? ld16_nt(wr + c) : ld16(wr + c)) : make_uint4(0, 0, 0, 0);
+      f.w[u] = ok ? WF::template ld<NTW>(wr + c) : WF::zero();
 #pragma unroll
       for (int t = 0; t < RT; ++t) f.x[u][t] = ok && xok[t] ? ld16(xr[t] + c) : make_uint4(0, 0, 0, 0);
     }
@@ -93,15 +146,16 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
   f32x4 acc[RT];
 #pragma unroll
   for (int t = 0; t < RT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  RowsFrag<RT> cur, nxt;
+  RowsFrag<RT, WT> cur, nxt;
   if (ngrp > 0) load_group(0, cur);
   for (int g = 0; g < ngrp; ++g) {
     if (g + 1 < ngrp) load_group(g + 1, nxt);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       // a step past K multiplies zero fragments: +0 into the accumulator, the bits unchanged
+      const auto& b = WF::operand(cur.w[u]);  // int8: converted once, shared by the step's RT MFMAs
 #pragma unroll
-      for (int t = 0; t < RT; ++t) acc[t] = rows_mfma(cur.x[u][t], cur.w[u], acc[t]);
+      for (int t = 0; t < RT; ++t) acc[t] = rows_mfma(cur.x[u][t], b, acc[t]);
     }
     if (g + 1 < ngrp) cur = nxt;
   }
@@ -114,10 +168,13 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
     const int n = n0 + r;
     if (n < N) {
       const float bv = bias ? bf2f(bias[n]) : 0.f;
+      float sc = 1.f;
+      if constexpr (W8) sc = scale[n];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = wid * 16 + q * 4 + i;
-        if (m < M) y[(long)m * ldy + n] = proj_epilogue(s[i], bv, epi, resid + (long)m * ldy + n);
+        const float v = W8 ? s[i] * sc : s[i];  // a power of two: exact
+        if (m < M) y[(long)m * ldy + n] = proj_epilogue(v, bv, epi, resid + (long)m * ldy + n);
       }
     }
   }
@@ -131,15 +188,18 @@ bool gemm_rows_supported(int M, int K) {
   return M >= 1 && M <= kRowsMaxM && K >= 8 && K % 8 == 0 && K <= kRowsMaxK;
 }
 
-void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K, long ldy, const bf16_t* bias,
-               const bf16_t* resid, int epi, hipStream_t stream) {
+namespace {
+// the launch of gemm_rows (WT bf16_t, scale null) and gemm_rows_w8 (WT int8_t)
+template <class WT>
+void rows_launch(const bf16_t* x, const WT* W, const float* scale, bf16_t* y, int M, int N, int K, long ldy,
+                 const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream) {
   const int grid = cdiv(N, 16);
   const bool ntw = gemv_nt_weights();
   // the one launch: the row tiles and the weight-load policy pick the instantiation
   auto launch = [&](auto rt) {
     dispatch_bool(ntw, [&](auto nt) {
-      gemm_rows_kernel<decltype(rt)::value, decltype(nt)::value><<<grid, 256, 0, stream>>>(x, W, y, M, N, K, ldy,
-                                                                                           bias, resid, epi);
+      gemm_rows_kernel<decltype(rt)::value, decltype(nt)::value, WT><<<grid, 256, 0, stream>>>(
+          x, W, y, M, N, K, ldy, bias, resid, epi, scale);
     });
   };
   switch (cdiv(M, 16)) {  // row tiles: rows past M are zero operands, never stored
@@ -154,6 +214,19 @@ void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K,
 #endif
       break;
   }
+}
+}  // namespace
+
+void gemm_rows(const bf16_t* x, const bf16_t* W, bf16_t* y, int M, int N, int K, long ldy, const bf16_t* bias,
+               const bf16_t* resid, int epi, hipStream_t stream) {
+  rows_launch<bf16_t>(x, W, nullptr, y, M, N, K, ldy, bias, resid, epi, stream);
+}
+
+bool gemm_rows_w8_supported(int M, int K) { return gemm_rows_supported(M, K); }
+
+void gemm_rows_w8(const bf16_t* x, const int8_t* Wq, const float* scale, bf16_t* y, int M, int N, int K, long ldy,
+                  const bf16_t* bias, const bf16_t* resid, int epi, hipStream_t stream) {
+  rows_launch<int8_t>(x, Wq, scale, y, M, N, K, ldy, bias, resid, epi, stream);
 }
 
 }  // namespace mg

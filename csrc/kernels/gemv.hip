@@ -82,11 +82,7 @@ struct WChunk<int8_t> {
   typedef uint2 type;
   static MG_DEVICE uint2 zero() { return make_uint2(0, 0); }
   template <bool NT>
-  static MG_DEVICE uint2 ld(const int8_t* p) {
-    typedef unsigned v2u __attribute__((ext_vector_type(2)));
-    const v2u v = NT ? __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p)) : *reinterpret_cast<const v2u*>(p);
-    return make_uint2(v[0], v[1]);
-  }
+  static MG_DEVICE uint2 ld(const int8_t* p) { return NT ? ld8_nt(p) : ld8(p); }
   // 8 x int8 -> 8 x f32 (exact), column order = byte order
   static MG_DEVICE void unpack(const uint2& u, float (&f)[8]) {
 #pragma unroll

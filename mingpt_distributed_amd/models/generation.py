@@ -141,7 +141,8 @@ def _w8_named_weights(model):
 
 
 def w8_weights(model):
-    """int8 twins of the weights the skinny GEMM reads (the W8 rule in common.h), cached on the model.
+    """int8 twins of the weights the decode projections read -- the skinny GEMM up to 8 rows, with
+    ``_W8_ROWS`` the rows GEMM at 9..64 (the W8 rule in common.h) -- cached on the model.
 
     ``get(w)`` returns ``(q int8 [N, K], s float32 [N])`` or None.  A twin is built on first use and
     kept under the weight's (storage pointer, in-place version) stamp.  When the stamp changes the
@@ -190,7 +191,10 @@ def quantize_int8_(model):
     row.  ``lm_head.weight`` is the tied ``wte``, so the token embedding is snapped with it.  Biases,
     LayerNorms and ``wpe`` are untouched.  Every path (CPU, ``use_cache=False``, prefill, the rows and
     MFMA GEMMs) then computes the snapped model; GPU decode steps of up to 8 rows read the int8 twins
-    (``gemv_w8``) and produce the same bits.  The model is marked (``_mg_w8``).  Idempotent.  Returns
+    (``gemv_w8``) and produce the same bits, and so do steps of 9..64 rows (``gemm_rows_w8``) where the
+    module switch ``_W8_ROWS`` is set -- it is off, that kernel measured no faster than the bf16 rows
+    GEMM; the prefill and steps of more than 64 rows stay on the snapped bf16 weights.  The model is
+    marked (``_mg_w8``).  Idempotent.  Returns
     {weight name: the largest |W - s q| / a_n over its rows} (0.0 on a snapped model; < 1 / 127)."""
     report = {}
     for name, w in _w8_named_weights(model):
@@ -232,6 +236,11 @@ _ROWS_GEMM = os.environ.get("MINGPT_ROWS_GEMM", "1") != "0"
 # a model marked by quantize_int8_ runs its skinny-GEMM projections on the int8 twins (gemv_w8: the
 # same bits from half the weight bytes); False (MINGPT_W8_DECODE=0) keeps them on the bf16 kernel
 _W8_DECODE = os.environ.get("MINGPT_W8_DECODE", "1") != "0"
+# ... and with _W8_ROWS its rows-GEMM projections (9..64 rows) on gemm_rows_w8, the same bits again.
+# Off: measured against the bf16 rows GEMM on the same snapped model, every row-tile class had a case
+# slower than bf16 by more than the run-to-run spread (GPT-2 124M 2-4.5 %, gpt2-xl level; PERF.md 'W8
+# rows').  A module switch for that A/B, under _W8_DECODE; no environment variable
+_W8_ROWS = False
 # a kv_cache="int8" state keeps int8 caches and attends with attention_decode_kv8 (attention_kv8.hip);
 # False (MINGPT_KV8_DECODE=0) runs the same KV8 model on the bf16 kernels: bf16 caches holding snapped
 # rows, kv8_store on the step's row in place, then attention_decode -- the same bits
@@ -294,7 +303,8 @@ class _Body:
         self.C, self.G, self.bf, self.w8, self.model = ext(), G, bf16_weights(model), w8_weights(model), model
 
     def _w8_on(self):
-        """The skinny-GEMM projections read int8 twins: the model is marked and the switch is on."""
+        """The skinny-GEMM projections (with ``_W8_ROWS`` the rows-GEMM ones too) read int8 twins: the
+        model is marked and the switch is on."""
         return _W8_DECODE and self.model.__dict__.get("_mg_w8", False)
 
     def _route(self, rows):
@@ -304,7 +314,9 @@ class _Body:
         8192: every preset up to gpt2-xl (6400); the LayerNorm'ed projections and the LM head have
         K = D <= 2048, inside the kernel's 4096 for fused LayerNorm and wide outputs.  9..64 rows:
         the rows GEMM (gemm_rows.hip) streams each weight matrix once with the rows as MFMA
-        operands; more rows, a wider model, or ``_ROWS_GEMM`` off: the MFMA GEMM."""
+        operands; more rows, a wider model, or ``_ROWS_GEMM`` off: the MFMA GEMM.  On a model marked
+        by ``quantize_int8_`` the skinny GEMM, and with ``_W8_ROWS`` the rows GEMM, read the int8
+        twins (``_lin``); the MFMA GEMM and the prefill read the snapped bf16 weights."""
         K = 4 * self.model.config.n_embed
         if self.C.gemv_supported(rows, K):
             return "gemv"
@@ -317,7 +329,9 @@ class _Body:
         ``route`` names: ``"gemv"`` the skinny GEMM (gemv.hip, up to 8 decode rows; the LayerNorm is
         fused into its staging, and ``am`` fuses the LM head's greedy argmax), ``"rows"`` the rows GEMM
         (gemm_rows.hip, 9..64 decode rows) and ``"mfma"`` the MFMA GEMM (gemm.hip), both behind a
-        LayerNorm launch."""
+        LayerNorm launch.  With W8 on (``_w8_on``) the skinny GEMM, and with ``_W8_ROWS`` the rows GEMM,
+        take a weight's int8 twin (``gemv_w8``, ``gemm_rows_w8``) where one is live, else the bf16
+        weight, per weight."""
         C, G, bf = self.C, self.G, self.bf
         eps = self.model.config.layer_norm_eps
         if route not in ("gemv", "rows", "mfma"):
@@ -333,7 +347,9 @@ class _Body:
         if ln is not None:
             inp, _, _ = C.layernorm_fwd(inp, bf(ln.weight), bf(ln.bias), eps)
         if route == "rows":
-            return C.gemm_rows(inp, bf(w), code, bf(b) if b is not None else None, resid, ld)
+            tw = self.w8(w) if _W8_ROWS and self._w8_on() else None
+            kernel, wt = (C.gemm_rows, (bf(w),)) if tw is None else (C.gemm_rows_w8, tw)
+            return kernel(inp, *wt, code, bf(b) if b is not None else None, resid, ld)
         if epi == "gelu":
             pre = torch.empty((inp.shape[0], w.shape[0]), dtype=torch.bfloat16, device=inp.device)
             return G.gemm_nt(inp, bf(w), bias=bf(b), epi="gelu", pre_out=pre)
@@ -528,7 +544,7 @@ class _GpuCache(_Body):
     def _stamp(self):
         # the weights' stamp, which skinny GEMM and which decode attention the steps launch: a loop
         # captured for one kernel is never replayed for the other
-        return _weight_stamp(self.model), self._w8_on(), self._kv8_on()
+        return _weight_stamp(self.model), (self._w8_on(), _W8_ROWS), self._kv8_on()
 
     def _fresh(self):
         if self.kv8:
