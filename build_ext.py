@@ -35,9 +35,12 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-un
 # multiplies into v_pk_mul/fma_f32 pairs with s_nop between them, an anti-lever beside MFMAs
 # (MI355X_MICROARCH 'price of one filler'), and the hd = 64 backward's register budget is tight.
 # gemm_rows.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the int8 conversion or the
-# partial sums; the bf16 instantiations hold none either way (PERF.md 'W8 rows')
+# partial sums; the bf16 instantiations hold none either way (PERF.md 'W8 rows').
+# attention_extend.hip: the same for its accumulator rescales and the split combine
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attention_train.hip": ["-fno-slp-vectorize"],
-              "gemm_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "gemm_rows.hip": _NO_PK_F32,
+              "attention_extend.hip": _NO_PK_F32}
 
 
 

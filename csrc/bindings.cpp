@@ -696,6 +696,32 @@ at::Tensor attention_decode(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// Chunk attention over the KV cache (kernels.h): qkv_new [B * Tq, 3D] at positions base .. base + Tq - 1
+// of cache [B, Tmax, 3D]; appends their K/V rows and returns out [B * Tq, D]
+at::Tensor attention_extend(const at::Tensor& qkv_new, const at::Tensor& cache, int64_t H, int64_t base) {
+  CHECK_BF16(qkv_new); CHECK_BF16(cache); CHECK_CONTIG(qkv_new); CHECK_CONTIG(cache);
+  TORCH_CHECK(cache.dim() == 3 && cache.size(2) % 3 == 0, "attention_extend: cache must be [B, Tmax, 3D]");
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) == cache.size(2), "attention_extend: qkv_new must be [B * Tq, 3D]");
+  TORCH_CHECK(qkv_new.device() == cache.device(), "attention_extend: the cache is on another device");
+  const int64_t B = cache.size(0), Tmax = cache.size(1), D = cache.size(2) / 3;
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              "attention_extend: head dim must be a multiple of 8, at most 128");
+  TORCH_CHECK(qkv_new.size(0) >= B && qkv_new.size(0) % B == 0, "attention_extend: qkv_new must hold Tq >= 1 rows per sequence");
+  const int64_t Tq = qkv_new.size(0) / B;
+  TORCH_CHECK(base >= 0 && base + Tq <= Tmax, "attention_extend: base >= 0 and base + Tq <= Tmax");
+  TORCH_CHECK(B * Tmax * 3 * D < (int64_t(1) << 40) && B * H <= 65535, "attention_extend: batch too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(cache.data_ptr()) % 16 == 0, "attention_extend: tensors must be 16-byte aligned");
+  DevGuard g(cache.device());
+  auto out = at::empty({B * Tq, D}, cache.options());
+  const int64_t np = (int64_t)mg::attention_extend_part_floats((int)B, (int)Tq, (int)H, (int)(D / H), (int)base);
+  at::Tensor part;
+  if (np) part = at::empty({np}, cache.options().dtype(at::kFloat));
+  mg::attention_extend(bp(qkv_new), bp(cache), bp(out), np ? fp(part) : nullptr, (int)B, (int)Tq, (int)H,
+                       (int)(D / H), Tmax, (int)base, cur_stream());
+  return out;
+}
+
 // The int8 KV cache of one layer (kernels.h): kq int8 [B, 2, H, Tmax, hd], ks fp32 [B, 2, H, Tmax]
 void kv8_cache_args(const char* op, const at::Tensor& kq, const at::Tensor& ks, int64_t B, int64_t H, int64_t hd) {
   CHECK_DEV(kq); CHECK_CONTIG(kq); CHECK_F32(ks); CHECK_CONTIG(ks);
@@ -1386,5 +1412,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ctl"), py::arg("seq"), py::arg("steps"), py::arg("hist"));
   m.def("attention_decode_part_floats", [](int64_t B, int64_t H, int64_t hd) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
+  });
+  m.def("attention_extend", &attention_extend, py::arg("qkv_new"), py::arg("cache"), py::arg("H"), py::arg("base"));
+  // the key splits attention_extend runs B sequences of Tq new rows at `base` with (1: no combine launch)
+  m.def("attention_extend_splits", [](int64_t B, int64_t Tq, int64_t H, int64_t base) {
+    return (int64_t)mg::attention_extend_splits((int)B, (int)Tq, (int)H, (int)base);
   });
 }

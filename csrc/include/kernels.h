@@ -285,6 +285,21 @@ void attention_decode(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, int B, 
                       long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
                       const int* pos_dev = nullptr, int pos_stride = 0, int group = 1);
 
+// attention_extend.hip -- chunk attention over the KV cache: qkv_new [B * Tq, 3D] holds Tq new tokens
+// per sequence, row m = b * Tq + r the token at position base + r of sequence b of cache [B, Tmax, 3D].
+// Its K and V thirds are stored to cache row base + r bit for bit (the Q third of a cache row is not
+// touched), and out [B * Tq, D] row m = softmax(q K^T / sqrt(hd)) V over keys 0 .. base + r of that
+// sequence.  Tq >= 1, base >= 0 (0: a plain causal prefill), base + Tq <= Tmax, hd % 8 == 0, hd <= 128,
+// 16-byte aligned tensors.  Cache rows at or past base + Tq are never read into a result (they may
+// hold NaN).  Two stream-ordered launches (append, then attention reading the cache only), plus a
+// combine launch when the keys are split: attention_extend_splits(B, Tq, H, base) = S in 1..16, a
+// function of the shapes and the CU count only; part: attention_extend_part_floats floats of
+// workspace (0 when S = 1; may then be null).  A row's bits depend on its own sequence only.
+int attention_extend_splits(int B, int Tq, int H, int base);
+size_t attention_extend_part_floats(int B, int Tq, int H, int hd, int base);
+void attention_extend(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, int B, int Tq, int H,
+                      int hd, long Tmax, int base, hipStream_t stream);
+
 // Int8 KV cache (the KV8 rule in common.h; attention_kv8.hip).  Per layer: kq int8 [B, 2, H, Tmax, hd]
 // (K then V, 16-byte aligned) and ks fp32 [B, 2, H, Tmax], one scale per (b, K | V, h, position).
 // hd % 8 == 0, hd <= 128; hd / 8 need not be a power of two.

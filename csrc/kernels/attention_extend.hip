@@ -1,0 +1,414 @@
+// Chunk attention over the KV cache for gfx950 (CDNA4, MI355X): Tq new tokens per sequence, at
+// positions base .. base + Tq - 1, attend to the `base` cached keys plus the chunk itself, and their
+// K/V rows are appended to the cache.  (Square-causal training forward: attention_fwd.hip; one query
+// per sequence: attention.hip.)  models/generation.py extends a cache that already holds a prompt's
+// prefix with it instead of prefilling from row 0 (`_GpuCache.extend`).
+//
+// Append and reads: TWO stream-ordered launches.  attn_extend_append_kernel copies the K and V thirds
+// of qkv_new to cache rows [base, base + Tq) bit for bit (the Q third of a cache row is never
+// written); the attention launch after it reads every key and value from the cache and writes no
+// cache byte, so no workgroup reads a row that another workgroup of its launch writes.  The other
+// way -- keys >= base from qkv_new, one designated workgroup per (b, h) appending, as the grouped
+// decode kernel does -- was not taken: `base` is not tile-aligned, so the tile that straddles it
+// would stage rows from two tensors with a per-row source select, and every tile would carry the
+// second descriptor; here a tile has one source and one descriptor, and the append is one small
+// copy per layer in front of a launch that is never captured per token.
+//
+// Stale rows: the cache comes from torch.empty, rows at or past base + Tq may hold NaN / inf bits.
+// Every K / V load goes through a buffer descriptor over the sequence's rows [0, base + Tq) only
+// (kv_rsrc): a row past it reads as zeros, and its scores are masked as well.  A 16-byte chunk whose
+// columns lie at or past hd (LDS images are 64 columns wide) is staged as zeros too: it would
+// otherwise read the next head, the next third or the next row's -- stale -- Q third, and 0 x NaN in
+// an MFMA is NaN.
+//
+// Attention kernel (FA2 structure of the training forward, no dropout):
+//  * grid (query block, b * h, key split); workgroup = 4 waves = 128 queries of one (b, h), each
+//    wave 32 of them; a wave whose queries are all past Tq issues no MFMA but stages tiles.
+//  * Q fragments (from qkv_new) live in VGPRs, pre-multiplied by log2(e) / sqrt(hd).
+//  * 64-key K / V tiles double-buffered through LDS (register staging: tile t + 1's loads are in
+//    flight during tile t's MFMAs), one barrier per tile.
+//  * S^T = K Q^T with v_mfma_f32_32x32x16_bf16: the query is on the lane, the softmax statistics are
+//    lane-local; the running max rides in as the MFMA's C operand and moves only when a tile's row
+//    sum leaves [2^-60, 2^60] (ext_tile).  P goes to bf16 in registers as the B operand of
+//    O^T = V^T P^T; V^T fragments come from LDS with ds_read_b64_tr_b16.
+//  * the causal limit of query r is key base + r: tiles wholly below base + (the wave's first query)
+//    run unmasked, tiles that straddle the diagonal take the masked body (a per-lane `lim`), tiles
+//    past the wave's last query are skipped per wave.
+//  * key splits: the shape that matters is few queries against many keys (Tq 1..64, base in the
+//    hundreds), where a workgroup per (query block, b, h) leaves most of the chip idle.  Split s
+//    takes `tps` whole 64-key tiles; with S > 1 every split writes its unnormalised fp32 state
+//    (m, l, O) of the rows below Tq to a workspace and attn_extend_combine_kernel -- a launch of its
+//    own: a launch boundary cannot hang, and this op is not captured per token -- rescales, sums in
+//    split order and stores bf16.  S = 1 stores `out` directly.  S depends on the shapes and the CU
+//    count only (attention_extend_splits), so equal calls give equal bits, and a row's bits depend
+//    on its own sequence only.
+//  * instantiated per number of 16-column MFMA k-steps, nks_for(hd).
+#include "attn_common.h"
+#include "kernels.h"
+
+using namespace mg;
+using namespace mg::attn;
+
+namespace {
+
+constexpr int kExtSplitsMax = 16;
+
+struct ExtArgs {
+  const bf16_t* qkv_new;  // [B * Tq, 3D]
+  const bf16_t* cache;    // [B, Tmax, 3D], rows [base, base + Tq) already appended
+  bf16_t* out;            // [B * Tq, D]
+  float* part_ml;         // S > 1: [nqb][B * H][S][128][2] {m, l}
+  float* part_o;          // S > 1: [nqb][B * H][S][128][hd]
+  int B, Tq, H, hd, D, base;
+  long Tmax;
+  int S, tps;             // key splits and whole 64-key tiles per split
+  float scale_log2;       // log2(e) / sqrt(hd)
+};
+
+// K and V thirds of qkv_new row b * Tq + r -> cache row base + r of sequence b, 16 bytes a thread
+__global__ __launch_bounds__(256) void attn_extend_append_kernel(const bf16_t* __restrict__ qkv_new,
+                                                                 bf16_t* __restrict__ cache, int B, int Tq,
+                                                                 int D, long Tmax, int base) {
+  const int cpr = D >> 2;  // 16-byte chunks of a row's K and V thirds (2 D elements)
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * Tq * cpr) return;
+  const long m = i / cpr;
+  const int c = (int)(i % cpr);
+  const long b = m / Tq, r = m % Tq;
+  const long ld = 3L * D;
+  st16(cache + (b * Tmax + base + r) * ld + D + 8 * c, ld16(qkv_new + m * ld + D + 8 * c));
+}
+
+// One 64-key tile for one wave's 32 queries: S'^T = K Q^T - m, p = exp2(S'), O^T += V^T P^T.  m moves
+// only when a tile's row sum leaves [lo, 2^60] (lo = 2^-60 on a split's first tile, where m starts
+// at 0, else 0); the tile is then recomputed against its row max (K is still in LDS).
+template <int NKS, bool MASK>
+MG_DEVICE void ext_tile(const char* sk, const char* sv, const int (&ko)[NKS], const bf16x8 (&qf)[NKS],
+                        f32x16 (&o)[(NKS + 1) / 2], f32x16& negm, float& m, float& l, bool first, int lim,
+                        int ta0, int tb0, int ta1, int tb1) {
+  constexpr int NO = (NKS + 1) / 2;
+  constexpr int HALF = 64 * ROWB;
+  f32x16 s[2];
+  auto scores = [&](int lim) {
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+      s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_row_at(sk + sub * 32 * ROWB, ko[0]), qf[0], negm, 0, 0, 0);
+#pragma unroll
+      for (int ks = 1; ks < NKS; ++ks)
+        s[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lds_row_at(sk + sub * 32 * ROWB, ko[ks]), qf[ks],
+                                                         s[sub], 0, 0, 0);
+    }
+    if constexpr (MASK) {  // key = k0 + c(sub, r) + 4 h32, c a constant: one compare per score
+      asm volatile("" : "+v"(lim));  // the compares stay below the MFMAs (SGPR pressure otherwise)
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          s[sub][r] = (sub * 32 + (r & 3) + 8 * (r >> 2) > lim) ? kNegBig : s[sub][r];
+    }
+  };
+  auto expsum = [&]() {
+    float rs = 0.f;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = fexp2(s[sub][r]);
+        rs += p;
+        s[sub][r] = p;
+      }
+    return rs;
+  };
+  scores(lim);
+  float rs = expsum();
+  const float lo = first ? 8.673617379884035e-19f : 0.f;  // 2^-60
+  if (__builtin_expect(__any(!(rs <= 1.152921504606847e18f && rs >= lo)), 0)) {  // 2^60; inf / nan
+    int lim2 = lim;
+    asm volatile("" : "+v"(lim2));
+    scores(lim2);
+    float mx = s[0][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[0][r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[1][r]);
+    mx = max_xor32(mx);
+    // a split's first tile may move m down as well (nothing accumulated yet); later tiles up only
+    const float d = first ? mx : fmaxf(mx, 0.f);
+    const float alpha = first ? 1.f : fexp2(-d);
+    l *= alpha;
+#pragma unroll
+    for (int n = 0; n < NO; ++n) o[n] *= alpha;
+    m += d;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) negm[r] = -m;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[sub][r] -= d;
+    rs = expsum();
+  }
+  l += rs;
+#pragma unroll
+  for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      const bf16x8 pf = pack_frag(s[sub], st);
+      const int rb = (sub * 32 + 16 * st) * ROWB;  // 16-row aligned: an immediate
+#pragma unroll
+      for (int n = 0; n < NO; ++n) {
+        const char* vb = sv + (n >> 1) * HALF + rb;
+        o[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            (n & 1) ? lds_tr_at(vb, ta1, tb1) : lds_tr_at(vb, ta0, tb0), pf, o[n], 0, 0, 0);
+      }
+    }
+}
+
+template <int NKS>
+__global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const ExtArgs a) {
+  constexpr int NH = (NKS + 3) / 4;   // 64-column halves of the LDS images
+  constexpr int NO = (NKS + 1) / 2;   // 32-column O^T accumulator tiles
+  constexpr int HALF = 64 * ROWB;     // one 64-row, 64-column image
+  constexpr int TILE = NH * HALF;     // one K or V tile
+  constexpr int NC = 2 * NH;          // 16-byte chunks per thread per tile per matrix
+  __shared__ __attribute__((aligned(16))) char smem[4 * TILE];  // K0 V0 K1 V1
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int h32 = lane >> 5, l32 = lane & 31;
+  const int qb = blockIdx.x, bh = blockIdx.y, sp = blockIdx.z;
+  const int b = bh / a.H, hh = bh % a.H;
+  const long ld = 3L * a.D;
+  const int q0 = qb * 128;
+  const int qend = min(a.Tq, q0 + 128);            // the block's queries are rows [q0, qend)
+  const int ntb = (a.base + qend + 63) / 64;       // key tiles the block's last query sees
+  const int t0 = sp * a.tps, t1 = min(t0 + a.tps, ntb);  // this split's tiles [t0, t1)
+
+  // tile staging: chunk c of this thread -> (half, row, 16-byte column chunk).  Buffer loads through
+  // a per-tile descriptor whose range ends at the sequence's row base + Tq (file header); a chunk
+  // whose columns are at or past hd is staged as zeros.
+  uint32_t voff[NC], sdst[NC];
+  bool cok[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int idx = threadIdx.x + 256 * c;
+    const int hf = idx >> 9, rem = idx & 511;
+    voff[c] = (uint32_t)(((rem >> 3) * ld + hf * 64 + (rem & 7) * 8) * 2);
+    sdst[c] = hf * HALF + lds_off(rem >> 3, rem & 7);
+    cok[c] = hf * 64 + (rem & 7) * 8 < a.hd;
+  }
+  const bf16_t* seq = a.cache + (long)b * a.Tmax * ld;
+  const uint64_t seq_bytes = (uint64_t)(a.base + a.Tq) * ld * 2;  // rows [0, base + Tq) of this sequence
+  const uint64_t kcol = (uint64_t)(a.D + hh * a.hd) * 2;
+  auto load_tile = [&](uint4 (&rk)[NC], uint4 (&rv)[NC], int k0) {
+    const uint64_t off = kcol + (uint64_t)k0 * ld * 2;
+    const __amdgpu_buffer_rsrc_t dk = kv_rsrc(seq, seq_bytes, off);
+    const __amdgpu_buffer_rsrc_t dv = kv_rsrc(seq, seq_bytes, off + (uint64_t)a.D * 2);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const uint4 k = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(dk, voff[c], 0, 0));
+      const uint4 v = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(dv, voff[c], 0, 0));
+      rk[c] = cok[c] ? k : make_uint4(0, 0, 0, 0);
+      rv[c] = cok[c] ? v : make_uint4(0, 0, 0, 0);
+    }
+  };
+  auto store_tile = [&](char* dst, const uint4 (&rk)[NC], const uint4 (&rv)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      *reinterpret_cast<uint4*>(dst + sdst[c]) = rk[c];
+      *reinterpret_cast<uint4*>(dst + TILE + sdst[c]) = rv[c];
+    }
+  };
+
+  // per-lane fragment offsets: K rows l32 (+32 per sub: an immediate), chunk 2 ks + h32;
+  // V^T transposed reads rows 4 h32 + q (+8), columns (n & 1) * 32 + cb + 4 p
+  int ko[NKS];
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) ko[ks] = (ks >> 2) * HALF + lds_off(l32, (2 * ks + h32) & 7);
+  const int trq = (lane & 15) >> 2, trc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int ta0 = tr_off(4 * h32 + trq, trc), tb0 = tr_off(8 + 4 * h32 + trq, trc);
+  const int ta1 = tr_off(4 * h32 + trq, 32 + trc), tb1 = tr_off(8 + 4 * h32 + trq, 32 + trc);
+
+  // this lane's query: row myr of the chunk, position base + myr; a lane past Tq holds a zero query
+  // under the last row's limit and stores nothing
+  const int wave_r = q0 + 32 * w;
+  const int myr = wave_r + l32;
+  const bool live = myr < a.Tq;
+  const int wave_first = a.base + wave_r;                    // position of the wave's first query
+  const int wave_last = a.base + min(wave_r + 31, a.Tq - 1);  // ... and of its last one
+  const int mypos = a.base + min(myr, a.Tq - 1);
+  const bf16_t* qrow = a.qkv_new + ((long)b * a.Tq + min(myr, a.Tq - 1)) * ld + hh * a.hd;
+  bf16x8 qf[NKS];
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int d = ks * 16 + 8 * h32;
+    const uint4 u = (live && d < a.hd) ? ld16(qrow + d) : make_uint4(0, 0, 0, 0);
+    float f[8];
+    unpack8(u, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] *= a.scale_log2;
+    qf[ks] = __builtin_bit_cast(bf16x8, pack8(f));
+  }
+  f32x16 o[NO], negm = f32x16{0};
+#pragma unroll
+  for (int n = 0; n < NO; ++n) o[n] = f32x16{0};
+  float m = 0.f, l = 0.f;
+
+  if (t0 < t1) {  // (an empty split of a short block stages nothing and writes neutral partials)
+    {
+      uint4 rk[NC], rv[NC];
+      load_tile(rk, rv, t0 * 64);
+      store_tile(smem, rk, rv);
+    }
+    __syncthreads();
+    for (int t = t0; t < t1; ++t) {
+      const int it = t - t0;
+      const char* sk = smem + (it & 1) * 2 * TILE;
+      const char* sv = sk + TILE;
+      const bool more = t + 1 < t1;
+      uint4 rk[NC], rv[NC];
+      if (more) load_tile(rk, rv, (t + 1) * 64);
+      const int k0 = t * 64;
+      if (k0 <= wave_last && wave_r < a.Tq) {
+        const int lim = mypos - k0 - 4 * h32;
+        // the causal mask only on the tiles that straddle the diagonal (separate bodies)
+        if (k0 + 63 > wave_first) ext_tile<NKS, true>(sk, sv, ko, qf, o, negm, m, l, t == t0, lim, ta0, tb0, ta1, tb1);
+        else ext_tile<NKS, false>(sk, sv, ko, qf, o, negm, m, l, t == t0, lim, ta0, tb0, ta1, tb1);
+      }
+      if (more) store_tile(smem + ((it + 1) & 1) * 2 * TILE, rk, rv);
+      __syncthreads();
+    }
+  }
+
+  const float lt = sum_xor32(l);
+  if (!live) return;
+  if (a.S == 1) {  // the whole key range: normalise and store
+    const float inv = 1.f / lt;
+    bf16_t* orow = a.out + ((long)b * a.Tq + myr) * a.D + hh * a.hd;
+#pragma unroll
+    for (int n = 0; n < NO; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = n * 32 + 8 * g + 4 * h32;
+        if (d < a.hd)
+          *reinterpret_cast<uint2*>(orow + d) = make_uint2(pack2(o[n][4 * g] * inv, o[n][4 * g + 1] * inv),
+                                                           pack2(o[n][4 * g + 2] * inv, o[n][4 * g + 3] * inv));
+      }
+    return;
+  }
+  // this split's state of row myr: {m, l} and the unnormalised O.  A row that saw no key of the
+  // split (no tile, or its position lies below the split's first key) has weight zero: m = -big
+  const bool seen = t0 < t1 && mypos >= t0 * 64;
+  const long slot = (((long)qb * gridDim.y + bh) * a.S + sp) * 128 + (myr - q0);
+  if (h32 == 0) *reinterpret_cast<float2*>(a.part_ml + 2 * slot) = make_float2(seen ? m : kNegBig, seen ? lt : 0.f);
+  float* prow = a.part_o + slot * a.hd;
+#pragma unroll
+  for (int n = 0; n < NO; ++n)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = n * 32 + 8 * g + 4 * h32;
+      if (d < a.hd)
+        *reinterpret_cast<float4*>(prow + d) = seen ? make_float4(o[n][4 * g], o[n][4 * g + 1], o[n][4 * g + 2], o[n][4 * g + 3])
+                                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// out row = sum_s 2^(m_s - M) O_s / sum_s 2^(m_s - M) l_s, M = max_s m_s, in split order: a thread
+// per (row, 4 columns).  Split 0 holds key 0, which every row sees, so M is a real max.
+__global__ __launch_bounds__(256) void attn_extend_combine_kernel(const ExtArgs a) {
+  const int qb = blockIdx.y, bh = blockIdx.z;
+  const int q0 = qb * 128, rows = min(a.Tq - q0, 128), hd4 = a.hd >> 2;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * hd4) return;
+  const int r = i / hd4, d = (i % hd4) * 4;
+  const long slot0 = ((long)qb * gridDim.z + bh) * a.S * 128 + r;
+  float ms[kExtSplitsMax], M = kNegBig;
+#pragma unroll
+  for (int s = 0; s < kExtSplitsMax; ++s) {
+    ms[s] = s < a.S ? a.part_ml[2 * (slot0 + 128L * s)] : kNegBig;
+    M = fmaxf(M, ms[s]);
+  }
+  float L = 0.f;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int s = 0; s < kExtSplitsMax; ++s) {
+    if (s < a.S) {
+      const float wgt = fexp2(ms[s] - M);
+      const float4 v = *reinterpret_cast<const float4*>(a.part_o + (slot0 + 128L * s) * a.hd + d);
+      L += wgt * a.part_ml[2 * (slot0 + 128L * s) + 1];
+      acc.x += wgt * v.x;
+      acc.y += wgt * v.y;
+      acc.z += wgt * v.z;
+      acc.w += wgt * v.w;
+    }
+  }
+  const float inv = 1.f / L;
+  const int b = bh / a.H, hh = bh % a.H;
+  bf16_t* orow = a.out + ((long)b * a.Tq + q0 + r) * a.D + hh * a.hd + d;
+  *reinterpret_cast<uint2*>(orow) = make_uint2(pack2(acc.x * inv, acc.y * inv), pack2(acc.z * inv, acc.w * inv));
+}
+
+int ext_cu_count() {
+  static int ncu[64] = {0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64) dev = 0;
+  if (!ncu[dev]) {
+    int n = 0;
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    ncu[dev] = n > 0 ? n : 256;
+  }
+  return ncu[dev];
+}
+
+// whole 64-key tiles per split: enough splits to put two workgroups on every CU, at least two tiles
+// each (a split's partial state is about a tile's worth of traffic), at most kExtSplitsMax splits
+int ext_tiles_per_split(int B, int Tq, int H, int base) {
+  const int nt = cdiv(base + Tq, 64);
+  const long wgs = (long)cdiv(Tq, 128) * B * H;
+  long S = 2L * ext_cu_count() / wgs;
+  S = std::min<long>(S, std::min(kExtSplitsMax, nt / 2));
+  return cdiv(nt, std::max<long>(S, 1));
+}
+
+template <int NKS>
+void launch_extend(const ExtArgs& a, hipStream_t stream) {
+  attn_extend_kernel<NKS><<<dim3(cdiv(a.Tq, 128), a.B * a.H, a.S), 256, 0, stream>>>(a);
+}
+
+}  // namespace
+
+namespace mg {
+
+int attention_extend_splits(int B, int Tq, int H, int base) {
+  return cdiv(cdiv(base + Tq, 64), ext_tiles_per_split(B, Tq, H, base));
+}
+
+size_t attention_extend_part_floats(int B, int Tq, int H, int hd, int base) {
+  const int S = attention_extend_splits(B, Tq, H, base);
+  return S > 1 ? (size_t)cdiv(Tq, 128) * B * H * S * 128 * (hd + 2) : 0;
+}
+
+void attention_extend(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, int B, int Tq, int H,
+                      int hd, long Tmax, int base, hipStream_t stream) {
+  ExtArgs a{};
+  a.qkv_new = qkv_new; a.cache = cache; a.out = out;
+  a.B = B; a.Tq = Tq; a.H = H; a.hd = hd; a.D = H * hd; a.base = base; a.Tmax = Tmax;
+  a.tps = ext_tiles_per_split(B, Tq, H, base);
+  a.S = attention_extend_splits(B, Tq, H, base);
+  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
+  const int nqb = cdiv(Tq, 128);
+  a.part_ml = part;
+  a.part_o = part ? part + (size_t)nqb * B * H * a.S * 128 * 2 : nullptr;
+  attn_extend_append_kernel<<<cdiv((long)B * Tq * (a.D >> 2), 256), 256, 0, stream>>>(qkv_new, cache, B, Tq, a.D,
+                                                                                     Tmax, base);
+  switch (nks_for(hd)) {
+    case 1: launch_extend<1>(a, stream); break;
+    case 2: launch_extend<2>(a, stream); break;
+    case 3: launch_extend<3>(a, stream); break;
+    case 4: launch_extend<4>(a, stream); break;
+    case 6: launch_extend<6>(a, stream); break;
+    default: launch_extend<8>(a, stream); break;
+  }
+  if (a.S > 1)
+    attn_extend_combine_kernel<<<dim3(cdiv(std::min(Tq, 128) * (hd >> 2), 256), nqb, B * H), 256, 0, stream>>>(a);
+}
+
+}  // namespace mg

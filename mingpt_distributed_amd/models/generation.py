@@ -439,6 +439,12 @@ class _GpuCache(_Body):
         self._sparams, self._rparams, self._pparams = (_Params(self.dev) for _ in range(3))
         self._rstate, self._bstate, self._sstate = None, {}, {}
         self.logits = None
+        # prefix reuse (``_state_for(reuse=True)``): the tokens whose K/V rows the bf16 caches hold, by
+        # row, in ``held[:, :nheld]`` (recorded after a reuse-enabled ``generate``; any prefill clears
+        # it), and how many of them the last prefill of this state kept (``reused``; 0: a full one)
+        self.held = (torch.zeros(B, tmax, dtype=torch.long, device=self.dev)
+                     if rows is None and not self.kv8 else None)
+        self.nheld = self.reused = 0
         if rows is None:
             self.prefill(idx, last)
 
@@ -500,6 +506,7 @@ class _GpuCache(_Body):
         those of column ``last[b]`` (int64 [B]: the row's length - 1) of row b."""
         cfg = self.model.config
         B = idx.size(0)
+        self.nheld = self.reused = 0
         if self.kv8:
             self._kv8_storage()
         x = self._prompt(idx, self._keep)
@@ -509,6 +516,39 @@ class _GpuCache(_Body):
             x = x[:, -1]
         self.logits = self._head(x.contiguous(), "mfma")[:, :cfg.vocab_size]
         return self.logits
+
+    def extend(self, idx_new, base):
+        """Prefill on top of what the caches hold: run the new tokens idx_new [B, Tq], which sit at
+        positions base .. base + Tq - 1 behind ``base`` cached rows per sequence, through the blocks on
+        the route of B * Tq rows (``_route``), each layer attending with ``attention_extend`` (the chunk
+        against the cached keys plus itself; it appends the chunk's K/V rows), and set ``logits`` [B, V]
+        to the last new row's -- where ``prefill`` leaves them, from the LM head on the route of B rows."""
+        C, bf = self.C, self.bf
+        tr, cfg = self.model.transformer, self.model.config
+        B, Tq = idx_new.shape
+        D, H = cfg.n_embed, cfg.n_head
+        pos = (base + torch.arange(Tq, dtype=torch.int32, device=self.dev)).repeat(B)  # one per row
+        x = C.embedding_fwd(idx_new.reshape(B * Tq, 1).contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0,
+                            pos, None, None, 1).view(B * Tq, D)
+        x = self._blocks(x, lambda i, qkv: C.attention_extend(qkv, self.caches[i], H, base), self._route(B * Tq))
+        self.logits = self._head(x.view(B, Tq, D)[:, -1].contiguous(), self._route(B))[:, :cfg.vocab_size]
+        return self.logits
+
+    def common_prefix(self, idx):
+        """The number of leading columns of idx [B, T] that equal ``held[:, :nheld]`` in every row: one
+        device reduction, one read."""
+        n = min(self.nheld, idx.size(1))
+        if n <= 0:
+            return 0
+        same = (idx[:, :n] == self.held[:, :n]).all(dim=0).long()
+        return int(same.cumprod(0).sum().item())
+
+    def hold(self, tokens):
+        """Record that the caches hold the K/V rows of ``tokens`` [B, n] (None: of nothing known)."""
+        self.nheld = 0
+        if tokens is not None and self.held is not None and tokens.size(1) <= self.tmax:
+            self.nheld = tokens.size(1)
+            self.held[:, :self.nheld].copy_(tokens)
 
     def _decode(self, tok, pos, hpos, pos_stride=0, am_part=None, seq=None):
         """One decode step, with nothing from the host: embed token ``tok`` [B, 1] (int64, on the
@@ -1086,18 +1126,45 @@ def kv_cache_nbytes(model):
     return {slot: model.__dict__[slot].cache_nbytes() for slot in _STATE_SLOTS if model.__dict__.get(slot) is not None}
 
 
-def _state_for(model, slot, idx, tmax, rows=None, last=None):
+# ``reuse``: extend a common prefix only where it measured faster than the fresh prefill (PERF.md 'Prefix
+# reuse': 16 cases on GPT-2 124M and gpt2-xl; the extension has more launches per layer, so it has to
+# save rows that cost something).  False takes every common prefix (tests of the path, A/B)
+_REUSE_GATE = True
+
+
+def _reuse_pays(B, P, Tq):
+    """The measured rule: the new rows fit the skinny or the rows GEMM (B * Tq <= 64, where the fresh
+    prefill would stream every weight for rows the cache already has), or the prefix saves at least 2048
+    rows of prefill (B * P).  Slower outside it: P = 1, and P = 512 with 128 new rows at B = 1."""
+    return not _REUSE_GATE or B * Tq <= 64 or B * P >= 2048
+
+
+def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
     """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, beside it ``_mg_beam_cache`` /
     ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain loops
     and their graphs alone, and the KV8 state of each (``_kv_slot``) -- or a new one when the device,
     the rows or ``tmax`` differ.  The
     plain state comes back prefilled with ``idx`` (``last``: ``_GpuCache.prefill``); the others are
-    prefilled by their callers, after the loop is built."""
+    prefilled by their callers, after the loop is built.
+
+    ``reuse`` (a plain bf16 state; ``generate(reuse_cache=True)``): when the state that is kept matches,
+    no weight changed since (``_stamp``) and its record ``held[:, :nheld]`` of the tokens in the caches
+    shares a prefix of P tokens with ``idx`` in every row -- P capped at T - 1: one row at least has to run
+    for the logits -- only ``idx[:, P:]`` is run, on top of the cached rows (``_GpuCache.extend``), where
+    that measured faster (``_reuse_pays``); else the prefill as ever.  ``reused`` on the state is P, 0 after a full
+    prefill."""
     c = model.__dict__.get(slot)
     if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
         c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows, kv8=slot in _KV8_SLOTS.values())
     elif rows is None:
-        c.prefill(idx, last)
+        P = 0
+        if reuse and last is None and c.held is not None and c.nheld > 0 and c._stamp() == c.stamp:
+            P = min(c.common_prefix(idx), idx.size(1) - 1)
+        if P >= 1 and _reuse_pays(idx.size(0), P, idx.size(1) - P):
+            c.extend(idx[:, P:], P)
+            c.nheld, c.reused = 0, P  # the rows past P are overwritten: the caller records the new ones
+        else:
+            c.prefill(idx, last)
     return c
 
 
@@ -1138,8 +1205,24 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
              top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
              presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
-             kv_cache: str = "bf16"):
-    """``kv_cache``: ``"bf16"`` (default: every path as it is without the argument) or ``"int8"``, the KV8
+             kv_cache: str = "bf16", reuse_cache: bool = False):
+    """``reuse_cache``: prefix reuse on the GPU.  The decode state the model keeps between calls records
+    which tokens its KV cache holds; when this call's prompt starts with P >= 1 of them (in every row of
+    the batch) and the shapes are ones where it measured faster (``_reuse_pays``: B * Tq <= 64 new rows, or
+    B * P >= 2048 rows saved), only the tokens behind that prefix are run -- ``attention_extend`` attends the chunk to
+    the cached keys plus itself -- instead of the whole prompt from row 0: a chat turn that appends to
+    the last exchange, or many continuations of one few-shot prompt.  It is the same model: the new rows
+    take another GEMM route (by their count) and attention tiling than a fresh prefill, so the logits
+    differ in the last bf16 bits and a token may differ only at a near-tie.  The record is kept by calls
+    that pass ``reuse_cache=True`` and fit one context window (prompt + ``max_new_tokens`` <=
+    ``block_size``); any other call on the state clears it, and the default (False) leaves every path,
+    loop and captured graph as it is.  Covers the device loops and the host loop (``seed=None``); on the
+    CPU and with ``use_cache=False`` it is accepted and has no effect; with ``kv_cache="int8"`` it is a
+    ValueError (the int8 cache has no extension kernel).  ``generate_batch``, ``generate_beam``,
+    ``generate_speculative`` and ``score`` do not take it.  ``projects/generate/generate.py
+    --reuse-cache`` passes it through.
+
+    ``kv_cache``: ``"bf16"`` (default: every path as it is without the argument) or ``"int8"``, the KV8
     model (the rule in common.h, ``ops.quant.snap_vectors``): every K and V vector -- one per sequence,
     position, layer and head -- is snapped to int8 values times one power-of-two scale before any
     attention reads it, prompt and new tokens alike, on the GPU and the CPU; Q is untouched.  On the GPU
@@ -1182,6 +1265,11 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     if kv8 and not use_cache:
         raise ValueError("generate: kv_cache='int8' needs use_cache=True (without a cache there is nothing to "
                          "quantize)")
+    if kv8 and reuse_cache:
+        raise ValueError("generate: reuse_cache=True needs kv_cache='bf16' (prefix reuse extends the bf16 cache; "
+                         "the int8 cache has no extension kernel)")
+    # prefix reuse: GPU cache paths whose whole call fits one context window (a sliding window re-prefills)
+    reuse = bool(reuse_cache) and idx.is_cuda and use_cache and idx.size(1) + max_new_tokens <= bs
     seeded = do_sample and seed is not None
     if seeded or (do_sample and top_p is not None):
         R.check_sample_args(temperature, top_k, top_p)
@@ -1232,13 +1320,14 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         else:
             first = lambda c, T, ctx: c.logits.argmax(-1)
             loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs, proc=pwords, ctx=ctx)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords, slot)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords, slot, reuse)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
         if cache is None or T > bs:
             idx_cond = idx if T <= bs else idx[:, -bs:]
-            cache = _state_for(model, slot, idx_cond, bs) if idx.is_cuda else _CpuCache(model, idx_cond, kv8)
+            cache = (_state_for(model, slot, idx_cond, bs, reuse=reuse) if idx.is_cuda
+                     else _CpuCache(model, idx_cond, kv8))
             cache.pos = idx_cond.size(1)
             logits = cache.logits
         logits = edit(logits, idx[:, max(0, T - bs):])
@@ -1251,11 +1340,13 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
             continue
         logits = cache.step(idx_next, cache.pos)
         cache.pos += 1
+    if reuse and cache is not None:  # every token but the last was fed (the last one too; one less is safe)
+        cache.hold(idx[:, :-1])
     return done(idx)
 
 
 def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False, proc=None,
-                           slot="_mg_decode_cache"):
+                           slot="_mg_decode_cache", reuse=False):
     """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
     window's first token ``first(cache, T, ctx)`` [B], then the device-side token loop ``loop(cache,
     tok, L, n, T, ctx)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
@@ -1266,7 +1357,9 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     is a fresh prefill of the last block_size tokens -- the reference's crop-every-step semantics
     (``/root/reference/mingpt/model.py:333``).  ``logprobs``: the first token gets its
     log-probability from the prefill logits (``with_logprob``), ``loop`` returns a (tokens,
-    log-probabilities) pair, and so does this.  ``slot``: the decode state's (``_kv_slot``)."""
+    log-probabilities) pair, and so does this.  ``slot``: the decode state's (``_kv_slot``).  ``reuse``
+    (the whole call fits one window): the prefill may extend the cached prefix (``_state_for``), and the
+    state then records what its caches hold -- every token but the last one produced, which was never fed."""
     bs = model.block_size
     B, T0 = idx.shape
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
@@ -1281,7 +1374,7 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
-        cache = _state_for(model, slot, ctx, bs)
+        cache = _state_for(model, slot, ctx, bs, reuse=reuse)
         if proc is not None:
             cache.process_prefill(ctx, proc)
         tok = first(cache, T, ctx)
@@ -1291,6 +1384,8 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
         if n > 0:
             put(slice(T, T + n), loop(cache, out[:, T - 1:T], L, n, T, ctx))
             T += n
+    if reuse:
+        cache.hold(out[:, :end - 1])
     return outs if logprobs else out
 
 

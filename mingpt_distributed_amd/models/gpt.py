@@ -221,7 +221,7 @@ class GPT(nn.Module):
                  top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
                  top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
-                 kv_cache: str = "bf16"):
+                 kv_cache: str = "bf16", reuse_cache: bool = False):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
         prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
         ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
@@ -232,14 +232,16 @@ class GPT(nn.Module):
         ``no_repeat_ngram_size``: the logits processors over the context the model saw, applied to
         the logits before everything else (1.0 / 0.0 / 0.0 / 0: off).  ``kv_cache="int8"``: the KV8
         model -- K and V vectors snapped to int8 times a power-of-two scale, an int8 cache on the GPU
-        (``generation.generate``); needs ``use_cache``."""
+        (``generation.generate``); needs ``use_cache``.  ``reuse_cache=True``: on the GPU a prompt that starts
+        with the tokens the KV cache still holds from the last such call runs only the tokens behind them
+        (``attention_extend``); same model, logits equal to the last bf16 bits (``generation.generate``)."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
                         top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs,
                         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                         frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                        kv_cache=kv_cache)
+                        kv_cache=kv_cache, reuse_cache=reuse_cache)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,

@@ -91,6 +91,10 @@ def main(argv=None):
     ap.add_argument("--kv-int8", action="store_true",
                     help="int8 KV cache: K and V vectors snapped to int8 with one power-of-two scale each "
                          "(kv_cache='int8'), on every decoding mode")
+    ap.add_argument("--reuse-cache", action="store_true",
+                    help="prefix reuse (reuse_cache=True): a prompt that starts with the tokens the KV cache "
+                         "holds from the last call runs only the tokens behind them; one prompt, not with "
+                         "--beams, --speculative or --kv-int8")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
@@ -137,6 +141,8 @@ def main(argv=None):
         return generate_speculative(model, tok, x, a)
     x = x.expand(a.num_samples, -1).contiguous()
     kw = dict({"return_logprobs": True} if a.logprobs else {}, **proc, **kv_args(a))
+    if a.reuse_cache:
+        kw["reuse_cache"] = True
     y = model.generate(x, max_new_tokens=a.steps, temperature=a.temperature, do_sample=not a.greedy,
                        top_k=a.top_k, seed=a.seed, top_p=a.top_p, **kw)
     y, lp = y if a.logprobs else (y, None)
