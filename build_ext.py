@@ -37,10 +37,13 @@ COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-un
 # gemm_rows.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the int8 conversion or the
 # partial sums; the bf16 instantiations hold none either way (PERF.md 'W8 rows').
 # attention_extend.hip: the same for its accumulator rescales and the split combine
+# attention_shared.hip: the same again -- the wave fold and the combine are a * x + b * y over float4s,
+# exactly what the vectoriser packs; a row's bits must not depend on which form a lane got
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attention_train.hip": ["-fno-slp-vectorize"],
               "gemm_rows.hip": _NO_PK_F32,
-              "attention_extend.hip": _NO_PK_F32}
+              "attention_extend.hip": _NO_PK_F32,
+              "attention_shared.hip": _NO_PK_F32}
 
 
 

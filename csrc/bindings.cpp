@@ -722,6 +722,56 @@ at::Tensor attention_extend(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// Decode attention for rows that share a prompt (kernels.h): qkv_new [R, 3D], R = B * N rows, N per prompt
+// of pre [B, Tpre, 3D]; own [R, Town, 3D] gets the rows' K/V at row pos - P; pos_dev / plen_dev int32 [1] on
+// the device.  part (optional): the decode state's workspace; without it a temporary one is allocated
+// for this call (tests; not for captured graphs).  Returns out [R, D]
+at::Tensor attention_decode_shared(const at::Tensor& qkv_new, const at::Tensor& pre, const at::Tensor& own, int64_t H,
+                                   int64_t N, const at::Tensor& pos_dev, const at::Tensor& plen_dev,
+                                   const c10::optional<at::Tensor>& part) {
+  CHECK_BF16(qkv_new); CHECK_BF16(pre); CHECK_BF16(own);
+  CHECK_CONTIG(qkv_new); CHECK_CONTIG(pre); CHECK_CONTIG(own);
+  TORCH_CHECK(pre.dim() == 3 && pre.size(2) % 3 == 0, "attention_decode_shared: pre must be [B, Tpre, 3D]");
+  const int64_t B = pre.size(0), Tpre = pre.size(1), D3 = pre.size(2), D = D3 / 3;
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) == D3, "attention_decode_shared: qkv_new must be [R, 3D]");
+  const int64_t R = qkv_new.size(0);
+  TORCH_CHECK(own.dim() == 3 && own.size(0) == R && own.size(2) == D3 && own.size(1) >= 1,
+              "attention_decode_shared: own must be [R, Town, 3D]");
+  const int64_t Town = own.size(1);
+  TORCH_CHECK(qkv_new.device() == pre.device() && own.device() == pre.device(),
+              "attention_decode_shared: tensors on different devices");
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              "attention_decode_shared: head dim must be a multiple of 8, at most 128");
+  TORCH_CHECK(N >= 1 && N <= 64 && R >= 1 && R % N == 0 && R / N == B && R <= 4096,
+              "attention_decode_shared: N in 1..64 rows per prompt of pre, R = B * N rows");
+  TORCH_CHECK(Tpre >= 1 && Tpre <= (1 << 20) && Town <= (1 << 20) && B * H <= 65535,
+              "attention_decode_shared: cache too long or batch too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(pre.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(own.data_ptr()) % 16 == 0,
+              "attention_decode_shared: tensors must be 16-byte aligned");
+  for (const at::Tensor* t : {&pos_dev, &plen_dev})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() >= 1 &&
+                t->device() == pre.device(), "attention_decode_shared: pos_dev / plen_dev must be int32 [1] on the device");
+  DevGuard g(pre.device());
+  auto out = at::empty({R, D}, pre.options());
+  const int64_t np = (int64_t)mg::attention_decode_shared_part_floats((int)B, (int)N, (int)H, (int)(D / H), (int)Tpre,
+                                                                      (int)Town);
+  at::Tensor pt;
+  if (part.has_value() && part->defined()) {
+    CHECK_F32(*part);
+    TORCH_CHECK(part->numel() >= np && part->device() == pre.device() && part->is_contiguous() &&
+                reinterpret_cast<uintptr_t>(part->data_ptr()) % 16 == 0,
+                "attention_decode_shared: part workspace too small");
+    pt = *part;
+  } else {
+    pt = at::empty({np}, pre.options().dtype(at::kFloat));
+  }
+  mg::attention_decode_shared(bp(qkv_new), bp(pre), bp(own), bp(out), fp(pt), (int)R, (int)N, (int)H, (int)(D / H),
+                              (int)Tpre, (int)Town, pos_dev.data_ptr<int>(), plen_dev.data_ptr<int>(), cur_stream());
+  return out;
+}
+
 // The int8 KV cache of one layer (kernels.h): kq int8 [B, 2, H, Tmax, hd], ks fp32 [B, 2, H, Tmax]
 void kv8_cache_args(const char* op, const at::Tensor& kq, const at::Tensor& ks, int64_t B, int64_t H, int64_t hd) {
   CHECK_DEV(kq); CHECK_CONTIG(kq); CHECK_F32(ks); CHECK_CONTIG(ks);
@@ -1417,5 +1467,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the key splits attention_extend runs B sequences of Tq new rows at `base` with (1: no combine launch)
   m.def("attention_extend_splits", [](int64_t B, int64_t Tq, int64_t H, int64_t base) {
     return (int64_t)mg::attention_extend_splits((int)B, (int)Tq, (int)H, (int)base);
+  });
+  m.def("attention_decode_shared", &attention_decode_shared, py::arg("qkv_new"), py::arg("pre"), py::arg("own"),
+        py::arg("H"), py::arg("N"), py::arg("pos_dev"), py::arg("plen_dev"), py::arg("part") = py::none());
+  m.def("attention_decode_shared_part_floats", [](int64_t B, int64_t N, int64_t H, int64_t hd, int64_t Tpre, int64_t Town) {
+    return (int64_t)mg::attention_decode_shared_part_floats((int)B, (int)N, (int)H, (int)hd, (int)Tpre, (int)Town);
+  });
+  // the prefix key splits of attention_decode_shared, each ceil(ceil(Tpre / 64) / splits) whole 64-key tiles
+  m.def("attention_decode_shared_splits", [](int64_t B, int64_t H, int64_t Tpre) {
+    return (int64_t)mg::attention_decode_shared_splits((int)B, (int)H, (int)Tpre);
   });
 }

@@ -300,6 +300,27 @@ size_t attention_extend_part_floats(int B, int Tq, int H, int hd, int base);
 void attention_extend(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, int B, int Tq, int H,
                       int hd, long Tmax, int base, hipStream_t stream);
 
+// attention_shared.hip -- decode attention for rows that share a prompt: R = B * N rows, row m belongs
+// to prompt b = m / N.  P = *plen_dev (clamped to [1, Tpre]) is the shared prefix length, pos = *pos_dev
+// the position of the step's token.  Row m attends with its own query (qkv_new [R, 3D] row m) to keys
+// 0 .. P - 1 from pre [B, Tpre, 3D] row b (never written), keys P .. pos - 1 from own [R, Town, 3D] rows
+// m, j - P, and key pos from qkv_new row m itself; it stores its K and V thirds to own[m, pos - P] bit
+// for bit (the Q third of an own row is never written) and out [R, D] row m = softmax(q K^T / sqrt(hd)) V
+// over those pos + 1 keys.  Needs P <= pos and pos - P < Town: otherwise nothing is appended and out is
+// zero.  hd % 8 == 0, hd <= 128, N in 1..64, R % N == 0, 16-byte aligned tensors (the kernels put no bound
+// on B; generate keeps R <= 64, the rows GEMM's limit).  pre rows at or
+// past P and own rows at or past pos - P are never read into a result (they may hold NaN).  Three
+// stream-ordered launches (prefix splits on MFMA, own splits, combine); the grids depend on Tpre, Town,
+// B, N, H and the CU count only, so a captured graph serves every (P, pos).  part: the caller's workspace
+// of attention_decode_shared_part_floats floats.  attention_decode_shared_splits: the prefix key splits
+// (1..16), each ceil(ceil(Tpre / 64) / splits) whole 64-key tiles.  A row's bits depend on its own query,
+// its own rows of own and qkv_new and its prompt's pre rows only.
+int attention_decode_shared_splits(int B, int H, int Tpre);
+size_t attention_decode_shared_part_floats(int B, int N, int H, int hd, int Tpre, int Town);
+void attention_decode_shared(const bf16_t* qkv_new, const bf16_t* pre, bf16_t* own, bf16_t* out, float* part,
+                             int R, int N, int H, int hd, int Tpre, int Town, const int* pos_dev,
+                             const int* plen_dev, hipStream_t stream);
+
 // Int8 KV cache (the KV8 rule in common.h; attention_kv8.hip).  Per layer: kq int8 [B, 2, H, Tmax, hd]
 // (K then V, 16-byte aligned) and ks fp32 [B, 2, H, Tmax], one scale per (b, K | V, h, position).
 // hd % 8 == 0, hd <= 128; hd / 8 need not be a power of two.

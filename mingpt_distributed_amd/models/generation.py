@@ -17,6 +17,8 @@ Layout of this file, top to bottom:
   (B * W rows) and ``_mg_spec_cache`` (B sequences, B * K step rows), and beside each the state of
   ``kv_cache="int8"`` (the KV8 model on int8 caches): ``_mg_kv8_cache``, ``_mg_beam_kv8_cache`` and
   ``_mg_spec_kv8_cache``.
+* ``_SharedCache(_GpuCache)``: the state of ``generate(num_return_sequences=N)`` (``_mg_shared_cache``): the
+  prompts' K/V once, the B * N rows' own K/V beside them, ``attention_decode_shared`` in ``_decode``.
 * the word builders, ``_state_for``, then one section per entry point: checks, host loop, GPU half.
 
 Who owns what.  A loop in ``_loops`` owns its graph and, for the rectangular loops, its ``tok`` /
@@ -401,6 +403,8 @@ class _GpuCache(_Body):
     hipGraphs, unless a weight changed storage or version since the capture (then the graphs are
     re-captured)."""
 
+    shared = False  # the state kind of ``_SharedCache``: its steps attend with attention_decode_shared
+
     def __init__(self, model, idx, tmax, last=None, rows=None, kv8=False):
         """``rows`` (beam search, speculative decoding): a state of that many decode rows whose
         layers' caches are one stacked buffer ``kv`` [L, rows, Tmax, 3D] (the reorder kernel walks
@@ -567,7 +571,11 @@ class _GpuCache(_Body):
         route = self._route(B)
         x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, pos, am_part, seq,
                             pos_stride).view(B, D)
-        if self._kv8_on():
+        if self.shared:  # N rows per prompt (_SharedCache): the prompt's K/V once, the rows' own beside them
+            assert pos_stride == 0
+            attend = lambda i, qkv: C.attention_decode_shared(qkv, self.caches[i], self.own[i], H, self.N, pos,
+                                                              self.plen, self.part)
+        elif self._kv8_on():
             attend = lambda i, qkv: C.attention_decode_kv8(qkv, self.kq[i], self.ks[i], H, hpos, pos, self.dec_part,
                                                            self.dec_cnt, pos_stride)
         elif self.kv8:  # the KV8 model on the bf16 kernel: snap the step's K/V in place, then attend
@@ -584,7 +592,7 @@ class _GpuCache(_Body):
     def _stamp(self):
         # the weights' stamp, which skinny GEMM and which decode attention the steps launch: a loop
         # captured for one kernel is never replayed for the other
-        return _weight_stamp(self.model), (self._w8_on(), _W8_ROWS), self._kv8_on()
+        return _weight_stamp(self.model), (self._w8_on(), _W8_ROWS), self._kv8_on(), self.shared
 
     def _fresh(self):
         if self.kv8:
@@ -1050,6 +1058,66 @@ class _GpuCache(_Body):
         return st
 
 
+class _SharedCache(_GpuCache):
+    """The decode state of ``generate(num_return_sequences=N)``: R = B * N decode rows, row b * N + j the
+    j-th continuation of prompt b.  Per layer the prompts' qkv rows are kept ONCE, ``caches[i]`` [B, tmax,
+    3D] (the prefill writes them with ``_prompt`` / ``_keep`` as ever), and beside them ``own[i]`` [R, Town,
+    3D] takes what each row generates; ``plen`` int32 [1] on the device is the prompt length, ``part`` the
+    kernel's workspace.  ``_decode`` attends with ``attention_decode_shared``; every token loop of
+    ``_GpuCache`` runs unchanged on the R rows.  ``Town`` is ``max_new_tokens`` rounded up to 64; a later
+    call that needs more reallocates ``own`` and drops the captured loops (``room``)."""
+
+    shared = True
+
+    def __init__(self, model, idx, tmax, N, new_tokens):
+        _Body.__init__(self, model)
+        cfg = model.config
+        D, H = cfg.n_embed, cfg.n_head
+        self.tmax, self.dev, self.N, self.prompts = tmax, idx.device, N, idx.size(0)
+        self.B = self.prompts * N  # the decode rows: what the loops and ``_route`` go by
+        self.kv = self.kqs = self.kss = self.held = None
+        self.kv8 = self.stacked = False
+        self.kq, self.ks = [], []
+        self.caches = [torch.empty(self.prompts, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
+                       for _ in range(cfg.n_layer)]
+        self.own, self.town = [], 0
+        self.plen = torch.ones(1, dtype=torch.int32, device=self.dev)
+        self.stamp = self._stamp()
+        self._loops = {}
+        self._sparams, self._rparams, self._pparams = (_Params(self.dev) for _ in range(3))
+        self._rstate, self._bstate, self._sstate = None, {}, {}
+        self.nheld = self.reused = 0
+        self.room(new_tokens)
+        self.prefill(idx)
+
+    def room(self, new_tokens):
+        """``own`` rows for a call of ``new_tokens`` new tokens: the captured steps bake the buffers in, so
+        growing them drops every loop."""
+        town = (max(int(new_tokens), 1) + 63) // 64 * 64
+        if town <= self.town:
+            return
+        cfg = self.model.config
+        D, H = cfg.n_embed, cfg.n_head
+        self._loops.clear()
+        self.own = None  # free the old rows before the new ones are allocated
+        self.own = [torch.empty(self.B, town, 3 * D, device=self.dev, dtype=torch.bfloat16) for _ in range(cfg.n_layer)]
+        self.part = torch.empty(self.C.attention_decode_shared_part_floats(self.prompts, self.N, H, D // H, self.tmax,
+                                                                           town), device=self.dev, dtype=torch.float32)
+        self.town = town
+
+    def cache_nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.caches + self.own)
+
+    def prefill(self, idx, last=None):
+        """Prefill the B prompts idx [B, T] once into ``caches`` and set ``logits`` [R, V] to each prompt's
+        last-position logits N times over: the first pick sees R rows, each with its own row index."""
+        x = self._prompt(idx, self._keep)[:, -1]
+        full = self._head(x.contiguous(), "mfma")
+        self.plen.fill_(idx.size(1))
+        self.logits = full.repeat_interleave(self.N, dim=0)[:, :self.model.config.vocab_size]
+        return self.logits
+
+
 _I64_MIN = -(1 << 63)
 
 
@@ -1104,7 +1172,7 @@ def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
 
 
 _STATE_SLOTS = ("_mg_decode_cache", "_mg_kv8_cache", "_mg_beam_cache", "_mg_beam_kv8_cache", "_mg_spec_cache",
-                "_mg_spec_kv8_cache")
+                "_mg_spec_kv8_cache", "_mg_shared_cache")
 # the bf16 slot of each kind of state and the KV8 slot kept beside it
 _KV8_SLOTS = {"_mg_decode_cache": "_mg_kv8_cache", "_mg_beam_cache": "_mg_beam_kv8_cache",
               "_mg_spec_cache": "_mg_spec_kv8_cache"}
@@ -1122,7 +1190,8 @@ def _kv_slot(who, kv_cache, slot="_mg_decode_cache"):
 def kv_cache_nbytes(model):
     """{state slot: bytes of its KV cache tensors} for every decode state ``model`` keeps: ``_mg_decode_cache``
     (bf16 qkv rows, 6 D bytes per token and layer), ``_mg_kv8_cache`` (``kv_cache="int8"``: 2 D + 8 H bytes),
-    ``_mg_beam_cache``, ``_mg_spec_cache`` and their KV8 states ``_mg_beam_kv8_cache``, ``_mg_spec_kv8_cache``."""
+    ``_mg_beam_cache``, ``_mg_spec_cache`` and their KV8 states ``_mg_beam_kv8_cache``, ``_mg_spec_kv8_cache``, and
+    ``_mg_shared_cache`` (``num_return_sequences``: B prompts' rows once plus R * Town rows of the continuations)."""
     return {slot: model.__dict__[slot].cache_nbytes() for slot in _STATE_SLOTS if model.__dict__.get(slot) is not None}
 
 
@@ -1168,6 +1237,35 @@ def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
     return c
 
 
+# ``num_return_sequences``: the shared-prefix state only where it measured no slower than the repeated
+# batch (PERF.md 'Shared prefix').  False takes the shared path wherever it applies (tests of the path, A/B)
+_SHARED_GATE = True
+_SHARED_ROWS_MAX = 64  # decode rows the skinny and the rows GEMM serve
+
+
+def _shared_pays(B, N, P):
+    """The measured rule (PERF.md 'Shared prefix'; GPT-2 124M and gpt2-xl, B = 1, N in {2, 8, 16, 64}, P in
+    {16, 128, 896}, 128 new tokens): N = 64, or N >= 16 on a prompt of at least 128 tokens -- every measured
+    case there decodes faster than the repeated batch (1.05x to 2.07x) with a faster first token.  Slower
+    outside it: N = 2 and N = 8 at every P on GPT-2 124M (0.78x to 1.00x; three launches per layer instead of
+    one, on rows that are few enough for the plain kernel) and N = 16 at P = 16 (0.96x).  B > 1 was not
+    measured and goes by the same N and P."""
+    return not _SHARED_GATE or N >= 64 or (N >= 16 and P >= 128)
+
+
+def _shared_state_for(model, idx, tmax, N, new_tokens):
+    """The shared-prefix state the model keeps under ``_mg_shared_cache``, prefilled with the prompts ``idx``
+    [B, T] and with room for ``new_tokens`` new tokens per row -- or a new one when B, N, ``tmax`` or the
+    device differ.  A slot of its own: the plain states and their graphs are never touched."""
+    c = model.__dict__.get("_mg_shared_cache")
+    if c is None or (c.prompts, c.N, c.tmax, c.dev) != (idx.size(0), N, tmax, idx.device):
+        c = model.__dict__["_mg_shared_cache"] = _SharedCache(model, idx, tmax, N, new_tokens)
+    else:
+        c.room(new_tokens)
+        c.prefill(idx)
+    return c
+
+
 def _replay(run, n, flags, eos_token):
     """``run(k)`` for n captured steps in all; returns the steps taken.  With a stop token (without
     one nothing finishes early) and ``_EARLY_EXIT`` the device's finished ``flags`` are read every
@@ -1205,8 +1303,24 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
              top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
              top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
              presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
-             kv_cache: str = "bf16", reuse_cache: bool = False):
-    """``reuse_cache``: prefix reuse on the GPU.  The decode state the model keeps between calls records
+             kv_cache: str = "bf16", reuse_cache: bool = False, num_return_sequences: int = 1):
+    """``num_return_sequences`` = N >= 1 (ValueError below 1): N continuations of every prompt.  The result
+    has B * N rows, rows b * N .. b * N + N - 1 the continuations of prompt b (with ``return_logprobs`` both
+    tensors), and is by definition what ``generate(idx.repeat_interleave(N, 0), ...)`` returns with every
+    other argument equal: the seeded sampler hashes the batch row b * N + j into the draw, so the rows of
+    one prompt diverge on their own, and greedy gives N equal rows.  N = 1 is the call without the
+    argument.  On the GPU device loops (``use_cache``, greedy or seeded) with ``kv_cache="bf16"``,
+    ``reuse_cache`` off, prompt + ``max_new_tokens`` <= ``block_size`` and B * N <= 64, a state of its own
+    (``_mg_shared_cache``, ``_SharedCache``) prefills each prompt once, keeps its K/V once and decodes the B * N
+    rows with ``attention_decode_shared``, which reads a prompt's keys once per (prompt, head) for all N
+    queries -- where that measured no slower than the repeated batch (``_shared_pays``; PERF.md 'Shared
+    prefix').  Everywhere else -- the CPU, ``use_cache=False``, ``seed=None``, the int8 cache, ``reuse_cache``, a
+    call past one context window -- the repeated batch is what runs, exactly.  On the shared path it is the
+    same model on another attention kernel and a B-row prefill: logits differ in the last bf16 bits and
+    a token may differ only at a near-tie.  ``generate_batch``, ``generate_beam``,
+    ``generate_speculative`` and ``score`` do not take it.
+
+    ``reuse_cache``: prefix reuse on the GPU.  The decode state the model keeps between calls records
     which tokens its KV cache holds; when this call's prompt starts with P >= 1 of them (in every row of
     the batch) and the shapes are ones where it measured faster (``_reuse_pays``: B * Tq <= 64 new rows, or
     B * P >= 2048 rows saved), only the tokens behind that prefix are run -- ``attention_extend`` attends the chunk to
@@ -1262,6 +1376,9 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     (``_GpuCache.sample``).  ``seed=None`` leaves every path as it was."""
     bs = model.block_size
     slot, kv8 = _kv_slot("generate", kv_cache)
+    N = int(num_return_sequences)
+    if N < 1:
+        raise ValueError(f"generate: num_return_sequences must be >= 1, got {num_return_sequences}")
     if kv8 and not use_cache:
         raise ValueError("generate: kv_cache='int8' needs use_cache=True (without a cache there is nothing to "
                          "quantize)")
@@ -1276,6 +1393,11 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     if seeded:
         seed = int(seed) & ((1 << 64) - 1)
     on_device = idx.is_cuda and use_cache and max_new_tokens > 0 and (seeded or not do_sample)  # the device loops
+    # N continuations per prompt: the shared-prefix state where it applies and pays, else the repeated batch
+    shared = (N > 1 and on_device and not kv8 and not reuse_cache and idx.size(1) + max_new_tokens <= bs
+              and idx.size(0) * N <= _SHARED_ROWS_MAX and _shared_pays(idx.size(0), N, idx.size(1)))
+    if N > 1 and not shared:
+        idx = idx.repeat_interleave(N, dim=0)
     proc, pwords = _processors("generate", model, on_device, repetition_penalty, presence_penalty,
                                frequency_penalty, no_repeat_ngram_size)
 
@@ -1320,7 +1442,8 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         else:
             first = lambda c, T, ctx: c.logits.argmax(-1)
             loop = lambda c, tok, L, n, T, ctx: c.greedy(tok, L, n, logprobs=return_logprobs, proc=pwords, ctx=ctx)
-        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords, slot, reuse)
+        return _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, return_logprobs, pwords, slot, reuse,
+                                      N if shared else 1)
     cache = None
     for _ in range(max_new_tokens):
         T = idx.size(1)
@@ -1346,7 +1469,7 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
 
 
 def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=False, proc=None,
-                           slot="_mg_decode_cache", reuse=False):
+                           slot="_mg_decode_cache", reuse=False, shared=1):
     """Greedy or seeded decode on the GPU: one prefill per context window, whose logits give the
     window's first token ``first(cache, T, ctx)`` [B], then the device-side token loop ``loop(cache,
     tok, L, n, T, ctx)`` [B, n] (``_GpuCache.greedy`` / ``.sample``: n steps from token ``tok`` at
@@ -1359,11 +1482,14 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     log-probability from the prefill logits (``with_logprob``), ``loop`` returns a (tokens,
     log-probabilities) pair, and so does this.  ``slot``: the decode state's (``_kv_slot``).  ``reuse``
     (the whole call fits one window): the prefill may extend the cached prefix (``_state_for``), and the
-    state then records what its caches hold -- every token but the last one produced, which was never fed."""
+    state then records what its caches hold -- every token but the last one produced, which was never fed.
+    ``shared`` = N > 1 (``num_return_sequences``; the whole call fits one window): the result has B * N rows,
+    the window's state is the shared-prefix one (``_shared_state_for``: ``idx`` is prefilled once, on B rows)
+    and ``ctx`` is the repeated prompt."""
     bs = model.block_size
-    B, T0 = idx.shape
+    B, T0 = idx.size(0) * shared, idx.size(1)
     out = torch.empty(B, T0 + max_new_tokens, dtype=torch.long, device=idx.device)
-    out[:, :T0] = idx
+    out[:, :T0] = idx if shared == 1 else idx.repeat_interleave(shared, dim=0)
     outs = (out, torch.zeros(out.shape, dtype=torch.float32, device=idx.device)) if logprobs else (out,)
 
     def put(cols, vals):  # tokens, or with logprobs the (tokens, lp) pair, into columns ``cols``
@@ -1374,7 +1500,10 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
     while T < end:
         ctx = out[:, max(0, T - bs):T]
         L = ctx.size(1)
-        cache = _state_for(model, slot, ctx, bs, reuse=reuse)
+        if shared == 1:
+            cache = _state_for(model, slot, ctx, bs, reuse=reuse)
+        else:
+            cache = _shared_state_for(model, idx, bs, shared, max_new_tokens)
         if proc is not None:
             cache.process_prefill(ctx, proc)
         tok = first(cache, T, ctx)

@@ -221,7 +221,7 @@ class GPT(nn.Module):
                  top_k: Optional[int] = None, use_cache: bool = True, seed: Optional[int] = None,
                  top_p: Optional[float] = None, return_logprobs: bool = False, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
-                 kv_cache: str = "bf16", reuse_cache: bool = False):
+                 kv_cache: str = "bf16", reuse_cache: bool = False, num_return_sequences: int = 1):
         """Autoregressive decode (reference ``model.py:322-356``).  With ``use_cache`` the prompt is
         prefilled once and every new token attends to a KV cache (fixes D32: O(steps * T^2)).
         ``seed`` (with ``do_sample``): reproducible counter-based sampling that stays on the device
@@ -234,14 +234,17 @@ class GPT(nn.Module):
         model -- K and V vectors snapped to int8 times a power-of-two scale, an int8 cache on the GPU
         (``generation.generate``); needs ``use_cache``.  ``reuse_cache=True``: on the GPU a prompt that starts
         with the tokens the KV cache still holds from the last such call runs only the tokens behind them
-        (``attention_extend``); same model, logits equal to the last bf16 bits (``generation.generate``)."""
+        (``attention_extend``); same model, logits equal to the last bf16 bits (``generation.generate``).
+        ``num_return_sequences=N``: N continuations per prompt, B * N rows, what the call returns for
+        ``idx.repeat_interleave(N, 0)``; on the GPU the prompt may be prefilled and kept once for its N rows
+        (``attention_decode_shared``; the rule and its limits in ``generation.generate``)."""
         from .generation import generate
 
         return generate(self, idx, max_new_tokens, temperature=temperature, do_sample=do_sample,
                         top_k=top_k, use_cache=use_cache, seed=seed, top_p=top_p, return_logprobs=return_logprobs,
                         repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                         frequency_penalty=frequency_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                        kv_cache=kv_cache, reuse_cache=reuse_cache)
+                        kv_cache=kv_cache, reuse_cache=reuse_cache, num_return_sequences=num_return_sequences)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens: int, temperature: float = 1.0, do_sample: bool = False,
