@@ -9,7 +9,8 @@ quantities per path, medians with ranges: ``ttft_ms``, the time of a call for on
 pick), and ``tok_s``, the N * (--new - 1) tokens of the decode loop over the time a call for --new tokens
 takes beyond that.  ``cache_bytes`` is ``kv_cache_nbytes`` of each path's state, ``same_rows`` the share of
 rows whose tokens equal the repeated batch's (they may part at a near-tie).  One JSON line per case.  A GPU is
-required."""
+required.  ``--kv-int8``: both arms with ``kv_cache="int8"`` -- the shared KV8 state (``_SHARED_KV8_GATE`` off
+as well, ``attention_decode_shared_kv8``) against the repeated batch on the plain KV8 state."""
 import argparse
 import gc
 import json
@@ -43,11 +44,13 @@ def main(argv=None):
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--kv-int8", action="store_true", help="kv_cache='int8' on both arms")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_shared_prefix: needs a GPU")
-    generation._SHARED_GATE = False
-    kw = dict(do_sample=True, seed=1234, top_k=50)
+    generation._SHARED_GATE = generation._SHARED_KV8_GATE = False
+    kw = dict(do_sample=True, seed=1234, top_k=50, **({"kv_cache": "int8"} if a.kv_int8 else {}))
+    slots = ("_mg_shared_kv8_cache", "_mg_kv8_cache") if a.kv_int8 else ("_mg_shared_cache", "_mg_decode_cache")
     med = statistics.median
     for mt in a.model_types.split(","):
         torch.manual_seed(0)
@@ -71,14 +74,14 @@ def main(argv=None):
                 nbytes = generation.kv_cache_nbytes(model)
                 rng = lambda v, d: [round(min(v), d), round(max(v), d)]
                 print(json.dumps({
-                    "bench": "shared_prefix", "model": mt, "N": N, "P": P, "new": a.new,
+                    "bench": "shared_prefix", "kv_cache": kw.get("kv_cache", "bf16"), "model": mt, "N": N, "P": P, "new": a.new,
                     **{f"{k}_ttft_ms": round(med(ttft[k]), 3) for k in run},
                     **{f"{k}_ttft_range_ms": rng(ttft[k], 3) for k in run},
                     **{f"{k}_tok_s": round(med(loop[k]), 1) for k in run},
                     **{f"{k}_tok_s_range": rng(loop[k], 1) for k in run},
                     "ttft_speedup": round(med(ttft["repeated"]) / med(ttft["shared"]), 3),
                     "loop_speedup": round(med(loop["shared"]) / med(loop["repeated"]), 3),
-                    "cache_bytes": {"shared": nbytes["_mg_shared_cache"], "repeated": nbytes["_mg_decode_cache"]},
+                    "cache_bytes": {"shared": nbytes[slots[0]], "repeated": nbytes[slots[1]]},
                     "same_rows": round(float((toks["shared"] == toks["repeated"]).all(1).float().mean()), 3)}),
                     flush=True)
         del model

@@ -810,6 +810,52 @@ void kv8_store(const at::Tensor& qkv, int64_t H, const c10::optional<at::Tensor>
                 (int)H, (int)(D / H), Tmax, cur_stream(), (int)rep);
 }
 
+// attention_decode_shared on the int8 cache (kernels.h): pre_q / pre_s of B prompts, own_q / own_s of R = B * N
+// rows (appended to at pos - P); the other arguments and the returned out [R, D] as attention_decode_shared's
+at::Tensor attention_decode_shared_kv8(const at::Tensor& qkv_new, const at::Tensor& pre_q, const at::Tensor& pre_s,
+                                       const at::Tensor& own_q, const at::Tensor& own_s, int64_t H, int64_t N,
+                                       const at::Tensor& pos_dev, const at::Tensor& plen_dev,
+                                       const c10::optional<at::Tensor>& part) {
+  const char* op = "attention_decode_shared_kv8";
+  CHECK_BF16(qkv_new); CHECK_CONTIG(qkv_new);
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) % 3 == 0, op, ": qkv_new must be [R, 3D]");
+  const int64_t R = qkv_new.size(0), D = qkv_new.size(1) / 3;
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              op, ": head dim must be a multiple of 8, at most 128");
+  const int64_t hd = D / H;
+  TORCH_CHECK(N >= 1 && N <= 64 && R >= 1 && R % N == 0 && R <= 4096,
+              op, ": N in 1..64 rows per prompt of pre_q, R = B * N rows");
+  const int64_t B = R / N;
+  kv8_cache_args(op, pre_q, pre_s, B, H, hd);
+  kv8_cache_args(op, own_q, own_s, R, H, hd);
+  const int64_t Tpre = pre_q.size(3), Town = own_q.size(3);
+  TORCH_CHECK(pre_q.device() == qkv_new.device() && own_q.device() == qkv_new.device(),
+              op, ": tensors on different devices");
+  TORCH_CHECK(Tpre >= 1 && Town >= 1 && Tpre <= (1 << 20) && Town <= (1 << 20) && B * H <= 65535,
+              op, ": cache too long or batch too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, op, ": tensors must be 16-byte aligned");
+  for (const at::Tensor* t : {&pos_dev, &plen_dev})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_cuda() && t->is_contiguous() && t->numel() >= 1 &&
+                t->device() == qkv_new.device(), op, ": pos_dev / plen_dev must be int32 [1] on the device");
+  DevGuard g(qkv_new.device());
+  auto out = at::empty({R, D}, qkv_new.options());
+  const int64_t np = (int64_t)mg::attention_decode_shared_part_floats((int)B, (int)N, (int)H, (int)hd, (int)Tpre,
+                                                                      (int)Town);
+  at::Tensor pt;
+  if (part.has_value() && part->defined()) {
+    CHECK_F32(*part);
+    TORCH_CHECK(part->numel() >= np && part->device() == qkv_new.device() && part->is_contiguous() &&
+                reinterpret_cast<uintptr_t>(part->data_ptr()) % 16 == 0, op, ": part workspace too small");
+    pt = *part;
+  } else {
+    pt = at::empty({np}, qkv_new.options().dtype(at::kFloat));
+  }
+  mg::attention_decode_shared_kv8(bp(qkv_new), pre_q.data_ptr<int8_t>(), fp(pre_s), own_q.data_ptr<int8_t>(), fp(own_s),
+                                  bp(out), fp(pt), (int)R, (int)N, (int)H, (int)hd, (int)Tpre, (int)Town,
+                                  pos_dev.data_ptr<int>(), plen_dev.data_ptr<int>(), cur_stream());
+  return out;
+}
+
 // attention_decode on the int8 cache: pos / pos_dev / part / counters / pos_stride / group as there (group =
 // K: kq / ks of B sequences, qkv_new [B * K, 3D], pos_dev int32 [B * K], the workspace for B * K rows)
 at::Tensor attention_decode_kv8(const at::Tensor& qkv_new, const at::Tensor& kq, const at::Tensor& ks, int64_t H,
@@ -1470,6 +1516,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("attention_decode_shared", &attention_decode_shared, py::arg("qkv_new"), py::arg("pre"), py::arg("own"),
         py::arg("H"), py::arg("N"), py::arg("pos_dev"), py::arg("plen_dev"), py::arg("part") = py::none());
+  m.def("attention_decode_shared_kv8", &attention_decode_shared_kv8, py::arg("qkv_new"), py::arg("pre_q"),
+        py::arg("pre_s"), py::arg("own_q"), py::arg("own_s"), py::arg("H"), py::arg("N"), py::arg("pos_dev"),
+        py::arg("plen_dev"), py::arg("part") = py::none());
   m.def("attention_decode_shared_part_floats", [](int64_t B, int64_t N, int64_t H, int64_t hd, int64_t Tpre, int64_t Town) {
     return (int64_t)mg::attention_decode_shared_part_floats((int)B, (int)N, (int)H, (int)hd, (int)Tpre, (int)Town);
   });

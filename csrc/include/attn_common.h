@@ -68,7 +68,7 @@ inline uint32_t mix32_host(uint32_t x) {
 // ------------------------------------------------------------------------------- forward
 // buffer descriptor over [base + off, base + total): reads past the end return 0.  The inputs are
 // readfirstlane'd so the compiler sees a uniform descriptor (no waterfall loop per load).
-MG_DEVICE __amdgpu_buffer_rsrc_t kv_rsrc(const bf16_t* base, uint64_t total, uint64_t off) {
+MG_DEVICE __amdgpu_buffer_rsrc_t kv_rsrc(const void* base, uint64_t total, uint64_t off) {
   const uint64_t p = reinterpret_cast<uint64_t>(base) + off;
   const uint64_t left = off < total ? total - off : 0;
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);

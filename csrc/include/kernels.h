@@ -348,6 +348,20 @@ void kv8_store(bf16_t* qkv, int8_t* kq, float* ks, int B, int T, int H, int hd, 
 void attention_decode_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, int B, int H, int hd,
                           long Tmax, int pos, hipStream_t stream, float* part, unsigned* counters,
                           const int* pos_dev = nullptr, int pos_stride = 0, int group = 1);
+// attention_decode_shared on the int8 cache (attention_shared.hip): pre_q int8 [B, 2, H, Tpre, hd] / pre_s
+// fp32 [B, 2, H, Tpre] hold the prompts' keys 0 .. P - 1 (read only: kv8_store wrote them), own_q int8 [R, 2, H,
+// Town, hd] / own_s fp32 [R, 2, H, Town] the rows' own keys P .. pos - 1.  The rule's (q, s) of qkv_new's K/V
+// are appended at own_*[m, :, :, pos - P] (qkv_new itself is not modified) and out [R, D] is bit for bit
+// what attention_decode_shared writes for qkv_new with its K/V thirds snapped over bf16 pre / own holding
+// the dequantized rows.  The prefix launch dequantizes the int8 tiles into the bf16 LDS images of the
+// bf16 kernel (16-byte loads where hd % 16 == 0, else 8-byte) and runs its tile body; the own launch is
+// its own body on attention_decode_kv8's loads; the combine is the same kernel.  Splits, workspace
+// (attention_decode_shared_part_floats), lengths from device memory, the out-of-range rule (nothing is
+// appended, out is zero) and every limit: attention_decode_shared's.  Int8 bytes and scale words of pre
+// keys at or past P and own keys at or past pos - P are never read into a result (the scales may be NaN).
+void attention_decode_shared_kv8(const bf16_t* qkv_new, const int8_t* pre_q, const float* pre_s, int8_t* own_q,
+                                 float* own_s, bf16_t* out, float* part, int R, int N, int H, int hd, int Tpre,
+                                 int Town, const int* pos_dev, const int* plen_dev, hipStream_t stream);
 // beam_reorder on the int8 cache, in place over L layers (kq_layer / ks_layer elements apart): kq int8
 // [L, R, 2, H, Tmax, hd], ks fp32 [L, R, 2, H, Tmax], R = B * W.  For every (K | V, head), positions t <
 // min(*pos, Tmax) of beam r of a prompt become those of beam parent[r] of the same prompt, int8 bytes

@@ -49,11 +49,24 @@
 //
 // Out of range (pos < P or pos - P >= Town): nothing is appended, every split is neutral and the
 // combine writes zero rows.
+//
+// KV8 (attention_decode_shared_kv8): the same launches on the int8 cache of kernels.h, pre_q / pre_s
+// [B, 2, H, Tpre, (hd)] and own_q / own_s [R, 2, H, Town, (hd)].  Only the loads differ.  Prefix: a 64-key
+// tile of one (b, K | V, h) plane is 64 * hd contiguous bytes plus 64 scale words (half the bf16 tile's
+// bytes, no strided rows); a wave loads them with 16-byte loads (hd % 16 == 0; KV = 16) or 8-byte loads
+// (KV = 8), dequantizes float(q) * s in registers -- exact, the bf16 value the snapped row holds -- and
+// writes the LDS images the bf16 staging writes, so shr_tile, the key walk, the fold and the partials
+// are this file's one copy.  No tile is prefetched under another here either: not measured.  With hd >
+// 64 and N > 32 the two query fragments run as two workgroups (no instantiation uses scratch).  Own:
+// attention_decode_kv8's loads and its snap of the step's K/V in LDS; the first own split appends the
+// rule's (q, s).  out equals the bf16 kernels on the dequantized rows bit for bit.
 #include "attn_common.h"
 #include "kernels.h"
+#include "kv8_common.h"
 
 using namespace mg;
 using namespace mg::attn;
+using namespace mg::kv8;
 
 namespace {
 
@@ -64,6 +77,11 @@ struct ShrArgs {
   const bf16_t* qkv_new;  // [R, 3D]
   const bf16_t* pre;      // [B, Tpre, 3D]
   bf16_t* own;            // [R, Town, 3D]
+  // KV8 (attention_decode_shared_kv8): the int8 caches in place of pre / own
+  const int8_t* pre_q;    // [B, 2, H, Tpre, hd]
+  const float* pre_s;     // [B, 2, H, Tpre]
+  int8_t* own_q;          // [R, 2, H, Town, hd]
+  float* own_s;           // [R, 2, H, Town]
   bf16_t* out;            // [R, D]
   float* part_ml;         // [B * H][St][N][2] {m, l}
   float* part_o;          // [B * H][St][N][hd]
@@ -168,7 +186,9 @@ MG_DEVICE void shr_tile(const char* sk, const char* sv, const int (&ko)[NKS], co
     }
 }
 
-template <int NKS, int NF>
+// KV = 0: bf16 qkv rows (pre).  KV = 16 / 8: the int8 cache (pre_q / pre_s), staged with 16-byte loads
+// (hd % 16 == 0) or 8-byte loads -- the KV8 staging in the file header.
+template <int NKS, int NF, int KV>
 __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_prefix_kernel(const ShrArgs a) {
   constexpr int NH = (NKS + 3) / 4;   // 64-column halves of the LDS images
   constexpr int NO = (NKS + 1) / 2;   // 32-column O^T accumulator tiles
@@ -224,6 +244,76 @@ __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_
     }
   };
 
+  // KV8 staging.  The 64 keys of a tile of one (b, K | V, h) plane are 64 * hd contiguous int8 bytes and
+  // 64 contiguous scale words.  Load c of a lane is the plane's bytes [(lane + 64 c) * CB, + CB) of the
+  // tile: cpr = hd / CB loads per lane and matrix, the same count in every lane, each instruction one
+  // contiguous 64 * CB bytes.  Lane l also loads the scale of key l, and the scale of a chunk's key row
+  // comes from that lane (ds_bpermute).  The chunk is dequantized in registers -- float(q) * s is exact
+  // and IS the bf16 value of the snapped row, a NaN scale makes the vector NaN -- packed to bf16 and
+  // written as the one or two 16-byte chunks of the swizzled image the bf16 staging writes.  Both planes
+  // are read through descriptors that end at key P: past it bytes and scale read as 0 and 0 x 0 = 0.
+  // The loads never touch columns at or past hd, so those image columns are zeroed once, before the
+  // first tile (zero_pad).
+  constexpr int CB = KV ? KV : 16;     // bytes per load
+  constexpr int NL = NKS * 16 / CB;    // loads per lane and matrix at most
+  typedef uint32_t kv8_chunk __attribute__((ext_vector_type(CB / 4)));
+  const int cpr = a.hd / CB;
+  uint32_t qdst[NL];                   // image offset of the chunk's first 8 columns; key row = bits 7..12
+#pragma unroll
+  for (int c = 0; c < NL; ++c) {
+    const int idx = lane + 64 * c, row = min(idx / max(cpr, 1), 63), col = (idx % max(cpr, 1)) * CB;
+    qdst[c] = (col >> 6) * HALF + lds_off(row, (col >> 3) & 7);
+  }
+  const long plane = ((long)b * 2 * a.H + hh) * a.Tpre;   // K; V is H * Tpre keys behind it
+  const long vplane = (long)a.H * a.Tpre;
+  auto kv8_chunk_store = [&](char* img, uint32_t dst, const kv8_chunk& u, float sc) {
+    float f[8];
+    dequant8(make_uint2(u[0], u[1]), sc, f);
+    *reinterpret_cast<uint4*>(img + dst) = pack8(f);
+    if constexpr (CB == 16) {  // columns 8 .. 15 of the chunk: the neighbouring image chunk
+      dequant8(make_uint2(u[2], u[3]), sc, f);
+      *reinterpret_cast<uint4*>(img + (dst ^ 16)) = pack8(f);
+    }
+  };
+  auto stage_kv8 = [&](int k0) {
+    const uint64_t qbytes = (uint64_t)P * a.hd, qoff = (uint64_t)k0 * a.hd;
+    const __amdgpu_buffer_rsrc_t dk = kv_rsrc(a.pre_q + plane * a.hd, qbytes, qoff);
+    const __amdgpu_buffer_rsrc_t dv = kv_rsrc(a.pre_q + (plane + vplane) * a.hd, qbytes, qoff);
+    const __amdgpu_buffer_rsrc_t dsk = kv_rsrc(a.pre_s + plane, (uint64_t)P * 4, (uint64_t)k0 * 4);
+    const __amdgpu_buffer_rsrc_t dsv = kv_rsrc(a.pre_s + plane + vplane, (uint64_t)P * 4, (uint64_t)k0 * 4);
+    kv8_chunk rk[NL], rv[NL];
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+      if (c < cpr) {
+        const uint32_t off = (uint32_t)(lane + 64 * c) * CB;
+        if constexpr (CB == 16) {
+          rk[c] = __builtin_bit_cast(kv8_chunk, __builtin_amdgcn_raw_buffer_load_b128(dk, off, 0, 0));
+          rv[c] = __builtin_bit_cast(kv8_chunk, __builtin_amdgcn_raw_buffer_load_b128(dv, off, 0, 0));
+        } else {
+          rk[c] = __builtin_bit_cast(kv8_chunk, __builtin_amdgcn_raw_buffer_load_b64(dk, off, 0, 0));
+          rv[c] = __builtin_bit_cast(kv8_chunk, __builtin_amdgcn_raw_buffer_load_b64(dv, off, 0, 0));
+        }
+      }
+    }
+    const float sk = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsk, lane * 4, 0, 0));
+    const float sv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsv, lane * 4, 0, 0));
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+      if (c < cpr) {
+        const int row = (qdst[c] >> 7) & 63;
+        kv8_chunk_store(mine, qdst[c], rk[c], __shfl(sk, row, 64));
+        kv8_chunk_store(mine + TILE, qdst[c], rv[c], __shfl(sv, row, 64));
+      }
+    }
+  };
+  if constexpr (KV != 0) {
+    // image columns hd .. 32 NO - 1 (K fragments read below 16 NKS, V^T fragments below 32 NO): never
+    // staged, so zero this wave's two images once
+    if (a.hd < 32 * NO) {
+      for (int i = lane * 16; i < 2 * TILE; i += 64 * 16) *reinterpret_cast<uint4*>(mine + i) = make_uint4(0, 0, 0, 0);
+    }
+  }
+
   // per-lane fragment offsets (as in the extend kernel): K rows l32 (+32 per sub), chunk 2 ks + h32;
   // V^T transposed reads rows 4 h32 + q (+8), columns (n & 1) * 32 + cb + 4 p
   int ko[NKS];
@@ -235,12 +325,14 @@ __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_
 
   // this lane's queries: slot 32 f + l32 of the group, row b * N + slot; a lane past N holds a zero
   // query and stores nothing
+  // KV8 with hd > 64 and N > 32 runs its two fragments as two workgroups of one (blockIdx.z; launch_prefix)
+  const int f0 = KV != 0 ? blockIdx.z : 0;
   bf16x8 qf[NF][NKS];
   f32x16 o[NF][NO], negm[NF];
   float m[NF], l[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    const int j = 32 * f + l32;
+    const int j = 32 * (f + f0) + l32;
     const bf16_t* qrow = a.qkv_new + ((long)b * a.N + min(j, a.N - 1)) * ld + hh * a.hd;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
@@ -266,9 +358,13 @@ __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_
   for (int it = 0; it < niter; ++it, t += 4) {
     const bool have = t < t1;
     if (have) {
-      uint4 rk[NC], rv[NC];
-      load_tile(rk, rv, t * 64);
-      store_tile(rk, rv);
+      if constexpr (KV != 0) {
+        stage_kv8(t * 64);
+      } else {
+        uint4 rk[NC], rv[NC];
+        load_tile(rk, rv, t * 64);
+        store_tile(rk, rv);
+      }
     }
     __syncthreads();
     if (have) {
@@ -331,7 +427,7 @@ __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_
   // the split's partial of every row of the group (neutral when the split has no tile: m = -big)
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    const int j = 32 * f + l32;
+    const int j = 32 * (f + f0) + l32;
     if (j >= a.N) continue;
     const long slot = ((long)bh * a.St + sp) * a.N + j;
     if (h32 == 0) *reinterpret_cast<float2*>(a.part_ml + 2 * slot) = make_float2(m[f], lt[f]);
@@ -351,11 +447,20 @@ __global__ __launch_bounds__(256, (NKS > 4 || NF > 1) ? 1 : 2) void attn_shared_
 // The private keys of row m, head hh, own split so: indices [so * 256, ..) of the row's `no` =
 // pos - P + 1 own keys, the last of which (key pos) is qkv_new's.  The plain decode kernel's body: a
 // key per thread for the scores, then P V over key groups of hd / 8 lanes.
+// KV8: the own keys come from own_q / own_s through attention_decode_kv8's loads (8 or 16 bytes of int8
+// and one scale per key, dequantized to the floats the bf16 row holds); the step's K/V are snapped by
+// the KV8 rule into LDS by every own split (key pos is read from there, never from the cache) and their
+// (q, s) are appended at own row pos - P by the row's first own split.  The sums are the bf16
+// instantiation's statements, element for element.
+template <bool KV8>
 __global__ __launch_bounds__(256) void attn_shared_own_kernel(const ShrArgs a) {
   __shared__ float qs[128];
   __shared__ float sc[256];
   __shared__ float red[16];
   __shared__ float acc[256 * 8];
+  __shared__ float vs[KV8 ? 256 : 1];     // KV8: the V scale of the split's key t
+  __shared__ float nkv[KV8 ? 256 : 1];    // KV8: the step's snapped K [0, 128) and V [128, 256) of this head
+  __shared__ uint32_t cm[KV8 ? 32 : 1];
   const int row = blockIdx.x / a.H, hh = blockIdx.x % a.H, so = blockIdx.y;
   const int b = row / a.N, j = row % a.N;
   const int hd = a.hd, D = a.D;
@@ -374,25 +479,89 @@ __global__ __launch_bounds__(256) void attn_shared_own_kernel(const ShrArgs a) {
     return;
   }
   const bf16_t* qrow = a.qkv_new + (long)row * ld + hh * hd;
-  bf16_t* orows = a.own + (long)row * a.Town * ld;
-  if (so == 0 && threadIdx.x < (hd >> 2)) {  // append K and V at own row pos - P, 16 bytes a thread
-    const int which = threadIdx.x / (hd >> 3), c = threadIdx.x % (hd >> 3);
-    st16(orows + (long)(pos - P) * ld + (long)D * (1 + which) + hh * hd + 8 * c, ld16(qrow + (long)D * (1 + which) + 8 * c));
+  bf16_t* orows = KV8 ? nullptr : a.own + (long)row * a.Town * ld;
+  const int dch = hd >> 3;
+  // KV8: this row's K and V planes of the head in own_q (bytes: * hd) and own_s
+  const long rowk = ((long)row * 2 * a.H + hh) * a.Town, rowv = rowk + (long)a.H * a.Town;
+  uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+  const int which = threadIdx.x / dch, c8 = threadIdx.x % dch;  // threads below 2 dch: K | V, 16-byte chunk
+  if constexpr (KV8) {
+    if (threadIdx.x < 2 * dch) {
+      raw = ld16(qrow + (long)D * (1 + which) + 8 * c8);
+      cm[threadIdx.x] = max_abs8(raw);
+    }
+  } else {
+    if (so == 0 && threadIdx.x < (hd >> 2)) {  // append K and V at own row pos - P, 16 bytes a thread
+      st16(orows + (long)(pos - P) * ld + (long)D * (1 + which) + hh * hd + 8 * c8, ld16(qrow + (long)D * (1 + which) + 8 * c8));
+    }
   }
   for (int d = threadIdx.x; d < hd; d += 256) qs[d] = bf2f(qrow[d]);
   __syncthreads();
+  if constexpr (KV8) {
+    if (threadIdx.x < 2 * dch) {  // snap the step's K/V into LDS; the first own split appends their (q, s)
+      uint32_t a15 = 0;
+      for (int i = 0; i < dch; ++i) a15 = max(a15, cm[which * dch + i]);
+      int ex;
+      bool live;
+      const float sn = kv8_scale(a15, ex, live);
+      float f[8];
+      const uint2 q8 = kv8_quant8(raw, ex, live, sn, f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) nkv[which * 128 + c8 * 8 + e] = f[e];
+      if (so == 0) {
+        const long r = (which ? rowv : rowk) + (pos - P);
+        *reinterpret_cast<uint2*>(a.own_q + r * hd + c8 * 8) = q8;
+        if (c8 == 0) a.own_s[r] = sn;
+      }
+    }
+    __syncthreads();
+  }
   auto kv_row = [&](int i) {  // K columns of own key i of this head (V: + D)
     return i == no - 1 ? qrow + D : orows + (long)i * ld + D + hh * hd;
   };
   float s = -INFINITY;
   if (threadIdx.x < nk) {
-    const bf16_t* kr = kv_row(k0 + threadIdx.x);
     float dot = 0.f;
-    for (int d = 0; d < hd; d += 8) {
-      float k8[8];
-      unpack8(ld16(kr + d), k8);
+    auto dot8 = [&](int d, const float (&k8)[8]) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) dot += qs[d + e] * k8[e];
+    };
+    if constexpr (KV8) {
+      const int i = k0 + threadIdx.x;
+      float k8[8];
+      if (i == no - 1) {
+        vs[threadIdx.x] = 0.f;
+        for (int d = 0; d < hd; d += 8) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) k8[e] = nkv[d + e];
+          dot8(d, k8);
+        }
+      } else {
+        const float sk = a.own_s[rowk + i];
+        vs[threadIdx.x] = a.own_s[rowv + i];
+        const int8_t* kr = a.own_q + (rowk + i) * hd;
+        if ((hd & 15) == 0) {
+          for (int d = 0; d < hd; d += 16) {
+            const uint4 u = ld16(kr + d);
+            dequant8(make_uint2(u.x, u.y), sk, k8);
+            dot8(d, k8);
+            dequant8(make_uint2(u.z, u.w), sk, k8);
+            dot8(d + 8, k8);
+          }
+        } else {
+          for (int d = 0; d < hd; d += 8) {
+            dequant8(*reinterpret_cast<const uint2*>(kr + d), sk, k8);
+            dot8(d, k8);
+          }
+        }
+      }
+    } else {
+      const bf16_t* kr = kv_row(k0 + threadIdx.x);
+      for (int d = 0; d < hd; d += 8) {
+        float k8[8];
+        unpack8(ld16(kr + d), k8);
+        dot8(d, k8);
+      }
     }
     s = dot * a.scale_log2;
   }
@@ -401,14 +570,22 @@ __global__ __launch_bounds__(256) void attn_shared_own_kernel(const ShrArgs a) {
   sc[threadIdx.x] = p;
   const float sm = block_sum<4>(p, red + 4);
   __syncthreads();
-  const int dch = hd >> 3;
   const int ngrp = 256 / dch;
   const int grp = threadIdx.x / dch, d8 = (threadIdx.x % dch) * 8;
   float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (grp < ngrp) {
     for (int jj = grp; jj < nk; jj += ngrp) {
       float v8[8];
-      unpack8(ld16(kv_row(k0 + jj) + D + d8), v8);
+      if constexpr (KV8) {
+        if (k0 + jj == no - 1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v8[e] = nkv[128 + d8 + e];
+        } else {
+          dequant8(*reinterpret_cast<const uint2*>(a.own_q + (rowv + k0 + jj) * hd + d8), vs[jj], v8);
+        }
+      } else {
+        unpack8(ld16(kv_row(k0 + jj) + D + d8), v8);
+      }
       const float pj = sc[jj];
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += pj * v8[e];
@@ -486,11 +663,51 @@ int shr_prefix_splits(int B, int H, int Tpre) {
 // floats of the {m, l} region, rounded so that the O region behind it stays 16-byte aligned
 size_t shr_ml_floats(int B, int N, int H, int St) { return ((size_t)B * H * St * N * 2 + 3) & ~(size_t)3; }
 
-template <int NKS>
+template <int NKS, int KV>
 void launch_prefix(const ShrArgs& a, hipStream_t stream) {
   const dim3 grid(a.B * a.H, a.Sp);
-  if (a.N <= 32) attn_shared_prefix_kernel<NKS, 1><<<grid, 256, 0, stream>>>(a);
-  else attn_shared_prefix_kernel<NKS, 2><<<grid, 256, 0, stream>>>(a);
+  if (a.N <= 32) {
+    attn_shared_prefix_kernel<NKS, 1, KV><<<grid, 256, 0, stream>>>(a);
+  } else if constexpr (KV != 0 && NKS > 4) {
+    // two query fragments at hd > 64 need more than the 512 registers (the bf16 <8, 2> spills): one
+    // workgroup per fragment instead.  A row's bits do not depend on which fragment slot computes it
+    attn_shared_prefix_kernel<NKS, 1, KV><<<dim3(a.B * a.H, a.Sp, 2), 256, 0, stream>>>(a);
+  } else {
+    attn_shared_prefix_kernel<NKS, 2, KV><<<grid, 256, 0, stream>>>(a);
+  }
+}
+
+// the three launches of one call; kv: 0 (bf16 rows), 16 / 8 (int8 planes by the staging's load width)
+template <int KV>
+void launch_shared(const ShrArgs& a, hipStream_t stream) {
+  switch (nks_for(a.hd)) {
+    case 1: launch_prefix<1, KV>(a, stream); break;
+    case 2: launch_prefix<2, KV>(a, stream); break;
+    case 3: launch_prefix<3, KV>(a, stream); break;
+    case 4: launch_prefix<4, KV>(a, stream); break;
+    case 6: launch_prefix<6, KV>(a, stream); break;
+    default: launch_prefix<8, KV>(a, stream); break;
+  }
+  const int R = a.B * a.N;
+  attn_shared_own_kernel<KV != 0><<<dim3(R * a.H, a.So), 256, 0, stream>>>(a);
+  attn_shared_combine_kernel<<<cdiv((long)R * a.H * (a.hd >> 2), 256), 256, 0, stream>>>(a);
+}
+
+// the shapes, the split plan and the workspace layout: the same for both storage kinds
+ShrArgs shr_plan(const bf16_t* qkv_new, bf16_t* out, float* part, int R, int N, int H, int hd, int Tpre, int Town,
+                 const int* pos_dev, const int* plen_dev) {
+  ShrArgs a{};
+  a.qkv_new = qkv_new; a.out = out;
+  a.pos_dev = pos_dev; a.plen_dev = plen_dev;
+  a.B = R / N; a.N = N; a.H = H; a.hd = hd; a.D = H * hd; a.Tpre = Tpre; a.Town = Town;
+  a.Sp = mg::attention_decode_shared_splits(a.B, H, Tpre);
+  a.tps = cdiv(cdiv(Tpre, 64), a.Sp);
+  a.So = cdiv(Town, kShrOwnKeys);
+  a.St = a.Sp + a.So;
+  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
+  a.part_ml = part;
+  a.part_o = part + shr_ml_floats(a.B, N, H, a.St);
+  return a;
 }
 
 }  // namespace
@@ -510,27 +727,18 @@ size_t attention_decode_shared_part_floats(int B, int N, int H, int hd, int Tpre
 void attention_decode_shared(const bf16_t* qkv_new, const bf16_t* pre, bf16_t* own, bf16_t* out, float* part,
                              int R, int N, int H, int hd, int Tpre, int Town, const int* pos_dev,
                              const int* plen_dev, hipStream_t stream) {
-  ShrArgs a{};
-  a.qkv_new = qkv_new; a.pre = pre; a.own = own; a.out = out;
-  a.pos_dev = pos_dev; a.plen_dev = plen_dev;
-  a.B = R / N; a.N = N; a.H = H; a.hd = hd; a.D = H * hd; a.Tpre = Tpre; a.Town = Town;
-  a.Sp = attention_decode_shared_splits(a.B, H, Tpre);
-  a.tps = cdiv(cdiv(Tpre, 64), a.Sp);
-  a.So = cdiv(Town, kShrOwnKeys);
-  a.St = a.Sp + a.So;
-  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
-  a.part_ml = part;
-  a.part_o = part + shr_ml_floats(a.B, N, H, a.St);
-  switch (nks_for(hd)) {
-    case 1: launch_prefix<1>(a, stream); break;
-    case 2: launch_prefix<2>(a, stream); break;
-    case 3: launch_prefix<3>(a, stream); break;
-    case 4: launch_prefix<4>(a, stream); break;
-    case 6: launch_prefix<6>(a, stream); break;
-    default: launch_prefix<8>(a, stream); break;
-  }
-  attn_shared_own_kernel<<<dim3(R * H, a.So), 256, 0, stream>>>(a);
-  attn_shared_combine_kernel<<<cdiv((long)R * H * (hd >> 2), 256), 256, 0, stream>>>(a);
+  ShrArgs a = shr_plan(qkv_new, out, part, R, N, H, hd, Tpre, Town, pos_dev, plen_dev);
+  a.pre = pre; a.own = own;
+  launch_shared<0>(a, stream);
+}
+
+void attention_decode_shared_kv8(const bf16_t* qkv_new, const int8_t* pre_q, const float* pre_s, int8_t* own_q,
+                                 float* own_s, bf16_t* out, float* part, int R, int N, int H, int hd, int Tpre,
+                                 int Town, const int* pos_dev, const int* plen_dev, hipStream_t stream) {
+  ShrArgs a = shr_plan(qkv_new, out, part, R, N, H, hd, Tpre, Town, pos_dev, plen_dev);
+  a.pre_q = pre_q; a.pre_s = pre_s; a.own_q = own_q; a.own_s = own_s;
+  if (hd % 16 == 0) launch_shared<16>(a, stream);
+  else launch_shared<8>(a, stream);
 }
 
 }  // namespace mg

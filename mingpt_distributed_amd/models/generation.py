@@ -18,7 +18,8 @@ Layout of this file, top to bottom:
   ``kv_cache="int8"`` (the KV8 model on int8 caches): ``_mg_kv8_cache``, ``_mg_beam_kv8_cache`` and
   ``_mg_spec_kv8_cache``.
 * ``_SharedCache(_GpuCache)``: the state of ``generate(num_return_sequences=N)`` (``_mg_shared_cache``): the
-  prompts' K/V once, the B * N rows' own K/V beside them, ``attention_decode_shared`` in ``_decode``.
+  prompts' K/V once, the B * N rows' own K/V beside them, ``attention_decode_shared`` in ``_decode``; with
+  ``kv_cache="int8"`` ``_mg_shared_kv8_cache``, the same on int8 caches and ``attention_decode_shared_kv8``.
 * the word builders, ``_state_for``, then one section per entry point: checks, host loop, GPU half.
 
 Who owns what.  A loop in ``_loops`` owns its graph and, for the rectangular loops, its ``tok`` /
@@ -573,8 +574,17 @@ class _GpuCache(_Body):
                             pos_stride).view(B, D)
         if self.shared:  # N rows per prompt (_SharedCache): the prompt's K/V once, the rows' own beside them
             assert pos_stride == 0
-            attend = lambda i, qkv: C.attention_decode_shared(qkv, self.caches[i], self.own[i], H, self.N, pos,
-                                                              self.plen, self.part)
+            if self._kv8_on():
+                attend = lambda i, qkv: C.attention_decode_shared_kv8(qkv, self.kq[i], self.ks[i], self.own_q[i],
+                                                                      self.own_s[i], H, self.N, pos, self.plen,
+                                                                      self.part)
+            else:  # a KV8 state on the bf16 kernel snaps the step's K/V in place first
+
+                def attend(i, qkv):
+                    if self.kv8:
+                        C.kv8_store(qkv.view(B, 1, 3 * D), H)
+                    return C.attention_decode_shared(qkv, self.caches[i], self.own[i], H, self.N, pos, self.plen,
+                                                     self.part)
         elif self._kv8_on():
             attend = lambda i, qkv: C.attention_decode_kv8(qkv, self.kq[i], self.ks[i], H, hpos, pos, self.dec_part,
                                                            self.dec_cnt, pos_stride)
@@ -1065,22 +1075,24 @@ class _SharedCache(_GpuCache):
     3D] takes what each row generates; ``plen`` int32 [1] on the device is the prompt length, ``part`` the
     kernel's workspace.  ``_decode`` attends with ``attention_decode_shared``; every token loop of
     ``_GpuCache`` runs unchanged on the R rows.  ``Town`` is ``max_new_tokens`` rounded up to 64; a later
-    call that needs more reallocates ``own`` and drops the captured loops (``room``)."""
+    call that needs more reallocates ``own`` and drops the captured loops (``room``).
+
+    ``kv8`` (``kv_cache="int8"``, ``_mg_shared_kv8_cache``): the KV8 model.  With ``_KV8_DECODE`` on the
+    prompts' keys are ``kq[i]`` int8 [B, 2, H, tmax, hd] / ``ks[i]`` float32 [B, 2, H, tmax] (``kv8_store`` in the
+    prefill) and the rows' own ``own_q[i]`` [R, 2, H, Town, hd] / ``own_s[i]`` [R, 2, H, Town], read and appended
+    to by ``attention_decode_shared_kv8``; off, ``caches`` / ``own`` are bf16 rows holding snapped K/V and
+    the step snaps its row in place before ``attention_decode_shared`` -- the same bits."""
 
     shared = True
 
-    def __init__(self, model, idx, tmax, N, new_tokens):
+    def __init__(self, model, idx, tmax, N, new_tokens, kv8=False):
         _Body.__init__(self, model)
-        cfg = model.config
-        D, H = cfg.n_embed, cfg.n_head
         self.tmax, self.dev, self.N, self.prompts = tmax, idx.device, N, idx.size(0)
         self.B = self.prompts * N  # the decode rows: what the loops and ``_route`` go by
         self.kv = self.kqs = self.kss = self.held = None
-        self.kv8 = self.stacked = False
-        self.kq, self.ks = [], []
-        self.caches = [torch.empty(self.prompts, tmax, 3 * D, device=self.dev, dtype=torch.bfloat16)
-                       for _ in range(cfg.n_layer)]
-        self.own, self.town = [], 0
+        self.kv8, self.stacked = bool(kv8), False
+        self.caches, self.kq, self.ks = [], [], []
+        self.own, self.own_q, self.own_s, self.town = [], [], [], 0
         self.plen = torch.ones(1, dtype=torch.int32, device=self.dev)
         self.stamp = self._stamp()
         self._loops = {}
@@ -1090,8 +1102,32 @@ class _SharedCache(_GpuCache):
         self.room(new_tokens)
         self.prefill(idx)
 
+    def _kv8_storage(self):
+        """The caches of the kind the steps read now -- int8 pairs for a KV8 state with ``_KV8_DECODE`` on,
+        else bf16 qkv rows -- for the B prompts and, at ``town`` rows each, for the R decode rows.  What is
+        there and fits is kept; the other kind is freed (a flip of the switch; ``_stamp`` drops the loops)."""
+        cfg = self.model.config
+        D, H, L = cfg.n_embed, cfg.n_head, cfg.n_layer
+        new = lambda *shape, dtype: [torch.empty(*shape, device=self.dev, dtype=dtype) for _ in range(L)]
+        if self._kv8_on():
+            self.caches, self.own = [], []
+            if not self.kq:
+                self.kq = new(self.prompts, 2, H, self.tmax, D // H, dtype=torch.int8)
+                self.ks = new(self.prompts, 2, H, self.tmax, dtype=torch.float32)
+            if not self.own_q or self.own_q[0].size(3) != self.town:
+                self.own_q = self.own_s = None  # free the old rows before the new ones are allocated
+                self.own_q = new(self.B, 2, H, self.town, D // H, dtype=torch.int8)
+                self.own_s = new(self.B, 2, H, self.town, dtype=torch.float32)
+        else:
+            self.kq, self.ks, self.own_q, self.own_s = [], [], [], []
+            if not self.caches:
+                self.caches = new(self.prompts, self.tmax, 3 * D, dtype=torch.bfloat16)
+            if not self.own or self.own[0].size(1) != self.town:
+                self.own = None
+                self.own = new(self.B, self.town, 3 * D, dtype=torch.bfloat16)
+
     def room(self, new_tokens):
-        """``own`` rows for a call of ``new_tokens`` new tokens: the captured steps bake the buffers in, so
+        """Own rows for a call of ``new_tokens`` new tokens: the captured steps bake the buffers in, so
         growing them drops every loop."""
         town = (max(int(new_tokens), 1) + 63) // 64 * 64
         if town <= self.town:
@@ -1099,18 +1135,20 @@ class _SharedCache(_GpuCache):
         cfg = self.model.config
         D, H = cfg.n_embed, cfg.n_head
         self._loops.clear()
-        self.own = None  # free the old rows before the new ones are allocated
-        self.own = [torch.empty(self.B, town, 3 * D, device=self.dev, dtype=torch.bfloat16) for _ in range(cfg.n_layer)]
+        self.town = town
+        self._kv8_storage()
         self.part = torch.empty(self.C.attention_decode_shared_part_floats(self.prompts, self.N, H, D // H, self.tmax,
                                                                            town), device=self.dev, dtype=torch.float32)
-        self.town = town
 
     def cache_nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self.caches + self.own)
+        return sum(t.numel() * t.element_size()
+                   for t in self.caches + self.own + self.kq + self.ks + self.own_q + self.own_s)
 
     def prefill(self, idx, last=None):
-        """Prefill the B prompts idx [B, T] once into ``caches`` and set ``logits`` [R, V] to each prompt's
-        last-position logits N times over: the first pick sees R rows, each with its own row index."""
+        """Prefill the B prompts idx [B, T] once into ``caches`` (``kq`` / ``ks``) and set ``logits`` [R, V] to
+        each prompt's last-position logits N times over: the first pick sees R rows, each with its own row
+        index."""
+        self._kv8_storage()
         x = self._prompt(idx, self._keep)[:, -1]
         full = self._head(x.contiguous(), "mfma")
         self.plen.fill_(idx.size(1))
@@ -1172,7 +1210,7 @@ def _ragged_words(seed, temperature, top_k, eos_token, top_p=None):
 
 
 _STATE_SLOTS = ("_mg_decode_cache", "_mg_kv8_cache", "_mg_beam_cache", "_mg_beam_kv8_cache", "_mg_spec_cache",
-                "_mg_spec_kv8_cache", "_mg_shared_cache")
+                "_mg_spec_kv8_cache", "_mg_shared_cache", "_mg_shared_kv8_cache")
 # the bf16 slot of each kind of state and the KV8 slot kept beside it
 _KV8_SLOTS = {"_mg_decode_cache": "_mg_kv8_cache", "_mg_beam_cache": "_mg_beam_kv8_cache",
               "_mg_spec_cache": "_mg_spec_kv8_cache"}
@@ -1191,7 +1229,8 @@ def kv_cache_nbytes(model):
     """{state slot: bytes of its KV cache tensors} for every decode state ``model`` keeps: ``_mg_decode_cache``
     (bf16 qkv rows, 6 D bytes per token and layer), ``_mg_kv8_cache`` (``kv_cache="int8"``: 2 D + 8 H bytes),
     ``_mg_beam_cache``, ``_mg_spec_cache`` and their KV8 states ``_mg_beam_kv8_cache``, ``_mg_spec_kv8_cache``, and
-    ``_mg_shared_cache`` (``num_return_sequences``: B prompts' rows once plus R * Town rows of the continuations)."""
+    ``_mg_shared_cache`` (``num_return_sequences``: B prompts' rows once plus R * Town rows of the continuations)
+    and its KV8 state ``_mg_shared_kv8_cache`` (the same rows at 2 D + 8 H bytes)."""
     return {slot: model.__dict__[slot].cache_nbytes() for slot in _STATE_SLOTS if model.__dict__.get(slot) is not None}
 
 
@@ -1241,6 +1280,8 @@ def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
 # batch (PERF.md 'Shared prefix').  False takes the shared path wherever it applies (tests of the path, A/B)
 _SHARED_GATE = True
 _SHARED_ROWS_MAX = 64  # decode rows the skinny and the rows GEMM serve
+# the same switch for the shared KV8 state (``kv_cache="int8"``; PERF.md 'Shared prefix, int8')
+_SHARED_KV8_GATE = True
 
 
 def _shared_pays(B, N, P):
@@ -1253,13 +1294,25 @@ def _shared_pays(B, N, P):
     return not _SHARED_GATE or N >= 64 or (N >= 16 and P >= 128)
 
 
-def _shared_state_for(model, idx, tmax, N, new_tokens):
-    """The shared-prefix state the model keeps under ``_mg_shared_cache``, prefilled with the prompts ``idx``
-    [B, T] and with room for ``new_tokens`` new tokens per row -- or a new one when B, N, ``tmax`` or the
-    device differ.  A slot of its own: the plain states and their graphs are never touched."""
-    c = model.__dict__.get("_mg_shared_cache")
+def _shared_kv8_pays(N, P):
+    """The measured rule of the shared KV8 state (PERF.md 'Shared prefix, int8'; the grid of ``_shared_pays``
+    against the repeated batch on the plain KV8 state): N >= 16 at every prompt length -- every measured case
+    there decodes faster (1.08x to 2.48x) with a first token no slower.  Slower outside it: N = 2 at every P on
+    both models (0.86x to 0.97x) and N = 8 on GPT-2 124M (0.90x to 0.97x; gpt2-xl at N = 8 is 1.07x to 1.17x
+    faster, but a class goes only if no measured case in it is slower).  N between 8 and 16 and B > 1 were not
+    measured; ``P`` is kept for a rule that needs it."""
+    return not _SHARED_KV8_GATE or N >= 16
+
+
+def _shared_state_for(model, idx, tmax, N, new_tokens, kv8=False):
+    """The shared-prefix state the model keeps under ``_mg_shared_cache`` (``kv8``: the KV8 model's, under
+    ``_mg_shared_kv8_cache``), prefilled with the prompts ``idx`` [B, T] and with room for ``new_tokens`` new
+    tokens per row -- or a new one when B, N, ``tmax`` or the device differ.  Slots of their own: the plain
+    states and their graphs are never touched, nor is one shared state by a call on the other."""
+    slot = "_mg_shared_kv8_cache" if kv8 else "_mg_shared_cache"
+    c = model.__dict__.get(slot)
     if c is None or (c.prompts, c.N, c.tmax, c.dev) != (idx.size(0), N, tmax, idx.device):
-        c = model.__dict__["_mg_shared_cache"] = _SharedCache(model, idx, tmax, N, new_tokens)
+        c = model.__dict__[slot] = _SharedCache(model, idx, tmax, N, new_tokens, kv8)
     else:
         c.room(new_tokens)
         c.prefill(idx)
@@ -1309,12 +1362,14 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     tensors), and is by definition what ``generate(idx.repeat_interleave(N, 0), ...)`` returns with every
     other argument equal: the seeded sampler hashes the batch row b * N + j into the draw, so the rows of
     one prompt diverge on their own, and greedy gives N equal rows.  N = 1 is the call without the
-    argument.  On the GPU device loops (``use_cache``, greedy or seeded) with ``kv_cache="bf16"``,
+    argument.  On the GPU device loops (``use_cache``, greedy or seeded) with
     ``reuse_cache`` off, prompt + ``max_new_tokens`` <= ``block_size`` and B * N <= 64, a state of its own
     (``_mg_shared_cache``, ``_SharedCache``) prefills each prompt once, keeps its K/V once and decodes the B * N
     rows with ``attention_decode_shared``, which reads a prompt's keys once per (prompt, head) for all N
     queries -- where that measured no slower than the repeated batch (``_shared_pays``; PERF.md 'Shared
-    prefix').  Everywhere else -- the CPU, ``use_cache=False``, ``seed=None``, the int8 cache, ``reuse_cache``, a
+    prefix').  With ``kv_cache="int8"`` that state is the KV8 model's (``_mg_shared_kv8_cache``: the prompt's and
+    the rows' K/V as int8, ``attention_decode_shared_kv8``) under a gate of its own (``_shared_kv8_pays``; PERF.md
+    'Shared prefix, int8').  Everywhere else -- the CPU, ``use_cache=False``, ``seed=None``, ``reuse_cache``, a
     call past one context window -- the repeated batch is what runs, exactly.  On the shared path it is the
     same model on another attention kernel and a B-row prefill: logits differ in the last bf16 bits and
     a token may differ only at a near-tie.  ``generate_batch``, ``generate_beam``,
@@ -1394,8 +1449,9 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
         seed = int(seed) & ((1 << 64) - 1)
     on_device = idx.is_cuda and use_cache and max_new_tokens > 0 and (seeded or not do_sample)  # the device loops
     # N continuations per prompt: the shared-prefix state where it applies and pays, else the repeated batch
-    shared = (N > 1 and on_device and not kv8 and not reuse_cache and idx.size(1) + max_new_tokens <= bs
-              and idx.size(0) * N <= _SHARED_ROWS_MAX and _shared_pays(idx.size(0), N, idx.size(1)))
+    shared = (N > 1 and on_device and not reuse_cache and idx.size(1) + max_new_tokens <= bs
+              and idx.size(0) * N <= _SHARED_ROWS_MAX
+              and (_shared_kv8_pays(N, idx.size(1)) if kv8 else _shared_pays(idx.size(0), N, idx.size(1))))
     if N > 1 and not shared:
         idx = idx.repeat_interleave(N, dim=0)
     proc, pwords = _processors("generate", model, on_device, repetition_penalty, presence_penalty,
@@ -1503,7 +1559,7 @@ def _generate_windowed_gpu(model, idx, max_new_tokens, first, loop, logprobs=Fal
         if shared == 1:
             cache = _state_for(model, slot, ctx, bs, reuse=reuse)
         else:
-            cache = _shared_state_for(model, idx, bs, shared, max_new_tokens)
+            cache = _shared_state_for(model, idx, bs, shared, max_new_tokens, slot in _KV8_SLOTS.values())
         if proc is not None:
             cache.process_prefill(ctx, proc)
         tok = first(cache, T, ctx)

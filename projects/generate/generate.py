@@ -33,7 +33,8 @@ relative rounding error.
 
 ``--kv-int8`` keeps the KV cache as int8 with one power-of-two scale per (position, layer, head) K and V
 vector (``kv_cache="int8"``, the KV8 model: every attention reads the snapped K / V) and prints the cache
-bytes; it goes with sampling, ``--greedy``, ``--logprobs``, several prompts, ``--beams`` and ``--speculative``.
+bytes; it goes with sampling, ``--greedy``, ``--logprobs``, several prompts, ``--beams``, ``--speculative`` and
+``--num-return-sequences`` (the prompt's int8 K/V are then kept once for its N rows where that measured no slower).
 
 ``--logprobs`` prints, after each sample, the summed log-probability of its generated tokens under
 the model (temperature 1, before top-k / top-p) and their per-token perplexity.
@@ -97,8 +98,8 @@ def main(argv=None):
                          "--beams, --speculative or --kv-int8")
     ap.add_argument("--num-return-sequences", type=int, default=1,
                     help="continuations per sample row (num_return_sequences=N): --num-samples * N outputs; on the "
-                         "GPU the prompt is prefilled and its K/V kept once per row where that measured no slower; "
-                         "one prompt, not with --beams or --speculative")
+                         "GPU the prompt is prefilled and its K/V kept once per row where that measured no slower, "
+                         "with --kv-int8 as int8; one prompt, not with --beams or --speculative")
     ap.add_argument("--device", default="auto")
     ap.add_argument("--seed", type=int, default=3407,
                     help="initialisation seed and the sampler's seed (reproducible on-device sampling)")
