@@ -9,7 +9,13 @@ way, so both see the same allocator and cache state -- with ``reuse_cache=False`
 pairs after --warmup untimed ones, median and range.  ``reused`` is what the state reports for the timed
 reuse call (P: the extension ran; 0: ``generation._reuse_pays`` chose the prefill -- --ungated switches that
 rule off).  The first tokens of the two paths are compared (``same_first``; they
-may differ only at a near-tie).  One JSON line per case.  A GPU is required."""
+may differ only at a near-tie).  One JSON line per case.  A GPU is required.
+
+--kv-int8: the same protocol on the KV8 state (``kv_cache="int8"`` on every call, ``_mg_kv8_cache``; the
+extension is ``attention_extend_kv8``), gated by ``generation._reuse_kv8_pays``; the comparison is the fresh
+prefill of that same state.  --kernels: instead, the attention calls alone -- ``attention_extend_kv8``
+against ``attention_extend`` at each (B, P, Tq) with the model's heads, the three launches of one layer by
+device events, --reps alternating pairs."""
 import argparse
 import json
 import os
@@ -42,14 +48,21 @@ def main(argv=None):
     ap.add_argument("--ungated", action="store_true",
                     help="take every common prefix, also where generation._reuse_pays would prefill (the "
                          "measurement the rule was read from)")
+    ap.add_argument("--kv-int8", action="store_true", help="the KV8 state: kv_cache='int8' on every call")
+    ap.add_argument("--kernels", action="store_true",
+                    help="time attention_extend_kv8 against attention_extend alone (no model is run)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("bench_prefix_reuse: needs a GPU")
     if a.ungated:
         from mingpt_distributed_amd.models import generation
 
-        generation._REUSE_GATE = False
+        generation._REUSE_GATE = generation._REUSE_KV8_GATE = False
+    kw = {"kv_cache": "int8"} if a.kv_int8 else {}
+    slot = "_mg_kv8_cache" if a.kv_int8 else "_mg_decode_cache"
     cases = [tuple(int(v) for v in c.split(":")) for c in a.cases.split(",")]
+    if a.kernels:
+        return kernels(a, cases)
     for mt in a.model_types.split(","):
         torch.manual_seed(0)
         model = GPT(GPTConfig(model_type=mt, vocab_size=50257, block_size=1024, embed_drop=0.0, resid_drop=0.0,
@@ -62,16 +75,16 @@ def main(argv=None):
                 with torch.no_grad():
                     for rep in range(a.warmup + a.reps):
                         for reuse in (True, False):
-                            model.generate(idx[:, :P], 1, reuse_cache=True)  # the state holds the P tokens
-                            out, dt = timed(lambda: model.generate(idx, 1, reuse_cache=reuse))
+                            model.generate(idx[:, :P], 1, reuse_cache=True, **kw)  # the state holds the P tokens
+                            out, dt = timed(lambda: model.generate(idx, 1, reuse_cache=reuse, **kw))
                             if reuse:
-                                reused = model._mg_decode_cache.reused
+                                reused = model.__dict__[slot].reused
                             first[reuse] = out[:, -1]
                             if rep >= a.warmup:
                                 times[reuse].append(dt * 1e3)
                 med = {k: statistics.median(v) for k, v in times.items()}
                 print(json.dumps({
-                    "bench": "prefix_reuse", "model": mt, "B": B, "P": P, "Tq": Tq, "reused": reused,
+                    "bench": "prefix_reuse", "kv_cache": "int8" if a.kv_int8 else "bf16", "model": mt, "B": B, "P": P, "Tq": Tq, "reused": reused,
                     "fresh_ms": round(med[False], 3), "reuse_ms": round(med[True], 3),
                     "fresh_range_ms": [round(min(times[False]), 3), round(max(times[False]), 3)],
                     "reuse_range_ms": [round(min(times[True]), 3), round(max(times[True]), 3)],
@@ -79,6 +92,44 @@ def main(argv=None):
                     "same_first": bool(torch.equal(first[True], first[False]))}), flush=True)
         del model
         torch.cuda.empty_cache()
+
+
+def kernels(a, cases):
+    """One layer's attention calls on random caches: each call is its append, attention and combine launches."""
+    from mingpt_distributed_amd.models import GPTConfig
+    from mingpt_distributed_amd.ops._ext import ext
+
+    C = ext()
+    for mt in a.model_types.split(","):
+        cfg = GPTConfig(model_type=mt, vocab_size=50257, block_size=1024).resolve()
+        H, D = cfg.n_head, cfg.n_embed
+        for B in (int(b) for b in a.batches.split(",")):
+            for P, Tq in cases:
+                g = torch.Generator().manual_seed(P + Tq)
+                new = torch.randn(B * Tq, 3 * D, generator=g).to(torch.bfloat16).cuda()
+                cache = torch.randn(B, 1024, 3 * D, generator=g).to(torch.bfloat16).cuda()
+                kq = torch.randint(-127, 128, (B, 2, H, 1024, D // H), generator=g, dtype=torch.int8).cuda()
+                ks = torch.full((B, 2, H, 1024), 2.0 ** -6, device="cuda")
+                calls = {"bf16": lambda: C.attention_extend(new, cache, H, P),
+                         "int8": lambda: C.attention_extend_kv8(new, kq, ks, H, P)}
+                times = {k: [] for k in calls}
+                for rep in range(a.warmup + a.reps):
+                    for k, fn in calls.items():
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                        ev[0].record()
+                        for _ in range(20):
+                            fn()
+                        ev[1].record()
+                        torch.cuda.synchronize()
+                        if rep >= a.warmup:
+                            times[k].append(ev[0].elapsed_time(ev[1]) * 1e3 / 20)
+                med = {k: statistics.median(v) for k, v in times.items()}
+                print(json.dumps({
+                    "bench": "prefix_reuse_kernels", "model": mt, "B": B, "H": H, "hd": D // H, "base": P, "Tq": Tq,
+                    "splits": C.attention_extend_splits(B, Tq, H, P),
+                    "extend_us": round(med["bf16"], 2), "extend_kv8_us": round(med["int8"], 2),
+                    "extend_range_us": [round(min(times["bf16"]), 2), round(max(times["bf16"]), 2)],
+                    "extend_kv8_range_us": [round(min(times["int8"]), 2), round(max(times["int8"]), 2)]}), flush=True)
 
 
 if __name__ == "__main__":

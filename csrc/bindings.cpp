@@ -856,6 +856,36 @@ at::Tensor attention_decode_shared_kv8(const at::Tensor& qkv_new, const at::Tens
   return out;
 }
 
+// attention_extend on the int8 cache (kernels.h): qkv_new [B * Tq, 3D] at positions base .. base + Tq - 1 of
+// kq / ks of B sequences; appends the rule's (q, s) of their K/V vectors and returns out [B * Tq, D]
+at::Tensor attention_extend_kv8(const at::Tensor& qkv_new, const at::Tensor& kq, const at::Tensor& ks, int64_t H,
+                                int64_t base) {
+  const char* op = "attention_extend_kv8";
+  CHECK_BF16(qkv_new); CHECK_CONTIG(qkv_new);
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) % 3 == 0, op, ": qkv_new must be [B * Tq, 3D]");
+  const int64_t D = qkv_new.size(1) / 3;
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128,
+              op, ": head dim must be a multiple of 8, at most 128");
+  const int64_t hd = D / H;
+  TORCH_CHECK(kq.dim() == 5 && kq.size(0) >= 1, op, ": kq must be [B, 2, H, Tmax, hd]");
+  const int64_t B = kq.size(0), Tmax = kq.size(3);
+  kv8_cache_args(op, kq, ks, B, H, hd);
+  TORCH_CHECK(kq.device() == qkv_new.device(), op, ": the cache is on another device");
+  TORCH_CHECK(qkv_new.size(0) >= B && qkv_new.size(0) % B == 0, op, ": qkv_new must hold Tq >= 1 rows per sequence");
+  const int64_t Tq = qkv_new.size(0) / B;
+  TORCH_CHECK(base >= 0 && base + Tq <= Tmax, op, ": base >= 0 and base + Tq <= Tmax");
+  TORCH_CHECK(B * Tmax * 3 * D < (int64_t(1) << 40) && B * H <= 65535, op, ": batch too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0, op, ": tensors must be 16-byte aligned");
+  DevGuard g(qkv_new.device());
+  auto out = at::empty({B * Tq, D}, qkv_new.options());
+  const int64_t np = (int64_t)mg::attention_extend_part_floats((int)B, (int)Tq, (int)H, (int)hd, (int)base);
+  at::Tensor part;
+  if (np) part = at::empty({np}, qkv_new.options().dtype(at::kFloat));
+  mg::attention_extend_kv8(bp(qkv_new), kq.data_ptr<int8_t>(), fp(ks), bp(out), np ? fp(part) : nullptr, (int)B,
+                           (int)Tq, (int)H, (int)hd, Tmax, (int)base, cur_stream());
+  return out;
+}
+
 // attention_decode on the int8 cache: pos / pos_dev / part / counters / pos_stride / group as there (group =
 // K: kq / ks of B sequences, qkv_new [B * K, 3D], pos_dev int32 [B * K], the workspace for B * K rows)
 at::Tensor attention_decode_kv8(const at::Tensor& qkv_new, const at::Tensor& kq, const at::Tensor& ks, int64_t H,
@@ -1510,6 +1540,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return (int64_t)mg::attention_decode_part_floats((int)B, (int)H, (int)hd);
   });
   m.def("attention_extend", &attention_extend, py::arg("qkv_new"), py::arg("cache"), py::arg("H"), py::arg("base"));
+  m.def("attention_extend_kv8", &attention_extend_kv8, py::arg("qkv_new"), py::arg("kq"), py::arg("ks"), py::arg("H"),
+        py::arg("base"));
   // the key splits attention_extend runs B sequences of Tq new rows at `base` with (1: no combine launch)
   m.def("attention_extend_splits", [](int64_t B, int64_t Tq, int64_t H, int64_t base) {
     return (int64_t)mg::attention_extend_splits((int)B, (int)Tq, (int)H, (int)base);

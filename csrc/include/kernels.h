@@ -362,6 +362,18 @@ void attention_decode_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* 
 void attention_decode_shared_kv8(const bf16_t* qkv_new, const int8_t* pre_q, const float* pre_s, int8_t* own_q,
                                  float* own_s, bf16_t* out, float* part, int R, int N, int H, int hd, int Tpre,
                                  int Town, const int* pos_dev, const int* plen_dev, hipStream_t stream);
+// attention_extend on the int8 cache (attention_extend.hip): qkv_new [B * Tq, 3D] row b * Tq + r is the token
+// at position base + r of sequence b of kq / ks.  The rule's (q, s) of every K and V vector of the chunk are
+// appended at positions base .. base + Tq - 1 (qkv_new itself is not modified, no other cache byte or scale
+// word is written) and out [B * Tq, D] is bit for bit what attention_extend writes for qkv_new with its K/V
+// thirds snapped over a bf16 cache holding the dequantized rows 0 .. base - 1.  Three stream-ordered
+// launches: the snap-append, attention_extend's attention kernel with the tile staging swapped (the int8
+// tiles of a (b, K | V, h) plane are dequantized into the bf16 LDS images, 16-byte loads where hd % 16 == 0,
+// else 8-byte; tile body, mask and partials are the same code) and its combine kernel.  Splits
+// (attention_extend_splits), workspace (attention_extend_part_floats) and every limit: attention_extend's.
+// Int8 bytes and scale words at or past base + Tq are never read into a result (the scales may be NaN).
+void attention_extend_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, float* part, int B, int Tq,
+                          int H, int hd, long Tmax, int base, hipStream_t stream);
 // beam_reorder on the int8 cache, in place over L layers (kq_layer / ks_layer elements apart): kq int8
 // [L, R, 2, H, Tmax, hd], ks fp32 [L, R, 2, H, Tmax], R = B * W.  For every (K | V, head), positions t <
 // min(*pos, Tmax) of beam r of a prompt become those of beam parent[r] of the same prompt, int8 bytes

@@ -43,11 +43,35 @@
 //    count only (attention_extend_splits), so equal calls give equal bits, and a row's bits depend
 //    on its own sequence only.
 //  * instantiated per number of 16-column MFMA k-steps, nks_for(hd).
+//
+// KV8 (attention_extend_kv8): the same three launches on the int8 cache of kernels.h, kq [B, 2, H, Tmax,
+// hd] and ks [B, 2, H, Tmax].  Only the append and the tile staging differ.
+//  * attn_extend_snap_kernel appends the KV8 rule's (q, s) of the chunk's K and V vectors at positions
+//    base .. base + Tq - 1 and leaves qkv_new alone.  A kernel of its own beside kv8_store's, not that
+//    kernel with an offset and a flag: this one writes no qkv byte and never replicates rows, and it
+//    stays in this file with this file's flags; the rule itself is kv8_common.h's one copy.
+//  * attn_extend_kernel<NKS, KV>, KV = 16 (hd % 16 == 0) or 8 bytes per load.  A 64-key tile of one
+//    (b, K | V, h) plane is 64 * hd contiguous bytes and 64 scale words: half the bf16 tile's bytes and no
+//    strided rows.  Thread i of the workgroup loads bytes [(i + 256 c) * KV, + KV) of the tile, so every
+//    load instruction of a wave covers one contiguous 64 * KV bytes, and the scale word of that chunk's
+//    key with a 4-byte load of its own (at most 16 lanes share a word: served by one cache line; a
+//    cross-wave exchange of 64 scale words through LDS would cost a barrier per tile).  Both planes go
+//    through descriptors that end at key base + Tq, so a key past it reads q = 0, s = 0 and stages 0.
+//    The chunk is dequantized in registers -- float(q) * s is exact, it IS the bf16 value of the
+//    snapped row, and a NaN scale makes the vector NaN -- at store time, after the current tile's
+//    MFMAs, so what waits in registers under them is the raw int8 chunk and its scale: (KV / 4 + 1)
+//    registers per load against the bf16 staging's 4 per 8 columns.  The stores write the swizzled
+//    images the bf16 staging writes; fragment offsets, ext_tile, mask, partials and combine are the
+//    one copy above, and the key split is the same function, so out equals attention_extend on the
+//    snapped chunk over the dequantized cache bit for bit.  Image columns at or past hd are covered by
+//    no load: both buffers are zeroed once before the first tile when hd < 32 NO.
 #include "attn_common.h"
 #include "kernels.h"
+#include "kv8_common.h"
 
 using namespace mg;
 using namespace mg::attn;
+using namespace mg::kv8;
 
 namespace {
 
@@ -56,6 +80,9 @@ constexpr int kExtSplitsMax = 16;
 struct ExtArgs {
   const bf16_t* qkv_new;  // [B * Tq, 3D]
   const bf16_t* cache;    // [B, Tmax, 3D], rows [base, base + Tq) already appended
+  // KV8 (attention_extend_kv8): the int8 cache in place of `cache`, positions [base, base + Tq) appended
+  const int8_t* kq;       // [B, 2, H, Tmax, hd]
+  const float* ks;        // [B, 2, H, Tmax]
   bf16_t* out;            // [B * Tq, D]
   float* part_ml;         // S > 1: [nqb][B * H][S][128][2] {m, l}
   float* part_o;          // S > 1: [nqb][B * H][S][128][hd]
@@ -77,6 +104,37 @@ __global__ __launch_bounds__(256) void attn_extend_append_kernel(const bf16_t* _
   const long b = m / Tq, r = m % Tq;
   const long ld = 3L * D;
   st16(cache + (b * Tmax + base + r) * ld + D + 8 * c, ld16(qkv_new + m * ld + D + 8 * c));
+}
+
+// KV8 append: the rule's (q, s) of the K and V vectors of qkv_new row b * Tq + r -> position base + r of
+// the (b, K | V, h) planes.  One thread per 16-byte chunk; the dch = hd / 8 chunks of a vector sit in
+// consecutive threads of one workgroup (256 / dch whole vectors per workgroup) and meet through LDS.
+// Vector v = ((b * Tq + r) * 2 + w) * H + h walks consecutive addresses of the K and V thirds.
+__global__ __launch_bounds__(256) void attn_extend_snap_kernel(const bf16_t* __restrict__ qkv_new,
+                                                               int8_t* __restrict__ kq, float* __restrict__ ks,
+                                                               long NV, int Tq, int H, int hd, long Tmax, int base) {
+  __shared__ uint32_t cm[256];
+  const int dch = hd >> 3, vpb = 256 / dch;
+  const int lv = threadIdx.x / dch, c = threadIdx.x % dch;
+  const long v = (long)blockIdx.x * vpb + lv;
+  const bool on = lv < vpb && v < NV;
+  const int h = (int)(v % H), w = (int)((v / H) % 2);
+  const long m = v / (2L * H);
+  const uint4 raw = on ? ld16(qkv_new + (m * 3 + 1 + w) * H * hd + h * hd + c * 8) : make_uint4(0u, 0u, 0u, 0u);
+  cm[threadIdx.x] = max_abs8(raw);
+  __syncthreads();
+  if (!on) return;
+  uint32_t a15 = 0;
+  for (int i = 0; i < dch; ++i) a15 = max(a15, cm[lv * dch + i]);
+  int ex;
+  bool live;
+  const float s = kv8_scale(a15, ex, live);
+  float f[8];
+  const uint2 q8 = kv8_quant8(raw, ex, live, s, f);
+  const long b = m / Tq, r = m % Tq;
+  const long row = ((b * 2 + w) * H + h) * Tmax + base + r;
+  *reinterpret_cast<uint2*>(kq + row * hd + c * 8) = q8;
+  if (c == 0) ks[row] = s;
 }
 
 // One 64-key tile for one wave's 32 queries: S'^T = K Q^T - m, p = exp2(S'), O^T += V^T P^T.  m moves
@@ -163,7 +221,21 @@ MG_DEVICE void ext_tile(const char* sk, const char* sv, const int (&ko)[NKS], co
     }
 }
 
-template <int NKS>
+// what a thread holds of tile t + 1 under tile t's MFMAs
+template <int NC>
+struct ExtRegs {  // bf16 rows: 16-byte chunks of K and V
+  uint4 k[NC], v[NC];
+};
+template <int NL, int CB>
+struct ExtRegsKv8 {  // int8 planes: CB-byte chunks and the scale of each chunk's key
+  typedef uint32_t chunk __attribute__((ext_vector_type(CB / 4)));
+  chunk k[NL], v[NL];
+  float sk[NL], sv[NL];
+};
+
+// KV = 0: bf16 cache rows.  KV = 16 / 8: the int8 cache (kq / ks), staged with 16-byte loads (hd % 16 ==
+// 0) or 8-byte loads -- the KV8 staging in the file header.
+template <int NKS, int KV>
 __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const ExtArgs a) {
   constexpr int NH = (NKS + 3) / 4;   // 64-column halves of the LDS images
   constexpr int NO = (NKS + 1) / 2;   // 32-column O^T accumulator tiles
@@ -197,7 +269,9 @@ __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const
   const bf16_t* seq = a.cache + (long)b * a.Tmax * ld;
   const uint64_t seq_bytes = (uint64_t)(a.base + a.Tq) * ld * 2;  // rows [0, base + Tq) of this sequence
   const uint64_t kcol = (uint64_t)(a.D + hh * a.hd) * 2;
-  auto load_tile = [&](uint4 (&rk)[NC], uint4 (&rv)[NC], int k0) {
+  auto load_tile = [&](auto& rg, int k0) {
+    uint4 (&rk)[NC] = rg.k;
+    uint4 (&rv)[NC] = rg.v;
     const uint64_t off = kcol + (uint64_t)k0 * ld * 2;
     const __amdgpu_buffer_rsrc_t dk = kv_rsrc(seq, seq_bytes, off);
     const __amdgpu_buffer_rsrc_t dv = kv_rsrc(seq, seq_bytes, off + (uint64_t)a.D * 2);
@@ -209,12 +283,80 @@ __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const
       rv[c] = cok[c] ? v : make_uint4(0, 0, 0, 0);
     }
   };
-  auto store_tile = [&](char* dst, const uint4 (&rk)[NC], const uint4 (&rv)[NC]) {
+  auto store_tile = [&](char* dst, const auto& rg) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      *reinterpret_cast<uint4*>(dst + sdst[c]) = rk[c];
-      *reinterpret_cast<uint4*>(dst + TILE + sdst[c]) = rv[c];
+      *reinterpret_cast<uint4*>(dst + sdst[c]) = rg.k[c];
+      *reinterpret_cast<uint4*>(dst + TILE + sdst[c]) = rg.v[c];
     }
+  };
+
+  // KV8 staging (file header).  Load c of a thread is chunk idx = thread + 256 c of the tile's 64 * cpr
+  // chunks, cpr = hd / CB per key: key row idx / cpr, columns (idx % cpr) * CB.  qok: the chunk exists.
+  constexpr int CB = KV ? KV : 16;              // bytes per load
+  constexpr int NL = (NKS * 4 + CB - 1) / CB;   // loads per thread and matrix at most: 64 * 16 NKS / CB / 256
+  const int cpr = max(a.hd / CB, 1);
+  uint32_t qdst[NL], qkey[NL];                  // image offset of the chunk's first 8 columns; its key row
+  bool qok[NL];
+#pragma unroll
+  for (int c = 0; c < NL; ++c) {
+    const int idx = threadIdx.x + 256 * c, row = min(idx / cpr, 63), col = (idx % cpr) * CB;
+    qok[c] = idx < 64 * cpr;
+    qkey[c] = row;
+    qdst[c] = (col >> 6) * HALF + lds_off(row, (col >> 3) & 7);
+  }
+  const long plane = ((long)b * 2 * a.H + hh) * a.Tmax;  // K; V is H * Tmax keys behind it
+  const long vplane = (long)a.H * a.Tmax;
+  auto load_kv8 = [&](auto& rg, int k0) {
+    const uint64_t qbytes = (uint64_t)(a.base + a.Tq) * a.hd, qoff = (uint64_t)k0 * a.hd;
+    const uint64_t sbytes = (uint64_t)(a.base + a.Tq) * 4, soff = (uint64_t)k0 * 4;
+    const __amdgpu_buffer_rsrc_t dk = kv_rsrc(a.kq + plane * a.hd, qbytes, qoff);
+    const __amdgpu_buffer_rsrc_t dv = kv_rsrc(a.kq + (plane + vplane) * a.hd, qbytes, qoff);
+    const __amdgpu_buffer_rsrc_t dsk = kv_rsrc(a.ks + plane, sbytes, soff);
+    const __amdgpu_buffer_rsrc_t dsv = kv_rsrc(a.ks + plane + vplane, sbytes, soff);
+    typedef typename ExtRegsKv8<NL, CB>::chunk chunk;
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+      if (qok[c]) {
+        const uint32_t off = (uint32_t)(threadIdx.x + 256 * c) * CB;
+        if constexpr (CB == 16) {
+          rg.k[c] = __builtin_bit_cast(chunk, __builtin_amdgcn_raw_buffer_load_b128(dk, off, 0, 0));
+          rg.v[c] = __builtin_bit_cast(chunk, __builtin_amdgcn_raw_buffer_load_b128(dv, off, 0, 0));
+        } else {
+          rg.k[c] = __builtin_bit_cast(chunk, __builtin_amdgcn_raw_buffer_load_b64(dk, off, 0, 0));
+          rg.v[c] = __builtin_bit_cast(chunk, __builtin_amdgcn_raw_buffer_load_b64(dv, off, 0, 0));
+        }
+        rg.sk[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsk, qkey[c] * 4, 0, 0));
+        rg.sv[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dsv, qkey[c] * 4, 0, 0));
+      }
+    }
+  };
+  auto store_chunk = [&](char* img, uint32_t dst, const auto& u, float sc) {
+    float f[8];
+    dequant8(make_uint2(u[0], u[1]), sc, f);
+    *reinterpret_cast<uint4*>(img + dst) = pack8(f);
+    if constexpr (CB == 16) {  // columns 8 .. 15 of the chunk: the neighbouring image chunk
+      dequant8(make_uint2(u[2], u[3]), sc, f);
+      *reinterpret_cast<uint4*>(img + (dst ^ 16)) = pack8(f);
+    }
+  };
+  auto store_kv8 = [&](char* dst, const auto& rg) {
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+      if (qok[c]) {
+        store_chunk(dst, qdst[c], rg.k[c], rg.sk[c]);
+        store_chunk(dst + TILE, qdst[c], rg.v[c], rg.sv[c]);
+      }
+    }
+  };
+  using Regs = std::conditional_t<KV != 0, ExtRegsKv8<NL, CB>, ExtRegs<NC>>;
+  auto load = [&](Regs& rg, int k0) {
+    if constexpr (KV != 0) load_kv8(rg, k0);
+    else load_tile(rg, k0);
+  };
+  auto store = [&](char* dst, const Regs& rg) {
+    if constexpr (KV != 0) store_kv8(dst, rg);
+    else store_tile(dst, rg);
   };
 
   // per-lane fragment offsets: K rows l32 (+32 per sub: an immediate), chunk 2 ks + h32;
@@ -252,10 +394,18 @@ __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const
   float m = 0.f, l = 0.f;
 
   if (t0 < t1) {  // (an empty split of a short block stages nothing and writes neutral partials)
+    if constexpr (KV != 0) {
+      // image columns hd .. 32 NO - 1 (K fragments read below 16 NKS, V^T fragments below 32 NO) are
+      // never staged: zero both buffers once
+      if (a.hd < 32 * NO) {
+        for (int i = threadIdx.x * 16; i < 4 * TILE; i += 256 * 16) *reinterpret_cast<uint4*>(smem + i) = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+      }
+    }
     {
-      uint4 rk[NC], rv[NC];
-      load_tile(rk, rv, t0 * 64);
-      store_tile(smem, rk, rv);
+      Regs rg;
+      load(rg, t0 * 64);
+      store(smem, rg);
     }
     __syncthreads();
     for (int t = t0; t < t1; ++t) {
@@ -263,8 +413,8 @@ __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const
       const char* sk = smem + (it & 1) * 2 * TILE;
       const char* sv = sk + TILE;
       const bool more = t + 1 < t1;
-      uint4 rk[NC], rv[NC];
-      if (more) load_tile(rk, rv, (t + 1) * 64);
+      Regs rg;
+      if (more) load(rg, (t + 1) * 64);
       const int k0 = t * 64;
       if (k0 <= wave_last && wave_r < a.Tq) {
         const int lim = mypos - k0 - 4 * h32;
@@ -272,7 +422,7 @@ __global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_kernel(const
         if (k0 + 63 > wave_first) ext_tile<NKS, true>(sk, sv, ko, qf, o, negm, m, l, t == t0, lim, ta0, tb0, ta1, tb1);
         else ext_tile<NKS, false>(sk, sv, ko, qf, o, negm, m, l, t == t0, lim, ta0, tb0, ta1, tb1);
       }
-      if (more) store_tile(smem + ((it + 1) & 1) * 2 * TILE, rk, rv);
+      if (more) store(smem + ((it + 1) & 1) * 2 * TILE, rg);
       __syncthreads();
     }
   }
@@ -368,9 +518,39 @@ int ext_tiles_per_split(int B, int Tq, int H, int base) {
   return cdiv(nt, std::max<long>(S, 1));
 }
 
-template <int NKS>
+template <int NKS, int KV>
 void launch_extend(const ExtArgs& a, hipStream_t stream) {
-  attn_extend_kernel<NKS><<<dim3(cdiv(a.Tq, 128), a.B * a.H, a.S), 256, 0, stream>>>(a);
+  attn_extend_kernel<NKS, KV><<<dim3(cdiv(a.Tq, 128), a.B * a.H, a.S), 256, 0, stream>>>(a);
+}
+
+// the attention launch and, with split keys, the combine; kv: 0 (bf16 rows), 16 / 8 (int8 planes by the
+// staging's load width)
+template <int KV>
+void launch_attend(const ExtArgs& a, hipStream_t stream) {
+  switch (nks_for(a.hd)) {
+    case 1: launch_extend<1, KV>(a, stream); break;
+    case 2: launch_extend<2, KV>(a, stream); break;
+    case 3: launch_extend<3, KV>(a, stream); break;
+    case 4: launch_extend<4, KV>(a, stream); break;
+    case 6: launch_extend<6, KV>(a, stream); break;
+    default: launch_extend<8, KV>(a, stream); break;
+  }
+  if (a.S > 1)
+    attn_extend_combine_kernel<<<dim3(cdiv(std::min(a.Tq, 128) * (a.hd >> 2), 256), cdiv(a.Tq, 128), a.B * a.H), 256, 0,
+                                 stream>>>(a);
+}
+
+// the shapes, the split plan and the workspace layout: the same for both storage kinds
+ExtArgs ext_plan(const bf16_t* qkv_new, bf16_t* out, float* part, int B, int Tq, int H, int hd, long Tmax, int base) {
+  ExtArgs a{};
+  a.qkv_new = qkv_new; a.out = out;
+  a.B = B; a.Tq = Tq; a.H = H; a.hd = hd; a.D = H * hd; a.base = base; a.Tmax = Tmax;
+  a.tps = ext_tiles_per_split(B, Tq, H, base);
+  a.S = mg::attention_extend_splits(B, Tq, H, base);
+  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
+  a.part_ml = part;
+  a.part_o = part ? part + (size_t)cdiv(Tq, 128) * B * H * a.S * 128 * 2 : nullptr;
+  return a;
 }
 
 }  // namespace
@@ -388,27 +568,21 @@ size_t attention_extend_part_floats(int B, int Tq, int H, int hd, int base) {
 
 void attention_extend(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, int B, int Tq, int H,
                       int hd, long Tmax, int base, hipStream_t stream) {
-  ExtArgs a{};
-  a.qkv_new = qkv_new; a.cache = cache; a.out = out;
-  a.B = B; a.Tq = Tq; a.H = H; a.hd = hd; a.D = H * hd; a.base = base; a.Tmax = Tmax;
-  a.tps = ext_tiles_per_split(B, Tq, H, base);
-  a.S = attention_extend_splits(B, Tq, H, base);
-  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
-  const int nqb = cdiv(Tq, 128);
-  a.part_ml = part;
-  a.part_o = part ? part + (size_t)nqb * B * H * a.S * 128 * 2 : nullptr;
+  ExtArgs a = ext_plan(qkv_new, out, part, B, Tq, H, hd, Tmax, base);
+  a.cache = cache;
   attn_extend_append_kernel<<<cdiv((long)B * Tq * (a.D >> 2), 256), 256, 0, stream>>>(qkv_new, cache, B, Tq, a.D,
                                                                                      Tmax, base);
-  switch (nks_for(hd)) {
-    case 1: launch_extend<1>(a, stream); break;
-    case 2: launch_extend<2>(a, stream); break;
-    case 3: launch_extend<3>(a, stream); break;
-    case 4: launch_extend<4>(a, stream); break;
-    case 6: launch_extend<6>(a, stream); break;
-    default: launch_extend<8>(a, stream); break;
-  }
-  if (a.S > 1)
-    attn_extend_combine_kernel<<<dim3(cdiv(std::min(Tq, 128) * (hd >> 2), 256), nqb, B * H), 256, 0, stream>>>(a);
+  launch_attend<0>(a, stream);
+}
+
+void attention_extend_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* out, float* part, int B, int Tq,
+                          int H, int hd, long Tmax, int base, hipStream_t stream) {
+  ExtArgs a = ext_plan(qkv_new, out, part, B, Tq, H, hd, Tmax, base);
+  a.kq = kq; a.ks = ks;
+  const long NV = (long)B * Tq * 2 * H;
+  attn_extend_snap_kernel<<<cdiv(NV, 256 / (hd >> 3)), 256, 0, stream>>>(qkv_new, kq, ks, NV, Tq, H, hd, Tmax, base);
+  if (hd % 16 == 0) launch_attend<16>(a, stream);
+  else launch_attend<8>(a, stream);
 }
 
 }  // namespace mg

@@ -444,11 +444,10 @@ class _GpuCache(_Body):
         self._sparams, self._rparams, self._pparams = (_Params(self.dev) for _ in range(3))
         self._rstate, self._bstate, self._sstate = None, {}, {}
         self.logits = None
-        # prefix reuse (``_state_for(reuse=True)``): the tokens whose K/V rows the bf16 caches hold, by
-        # row, in ``held[:, :nheld]`` (recorded after a reuse-enabled ``generate``; any prefill clears
-        # it), and how many of them the last prefill of this state kept (``reused``; 0: a full one)
-        self.held = (torch.zeros(B, tmax, dtype=torch.long, device=self.dev)
-                     if rows is None and not self.kv8 else None)
+        # prefix reuse (``_state_for(reuse=True)``): the tokens whose K/V rows the caches hold (bf16 or
+        # int8), by row, in ``held[:, :nheld]`` (recorded after a reuse-enabled ``generate``; any prefill
+        # clears it), and how many of them the last prefill of this state kept (``reused``; 0: a full one)
+        self.held = torch.zeros(B, tmax, dtype=torch.long, device=self.dev) if rows is None else None
         self.nheld = self.reused = 0
         if rows is None:
             self.prefill(idx, last)
@@ -527,7 +526,10 @@ class _GpuCache(_Body):
         positions base .. base + Tq - 1 behind ``base`` cached rows per sequence, through the blocks on
         the route of B * Tq rows (``_route``), each layer attending with ``attention_extend`` (the chunk
         against the cached keys plus itself; it appends the chunk's K/V rows), and set ``logits`` [B, V]
-        to the last new row's -- where ``prefill`` leaves them, from the LM head on the route of B rows."""
+        to the last new row's -- where ``prefill`` leaves them, from the LM head on the route of B rows.
+        A KV8 state attends with ``attention_extend_kv8`` on its int8 caches (the chunk's K/V are snapped
+        by the kernel); with ``_KV8_DECODE`` off it snaps the chunk in place (``kv8_store``) and runs
+        ``attention_extend`` on its bf16 caches of snapped rows -- the same model, bit for bit."""
         C, bf = self.C, self.bf
         tr, cfg = self.model.transformer, self.model.config
         B, Tq = idx_new.shape
@@ -535,7 +537,16 @@ class _GpuCache(_Body):
         pos = (base + torch.arange(Tq, dtype=torch.int32, device=self.dev)).repeat(B)  # one per row
         x = C.embedding_fwd(idx_new.reshape(B * Tq, 1).contiguous(), bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0,
                             pos, None, None, 1).view(B * Tq, D)
-        x = self._blocks(x, lambda i, qkv: C.attention_extend(qkv, self.caches[i], H, base), self._route(B * Tq))
+        if self._kv8_on():
+            attend = lambda i, qkv: C.attention_extend_kv8(qkv, self.kq[i], self.ks[i], H, base)
+        elif self.kv8:
+
+            def attend(i, qkv):
+                C.kv8_store(qkv.view(B, Tq, 3 * D), H)
+                return C.attention_extend(qkv, self.caches[i], H, base)
+        else:
+            attend = lambda i, qkv: C.attention_extend(qkv, self.caches[i], H, base)
+        x = self._blocks(x, attend, self._route(B * Tq))
         self.logits = self._head(x.view(B, Tq, D)[:, -1].contiguous(), self._route(B))[:, :cfg.vocab_size]
         return self.logits
 
@@ -1238,6 +1249,8 @@ def kv_cache_nbytes(model):
 # reuse': 16 cases on GPT-2 124M and gpt2-xl; the extension has more launches per layer, so it has to
 # save rows that cost something).  False takes every common prefix (tests of the path, A/B)
 _REUSE_GATE = True
+# the same switch for the KV8 state (``kv_cache="int8"``; PERF.md 'Prefix reuse, int8')
+_REUSE_KV8_GATE = True
 
 
 def _reuse_pays(B, P, Tq):
@@ -1245,6 +1258,16 @@ def _reuse_pays(B, P, Tq):
     prefill would stream every weight for rows the cache already has), or the prefix saves at least 2048
     rows of prefill (B * P).  Slower outside it: P = 1, and P = 512 with 128 new rows at B = 1."""
     return not _REUSE_GATE or B * Tq <= 64 or B * P >= 2048
+
+
+def _reuse_kv8_pays(B, P, Tq):
+    """The rule of the KV8 state (PERF.md 'Prefix reuse, int8'; the points of ``_reuse_pays`` against the
+    fresh prefill of the same KV8 state, 16 cases on GPT-2 124M and gpt2-xl): B * Tq <= 64 new rows or B * P >=
+    2048 rows saved -- the ten measured cases there are 1.24x to 2.87x faster.  Slower outside it, as on the bf16
+    state: P = 1 (0.86x to 0.96x) and P = 512 with 128 new rows at B = 1 (0.97x, 0.98x).  The rule reads as
+    ``_reuse_pays`` because the two tables agree; it is kept apart so that either can move alone.  More than
+    64 new rows on 512 < B * P < 4096 saved ones was not measured and goes by the same bound."""
+    return not _REUSE_KV8_GATE or B * Tq <= 64 or B * P >= 2048
 
 
 def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
@@ -1255,11 +1278,12 @@ def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
     plain state comes back prefilled with ``idx`` (``last``: ``_GpuCache.prefill``); the others are
     prefilled by their callers, after the loop is built.
 
-    ``reuse`` (a plain bf16 state; ``generate(reuse_cache=True)``): when the state that is kept matches,
-    no weight changed since (``_stamp``) and its record ``held[:, :nheld]`` of the tokens in the caches
+    ``reuse`` (a plain state, bf16 or KV8; ``generate(reuse_cache=True)``): when the state that is kept matches,
+    no weight changed and ``_KV8_DECODE`` was not flipped since (``_stamp``: a flip swaps a KV8 state's
+    storage) and its record ``held[:, :nheld]`` of the tokens in the caches
     shares a prefix of P tokens with ``idx`` in every row -- P capped at T - 1: one row at least has to run
     for the logits -- only ``idx[:, P:]`` is run, on top of the cached rows (``_GpuCache.extend``), where
-    that measured faster (``_reuse_pays``); else the prefill as ever.  ``reused`` on the state is P, 0 after a full
+    that measured faster (``_reuse_pays``; a KV8 state: ``_reuse_kv8_pays``); else the prefill as ever.  ``reused`` on the state is P, 0 after a full
     prefill."""
     c = model.__dict__.get(slot)
     if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
@@ -1268,7 +1292,7 @@ def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
         P = 0
         if reuse and last is None and c.held is not None and c.nheld > 0 and c._stamp() == c.stamp:
             P = min(c.common_prefix(idx), idx.size(1) - 1)
-        if P >= 1 and _reuse_pays(idx.size(0), P, idx.size(1) - P):
+        if P >= 1 and (_reuse_kv8_pays if c.kv8 else _reuse_pays)(idx.size(0), P, idx.size(1) - P):
             c.extend(idx[:, P:], P)
             c.nheld, c.reused = 0, P  # the rows past P are overwritten: the caller records the new ones
         else:
@@ -1386,8 +1410,12 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     that pass ``reuse_cache=True`` and fit one context window (prompt + ``max_new_tokens`` <=
     ``block_size``); any other call on the state clears it, and the default (False) leaves every path,
     loop and captured graph as it is.  Covers the device loops and the host loop (``seed=None``); on the
-    CPU and with ``use_cache=False`` it is accepted and has no effect; with ``kv_cache="int8"`` it is a
-    ValueError (the int8 cache has no extension kernel).  ``generate_batch``, ``generate_beam``,
+    CPU and with ``use_cache=False`` it is accepted and has no effect.  With ``kv_cache="int8"`` the KV8
+    state (``_mg_kv8_cache``) keeps the same record and extends its int8 cache with
+    ``attention_extend_kv8`` -- the chunk's K/V snapped by the rule, the result bit for bit the bf16
+    kernel's on the dequantized cache -- under a gate of its own (``_reuse_kv8_pays``; PERF.md 'Prefix
+    reuse, int8').  A wart, kept because a test pins it: on the CPU the bf16 cache ignores the argument
+    and ``kv_cache="int8"`` refuses it with a ValueError.  ``generate_batch``, ``generate_beam``,
     ``generate_speculative`` and ``score`` do not take it.  ``projects/generate/generate.py
     --reuse-cache`` passes it through.
 
@@ -1437,9 +1465,9 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, do_sampl
     if kv8 and not use_cache:
         raise ValueError("generate: kv_cache='int8' needs use_cache=True (without a cache there is nothing to "
                          "quantize)")
-    if kv8 and reuse_cache:
-        raise ValueError("generate: reuse_cache=True needs kv_cache='bf16' (prefix reuse extends the bf16 cache; "
-                         "the int8 cache has no extension kernel)")
+    if kv8 and reuse_cache and not idx.is_cuda:
+        raise ValueError("generate: reuse_cache=True with kv_cache='int8' needs idx on the GPU (prefix reuse "
+                         "extends the device cache)")
     # prefix reuse: GPU cache paths whose whole call fits one context window (a sliding window re-prefills)
     reuse = bool(reuse_cache) and idx.is_cuda and use_cache and idx.size(1) + max_new_tokens <= bs
     seeded = do_sample and seed is not None

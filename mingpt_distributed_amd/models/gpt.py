@@ -234,7 +234,8 @@ class GPT(nn.Module):
         model -- K and V vectors snapped to int8 times a power-of-two scale, an int8 cache on the GPU
         (``generation.generate``); needs ``use_cache``.  ``reuse_cache=True``: on the GPU a prompt that starts
         with the tokens the KV cache still holds from the last such call runs only the tokens behind them
-        (``attention_extend``); same model, logits equal to the last bf16 bits (``generation.generate``).
+        (``attention_extend``; with ``kv_cache="int8"`` the int8 cache is extended, ``attention_extend_kv8``);
+        same model, logits equal to the last bf16 bits (``generation.generate``).
         ``num_return_sequences=N``: N continuations per prompt, B * N rows, what the call returns for
         ``idx.repeat_interleave(N, 0)``; on the GPU the prompt may be prefilled and kept once for its N rows
         (``attention_decode_shared``; the rule and its limits in ``generation.generate``)."""

@@ -95,7 +95,7 @@ def main(argv=None):
     ap.add_argument("--reuse-cache", action="store_true",
                     help="prefix reuse (reuse_cache=True): a prompt that starts with the tokens the KV cache "
                          "holds from the last call runs only the tokens behind them; one prompt, not with "
-                         "--beams, --speculative or --kv-int8")
+                         "--beams or --speculative; with --kv-int8 (on the GPU) the int8 cache is extended")
     ap.add_argument("--num-return-sequences", type=int, default=1,
                     help="continuations per sample row (num_return_sequences=N): --num-samples * N outputs; on the "
                          "GPU the prompt is prefilled and its K/V kept once per row where that measured no slower, "
