@@ -722,6 +722,83 @@ at::Tensor attention_extend(const at::Tensor& qkv_new, const at::Tensor& cache, 
   return out;
 }
 
+// The host lists of the ragged chunk attention (kernels.h): Tq_b >= 1 new rows behind base_b >= 0 cached ones
+static void ragged_lists(const char* op, const std::vector<int64_t>& tq, const std::vector<int64_t>& base, int64_t Tmax,
+                         std::vector<int>& t, std::vector<int>& p) {
+  TORCH_CHECK(!tq.empty() && tq.size() == base.size() && tq.size() <= 65535, op, ": one Tq and one base per sequence");
+  int64_t M = 0;
+  for (size_t b = 0; b < tq.size(); ++b) {
+    TORCH_CHECK(tq[b] >= 1 && base[b] >= 0 && base[b] + tq[b] <= Tmax, op, ": sequence ", b,
+                " needs Tq >= 1, base >= 0 and base + Tq <= ", Tmax, ", got Tq ", tq[b], " base ", base[b]);
+    M += tq[b];
+    t.push_back((int)tq[b]);
+    p.push_back((int)base[b]);
+  }
+  TORCH_CHECK(M < (int64_t(1) << 24), op, ": too many new rows");
+}
+
+// The plan of attention_extend_ragged (kernels.h) as an int32 CPU tensor, for the device of `like` (default:
+// the current one; its CU count enters the key splits).  Python moves it to the device once per call
+at::Tensor attention_extend_ragged_plan(const std::vector<int64_t>& tq, const std::vector<int64_t>& base, int64_t H,
+                                        const c10::optional<at::Tensor>& like) {
+  std::vector<int> t, p;
+  ragged_lists("attention_extend_ragged_plan", tq, base, int64_t(1) << 30, t, p);
+  TORCH_CHECK(H >= 1 && H <= 4096, "attention_extend_ragged_plan: H");
+  c10::optional<DevGuard> g;
+  if (like.has_value() && like->defined()) { CHECK_DEV(*like); g.emplace(like->device()); }
+  const mg::ExtRaggedShape sh = mg::attention_extend_ragged_shape(t.data(), p.data(), (int)t.size(), (int)H);
+  auto plan = at::empty({(int64_t)sh.plan_ints()}, at::TensorOptions().dtype(at::kInt));
+  mg::attention_extend_ragged_plan(t.data(), p.data(), (int)t.size(), (int)H, plan.data_ptr<int>(), nullptr);
+  return plan;
+}
+
+// S_b, the key splits of every sequence under that plan
+std::vector<int64_t> attention_extend_ragged_splits(const std::vector<int64_t>& tq, const std::vector<int64_t>& base,
+                                                    int64_t H, const c10::optional<at::Tensor>& like) {
+  std::vector<int> t, p;
+  ragged_lists("attention_extend_ragged_splits", tq, base, int64_t(1) << 30, t, p);
+  TORCH_CHECK(H >= 1 && H <= 4096, "attention_extend_ragged_splits: H");
+  c10::optional<DevGuard> g;
+  if (like.has_value() && like->defined()) { CHECK_DEV(*like); g.emplace(like->device()); }
+  std::vector<int> s(t.size());
+  mg::attention_extend_ragged_plan(t.data(), p.data(), (int)t.size(), (int)H, nullptr, s.data());
+  return std::vector<int64_t>(s.begin(), s.end());
+}
+
+// Ragged chunk attention over the KV cache (kernels.h): qkv_new [M, 3D] packed, sequence b's Tq_b rows at
+// positions base_b .. of cache [B, Tmax, 3D]; plan: attention_extend_ragged_plan of the same lists, on the
+// cache's device.  Appends the rows' K/V and returns out [M, D]
+at::Tensor attention_extend_ragged(const at::Tensor& qkv_new, const at::Tensor& cache, int64_t H,
+                                   const std::vector<int64_t>& tq, const std::vector<int64_t>& base,
+                                   const at::Tensor& plan) {
+  const char* op = "attention_extend_ragged";
+  CHECK_BF16(qkv_new); CHECK_BF16(cache); CHECK_CONTIG(qkv_new); CHECK_CONTIG(cache); CHECK_DEV(plan); CHECK_CONTIG(plan);
+  TORCH_CHECK(cache.dim() == 3 && cache.size(2) % 3 == 0, op, ": cache must be [B, Tmax, 3D]");
+  TORCH_CHECK(qkv_new.dim() == 2 && qkv_new.size(1) == cache.size(2), op, ": qkv_new must be [M, 3D]");
+  TORCH_CHECK(qkv_new.device() == cache.device() && plan.device() == cache.device(), op, ": tensors on different devices");
+  const int64_t B = cache.size(0), Tmax = cache.size(1), D = cache.size(2) / 3;
+  TORCH_CHECK(H >= 1 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 128, op, ": head dim must be a multiple of 8, at most 128");
+  TORCH_CHECK((int64_t)tq.size() == B, op, ": ", B, " sequences in the cache, ", tq.size(), " in the lists");
+  std::vector<int> t, p;
+  ragged_lists(op, tq, base, Tmax, t, p);
+  TORCH_CHECK(B * Tmax * 3 * D < (int64_t(1) << 40), op, ": batch too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv_new.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(cache.data_ptr()) % 16 == 0, op, ": tensors must be 16-byte aligned");
+  DevGuard g(cache.device());
+  const mg::ExtRaggedShape sh = mg::attention_extend_ragged_shape(t.data(), p.data(), (int)B, (int)H);
+  TORCH_CHECK(qkv_new.size(0) == sh.M, op, ": qkv_new holds ", qkv_new.size(0), " rows, the lists sum to ", sh.M);
+  TORCH_CHECK(plan.scalar_type() == at::kInt && plan.numel() == (int64_t)sh.plan_ints(), op,
+              ": plan must be the int32 plan of these lists (", sh.plan_ints(), " ints)");
+  TORCH_CHECK((int64_t)sh.items * H < (int64_t(1) << 31) && (int64_t)sh.combs * H < (int64_t(1) << 31), op, ": batch too large");
+  auto out = at::empty({(int64_t)sh.M, D}, cache.options());
+  const int64_t np = (int64_t)sh.part_floats((int)H, (int)(D / H));
+  at::Tensor part;
+  if (np) part = at::empty({np}, cache.options().dtype(at::kFloat));
+  mg::attention_extend_ragged(bp(qkv_new), bp(cache), bp(out), np ? fp(part) : nullptr, plan.data_ptr<int>(), sh, (int)H,
+                              (int)(D / H), Tmax, cur_stream());
+  return out;
+}
+
 // Decode attention for rows that share a prompt (kernels.h): qkv_new [R, 3D], R = B * N rows, N per prompt
 // of pre [B, Tpre, 3D]; own [R, Town, 3D] gets the rows' K/V at row pos - P; pos_dev / plen_dev int32 [1] on
 // the device.  part (optional): the decode state's workspace; without it a temporary one is allocated
@@ -1546,6 +1623,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_extend_splits", [](int64_t B, int64_t Tq, int64_t H, int64_t base) {
     return (int64_t)mg::attention_extend_splits((int)B, (int)Tq, (int)H, (int)base);
   });
+  m.def("attention_extend_ragged", &attention_extend_ragged, py::arg("qkv_new"), py::arg("cache"), py::arg("H"),
+        py::arg("tq"), py::arg("base"), py::arg("plan"));
+  m.def("attention_extend_ragged_plan", &attention_extend_ragged_plan, py::arg("tq"), py::arg("base"), py::arg("H"),
+        py::arg("like") = py::none());
+  m.def("attention_extend_ragged_splits", &attention_extend_ragged_splits, py::arg("tq"), py::arg("base"), py::arg("H"),
+        py::arg("like") = py::none());
   m.def("attention_decode_shared", &attention_decode_shared, py::arg("qkv_new"), py::arg("pre"), py::arg("own"),
         py::arg("H"), py::arg("N"), py::arg("pos_dev"), py::arg("plen_dev"), py::arg("part") = py::none());
   m.def("attention_decode_shared_kv8", &attention_decode_shared_kv8, py::arg("qkv_new"), py::arg("pre_q"),

@@ -300,6 +300,48 @@ size_t attention_extend_part_floats(int B, int Tq, int H, int hd, int base);
 void attention_extend(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, int B, int Tq, int H,
                       int hd, long Tmax, int base, hipStream_t stream);
 
+// attention_extend.hip, ragged -- chunk attention over the KV cache with its own (base_b, Tq_b) per
+// sequence: qkv_new [M, 3D] holds the new rows packed with no padding, M = sum_b Tq_b, sequence b owning
+// rows cu[b] .. cu[b + 1] - 1; row cu[b] + r is the token at position base_b + r of sequence b of cache
+// [B, Tmax, 3D].  Its K and V thirds are stored to that cache row bit for bit (the Q third of a cache row
+// and every other cache byte are untouched), and out [M, D] row cu[b] + r = softmax(q K^T / sqrt(hd)) V
+// over keys 0 .. base_b + r of sequence b.  Tq_b >= 1, base_b >= 0 (0: nothing cached), base_b + Tq_b <=
+// Tmax, hd % 8 == 0, hd <= 128, 16-byte aligned tensors.  Cache rows of sequence b at or past base_b +
+// Tq_b are never read into a result (they may hold NaN).
+// The plan: int32 tables built on the host from the two lists, H and the CU count
+// (attention_extend_ragged_plan), uploaded once per call and handed to every layer's launch.  Layout, in
+// ints (ExtRaggedShape gives the offsets): header [8] {B, M, items, combs, slots, H, 0, 0}; row_seq [M]
+// and row_pos [M], the sequence and the position of packed row m (the append's tables, and the
+// embedding's positions); last [B] = cu[b + 1] - 1; seq [B][8] {cu, base, Tq, S, tps, 0, 0, 0}; items
+// [items][4] {b, query block, split | count << 16, first partial slot}; combs [combs][4] {b, query block,
+// count, first partial slot}.  Sequence b's keys go in S_b splits (1..16) of tps_b whole 64-key tiles, at
+// least two per split, S_b chosen from its own key count base_b + Tq_b and from the number of output
+// blocks (32 queries, one head) of the whole call, so that the launch puts about two workgroups on every
+// CU; an output block has as many splits as its own last query reaches (count <= S_b).  A block with one
+// split is stored to out directly; the others own `count` partial slots of 32 rows x H heads, `slots` in
+// all, with no padding to a maximum: part holds slots * H * 32 * (hd + 2) floats (may be null when slots
+// is 0).  Three stream-ordered launches: the append, the attention launch -- a 1-D grid of items x H
+// workgroups, which reads the cache and writes no cache byte -- and the combine over the blocks with more
+// than one split, in split order.  Nothing in a launch waits on another workgroup.  With equal lists a
+// row's bits depend on its own sequence's data only.  The kernels check every table entry against B, M,
+// Tmax and slots: a plan of other lists computes nothing rather than touch memory outside the tensors.
+struct ExtRaggedShape {
+  int B, M, items, combs, slots;
+  size_t row_seq() const { return 8; }
+  size_t row_pos() const { return row_seq() + M; }
+  size_t last() const { return row_pos() + M; }
+  size_t seq() const { return last() + B; }
+  size_t item() const { return seq() + 8 * (size_t)B; }
+  size_t comb() const { return item() + 4 * (size_t)items; }
+  size_t plan_ints() const { return comb() + 4 * (size_t)combs; }
+  size_t part_floats(int H, int hd) const { return (size_t)slots * H * 32 * (hd + 2); }
+};
+ExtRaggedShape attention_extend_ragged_shape(const int* tq, const int* base, int B, int H);
+// plan: plan_ints() ints, or null; splits: S_b per sequence [B], or null
+void attention_extend_ragged_plan(const int* tq, const int* base, int B, int H, int* plan, int* splits);
+void attention_extend_ragged(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, const int* plan,
+                             const ExtRaggedShape& shape, int H, int hd, long Tmax, hipStream_t stream);
+
 // attention_shared.hip -- decode attention for rows that share a prompt: R = B * N rows, row m belongs
 // to prompt b = m / N.  P = *plen_dev (clamped to [1, Tpre]) is the shared prefix length, pos = *pos_dev
 // the position of the step's token.  Row m attends with its own query (qkv_new [R, 3D] row m) to keys

@@ -65,6 +65,25 @@
 //    one copy above, and the key split is the same function, so out equals attention_extend on the
 //    snapped chunk over the dequantized cache bit for bit.  Image columns at or past hd are covered by
 //    no load: both buffers are zeroed once before the first tile when hd < 32 NO.
+//
+// Ragged (attention_extend_ragged; the contract and the plan tables: kernels.h): every sequence has its
+// own (base_b, Tq_b), the new rows are packed, and the shape that matters is a chat turn -- 5 to 50 new
+// rows behind hundreds of cached ones, another amount of each per sequence (generate_batch(reuse_cache=
+// True), `_GpuCache.extend_ragged`).  attn_extend_kernel's workgroup is 128 queries of one (b, h), a wave
+// per 32: three of its four waves would only stage tiles there, and its grid and split count know one
+// (base, Tq).  So the same three launches, but
+//  * a flat work list: a 1-D grid over items (sequence, 32-query block, key split) x heads from a plan the
+//    host builds once per call; no workgroup exists for padding, and a sequence's split count S_b comes
+//    from its own key count, so a long history beside short ones is split and they are not.  An output
+//    block owns as many partial slots as it has splits (no max-S padding); one with a single split stores
+//    `out` directly and takes no part in the combine, which walks each block's own count in split order.
+//  * the four waves split the KEYS: all hold the same 32 queries (Q fragments in VGPRs) and wave w runs
+//    tiles t0 + w, t0 + w + 4, ... of the item's key range through ext_tile, staging its own tiles into
+//    its own K / V image (LDS: 4 waves x 2 images, 128 KiB at hd = 128), masked body only from the tile
+//    that reaches past the block's first query.  The four (m, l, O) states are folded through LDS in wave
+//    order (attention_shared.hip's arrangement on a causal chunk), so with 1 to 32 queries per block every
+//    wave issues MFMAs.  A row below a wave's first key has weight zero in the fold.
+//  * the append reads the per-row (sequence, position) tables the packed embedding needs anyway.
 #include "attn_common.h"
 #include "kernels.h"
 #include "kv8_common.h"
@@ -495,6 +514,298 @@ __global__ __launch_bounds__(256) void attn_extend_combine_kernel(const ExtArgs 
   *reinterpret_cast<uint2*>(orow) = make_uint2(pack2(acc.x * inv, acc.y * inv), pack2(acc.z * inv, acc.w * inv));
 }
 
+// ------------------------------------------------------------------------------- ragged (file header)
+struct RagArgs {
+  const bf16_t* qkv_new;  // [M, 3D] packed rows
+  const bf16_t* cache;    // [B, Tmax, 3D], every sequence's new rows already appended
+  bf16_t* out;            // [M, D]
+  float* part_ml;         // [slots * H][32][2] {m, l}
+  float* part_o;          // [slots * H][32][hd]
+  const int* seq;         // plan tables (kernels.h): [B][8], [items][4], [combs][4]
+  const int* items;
+  const int* combs;
+  int B, M, H, hd, D, slots;
+  long Tmax;
+  float scale_log2;
+};
+
+// One sequence's row of the plan, checked against the tensors: the plan is the caller's tensor, and a plan
+// of other lists must not send a load or a store outside them (the workgroup then does nothing).
+struct RagSeq {
+  int cu, base, Tq, tps;
+  bool ok;
+};
+MG_DEVICE RagSeq rag_seq(const RagArgs& a, int b, int qb, int cnt, int pbase) {
+  RagSeq s{0, 0, 1, 1, false};
+  if ((unsigned)b >= (unsigned)a.B) return s;
+  const int* sq = a.seq + 8 * b;
+  s.cu = sq[0]; s.base = sq[1]; s.Tq = sq[2]; s.tps = sq[4];
+  s.ok = s.cu >= 0 && s.base >= 0 && s.Tq >= 1 && (long)s.cu + s.Tq <= a.M && (long)s.base + s.Tq <= a.Tmax &&
+         qb >= 0 && (long)qb * 32 < s.Tq && s.tps >= 1 && cnt >= 1 && cnt <= kExtSplitsMax &&
+         (cnt == 1 || (pbase >= 0 && (long)pbase + cnt <= a.slots));
+  return s;
+}
+
+// K and V thirds of packed row m -> cache row row_pos[m] of sequence row_seq[m], 16 bytes a thread
+__global__ __launch_bounds__(256) void attn_extend_ragged_append_kernel(const bf16_t* __restrict__ qkv_new,
+                                                                        bf16_t* __restrict__ cache,
+                                                                        const int* __restrict__ row_seq,
+                                                                        const int* __restrict__ row_pos, int M, int B,
+                                                                        int D, long Tmax) {
+  const int cpr = D >> 2;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)M * cpr) return;
+  const long m = i / cpr;
+  const int c = (int)(i % cpr);
+  const int b = row_seq[m], p = row_pos[m];
+  if ((unsigned)b >= (unsigned)B || p < 0 || p >= Tmax) return;
+  const long ld = 3L * D;
+  st16(cache + ((long)b * Tmax + p) * ld + D + 8 * c, ld16(qkv_new + m * ld + D + 8 * c));
+}
+
+// One item (sequence, 32-query block, key split) of the plan and one head: the four waves hold the same
+// 32 queries and take the split's 64-key tiles t0 + w, t0 + w + 4, ..., each wave staging its own tiles
+// into its own K / V image; the four states are folded through LDS in wave order and wave 0 stores `out`
+// (one split) or the split's partial.  PF: how much of the wave's next tile waits in registers under the
+// current one's MFMAs -- 2: K and V, 1: K (V is loaded once the image is free), 0: nothing -- the most each
+// instantiation holds without scratch (launch_ragged's callers).
+template <int NKS, int PF>
+__global__ __launch_bounds__(256, NKS > 4 ? 1 : 2) void attn_extend_ragged_kernel(const RagArgs a) {
+  constexpr int NH = (NKS + 3) / 4;   // 64-column halves of the LDS images
+  constexpr int NO = (NKS + 1) / 2;   // 32-column O^T accumulator tiles
+  constexpr int HALF = 64 * ROWB;     // one 64-row, 64-column image
+  constexpr int TILE = NH * HALF;     // one K or V tile
+  constexpr int NC = 8 * NH;          // 16-byte chunks per lane per tile per matrix (a wave stages its own tile)
+  constexpr int FOLD_O = NO * 8 * 32 * 16;  // one wave's O for the fold: [NO * 8 float4 columns][32 queries]
+  static_assert(3 * (FOLD_O + 32 * 8) <= 8 * TILE, "the fold reuses the tile regions");
+  __shared__ __attribute__((aligned(16))) char smem[8 * TILE];  // per wave: K, V
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int h32 = lane >> 5, l32 = lane & 31;
+  const int item = blockIdx.x / a.H, hh = blockIdx.x % a.H;
+  const int* it = a.items + 4 * item;
+  const int b = it[0], qb = it[1], sp = it[2] & 0xffff, cnt = it[2] >> 16, pbase = it[3];
+  const RagSeq sq = rag_seq(a, b, qb, cnt, pbase);
+  if (!sq.ok || sp >= cnt) return;  // uniform: before any barrier
+  const int base = sq.base, Tq = sq.Tq;
+  const long ld = 3L * a.D;
+  const int q0 = qb * 32;
+  const int qend = min(Tq, q0 + 32);            // the block's queries are rows [q0, qend) of the sequence
+  const int ntb = (base + qend + 63) / 64;      // key tiles the block's last query sees
+  const int t0 = sp * sq.tps, t1 = min(t0 + sq.tps, ntb);  // this split's tiles [t0, t1)
+
+  // tile staging: chunk c of this lane -> (half, row, 16-byte column chunk), through a per-tile descriptor
+  // that ends at the sequence's row base + Tq (file header); columns at or past hd are staged as zeros
+  // Chunk c = 8 hf + cc of a lane is row (lane >> 3) + 8 cc, 16-byte column chunk lane & 7 of half hf: one
+  // per-lane offset plus a wave-uniform step (added into the VGPR offset: the descriptor's range check
+  // must see it), and the swizzle of row r + 8 cc depends on cc's parity only -- two image offsets
+  const int r0 = lane >> 3, ch = lane & 7;
+  const uint32_t voff = (uint32_t)((r0 * ld + ch * 8) * 2);
+  const uint32_t sd[2] = {(uint32_t)lds_off(r0, ch), (uint32_t)(lds_off(r0 + 8, ch) - 8 * ROWB)};
+  const bool cok[2] = {ch * 8 < a.hd, 64 + ch * 8 < a.hd};
+  const bf16_t* seq = a.cache + (long)b * a.Tmax * ld;
+  const uint64_t seq_bytes = (uint64_t)(base + Tq) * ld * 2;  // rows [0, base + Tq) of this sequence
+  const uint64_t kcol = (uint64_t)(a.D + hh * a.hd) * 2;
+  auto load_mat = [&](uint4 (&r)[NC], int k0, bool vmat) {  // K or V of the tile at key k0
+    const __amdgpu_buffer_rsrc_t d = kv_rsrc(seq, seq_bytes, kcol + (uint64_t)k0 * ld * 2 + (vmat ? (uint64_t)a.D * 2 : 0));
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const uint32_t vo = voff + (uint32_t)(((c & 7) * 8 * ld + (c >> 3) * 64) * 2);
+      const uint4 u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(d, vo, 0, 0));
+      r[c] = cok[c >> 3] ? u : make_uint4(0, 0, 0, 0);
+    }
+  };
+  char* mine = smem + w * 2 * TILE;
+  auto store_mat = [&](const uint4 (&r)[NC], char* img) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) *reinterpret_cast<uint4*>(img + (c >> 3) * HALF + (c & 7) * 8 * ROWB + sd[c & 1]) = r[c];
+  };
+
+  // per-lane fragment offsets, as in attn_extend_kernel
+  int ko[NKS];
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) ko[ks] = (ks >> 2) * HALF + lds_off(l32, (2 * ks + h32) & 7);
+  const int trq = (lane & 15) >> 2, trc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int ta0 = tr_off(4 * h32 + trq, trc), tb0 = tr_off(8 + 4 * h32 + trq, trc);
+  const int ta1 = tr_off(4 * h32 + trq, 32 + trc), tb1 = tr_off(8 + 4 * h32 + trq, 32 + trc);
+
+  // this lane's query: row myr of the sequence's chunk, position base + myr; a lane past Tq holds a zero
+  // query under the last row's limit and stores nothing
+  const int myr = q0 + l32;
+  const bool live = myr < Tq;
+  const int mypos = base + min(myr, Tq - 1);
+  const bf16_t* qrow = a.qkv_new + ((long)sq.cu + min(myr, Tq - 1)) * ld + hh * a.hd;
+  bf16x8 qf[NKS];
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    const int d = ks * 16 + 8 * h32;
+    const uint4 u = (live && d < a.hd) ? ld16(qrow + d) : make_uint4(0, 0, 0, 0);
+    float f[8];
+    unpack8(u, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] *= a.scale_log2;
+    qf[ks] = __builtin_bit_cast(bf16x8, pack8(f));
+  }
+  f32x16 o[NO], negm = f32x16{0};
+#pragma unroll
+  for (int n = 0; n < NO; ++n) o[n] = f32x16{0};
+  float m = 0.f, l = 0.f;
+
+  // the trip count is the same for the four waves: the barriers are uniform
+  const int niter = (t1 - t0 + 3) >> 2;
+  const int tw = t0 + w;  // this wave's first tile
+  {
+    uint4 rk[PF >= 1 ? NC : 1], rv[PF >= 2 ? NC : 1];  // what waits in registers under the MFMAs
+    int t = tw;
+    if (t < t1) {
+      if constexpr (PF >= 1) load_mat(rk, t * 64, false);
+      if constexpr (PF >= 2) load_mat(rv, t * 64, true);
+    }
+    for (int i = 0; i < niter; ++i, t += 4) {
+      const bool have = t < t1;
+      const int k0 = t * 64;
+      if (have) {
+        if constexpr (PF >= 1) {
+          store_mat(rk, mine);
+        } else {
+          uint4 r[NC];
+          load_mat(r, k0, false);
+          store_mat(r, mine);
+        }
+        if constexpr (PF >= 2) {
+          store_mat(rv, mine + TILE);
+        } else {
+          uint4 r[NC];
+          load_mat(r, k0, true);
+          store_mat(r, mine + TILE);
+        }
+      }
+      __syncthreads();
+      if (t + 4 < t1) {
+        if constexpr (PF >= 1) load_mat(rk, k0 + 256, false);
+        if constexpr (PF >= 2) load_mat(rv, k0 + 256, true);
+      }
+      if (have) {
+        const int lim = mypos - k0 - 4 * h32;
+        // the causal mask only on the tiles that reach past the block's first query (separate bodies)
+        if (k0 + 63 > base + q0) ext_tile<NKS, true>(mine, mine + TILE, ko, qf, o, negm, m, l, i == 0, lim, ta0, tb0, ta1, tb1);
+        else ext_tile<NKS, false>(mine, mine + TILE, ko, qf, o, negm, m, l, i == 0, lim, ta0, tb0, ta1, tb1);
+      }
+      __syncthreads();
+    }
+  }
+
+  // A row that saw no key of this wave's tiles (no tile, or its position lies below the first one's first
+  // key: the wave's tiles ascend) has weight zero, whatever the masked bodies left in its registers
+  const bool seen = tw < t1 && mypos >= tw * 64;
+  float lt = sum_xor32(l);
+  if (!seen) {
+    m = kNegBig;
+    lt = 0.f;
+  }
+#pragma unroll
+  for (int n = 0; n < NO; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[n][r] = seen ? o[n][r] : 0.f;
+
+  // fold in wave order: waves 1..3 -> LDS, wave 0 merges 1, 2, 3 into its own state
+  float4* fo = reinterpret_cast<float4*>(smem);
+  float2* fml = reinterpret_cast<float2*>(smem + 3 * FOLD_O);
+  if (w > 0) {
+#pragma unroll
+    for (int n = 0; n < NO; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        fo[((w - 1) * NO * 8 + n * 8 + 2 * g + h32) * 32 + l32] =
+            make_float4(o[n][4 * g], o[n][4 * g + 1], o[n][4 * g + 2], o[n][4 * g + 3]);
+    if (h32 == 0) fml[(w - 1) * 32 + l32] = make_float2(m, lt);
+  }
+  __syncthreads();
+  if (w != 0 || !live) return;
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const float2 ml = fml[u * 32 + l32];
+    const float Mx = fmaxf(m, ml.x);
+    const float ca = fexp2(m - Mx), cb = fexp2(ml.x - Mx);
+    lt = ca * lt + cb * ml.y;
+    m = Mx;
+#pragma unroll
+    for (int n = 0; n < NO; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 v = fo[(u * NO * 8 + n * 8 + 2 * g + h32) * 32 + l32];
+        o[n][4 * g] = ca * o[n][4 * g] + cb * v.x;
+        o[n][4 * g + 1] = ca * o[n][4 * g + 1] + cb * v.y;
+        o[n][4 * g + 2] = ca * o[n][4 * g + 2] + cb * v.z;
+        o[n][4 * g + 3] = ca * o[n][4 * g + 3] + cb * v.w;
+      }
+  }
+  if (cnt == 1) {  // the block's whole key range (key 0 is in it: lt > 0): normalise and store
+    const float inv = 1.f / lt;
+    bf16_t* orow = a.out + ((long)sq.cu + myr) * a.D + hh * a.hd;
+#pragma unroll
+    for (int n = 0; n < NO; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d = n * 32 + 8 * g + 4 * h32;
+        if (d < a.hd)
+          *reinterpret_cast<uint2*>(orow + d) = make_uint2(pack2(o[n][4 * g] * inv, o[n][4 * g + 1] * inv),
+                                                           pack2(o[n][4 * g + 2] * inv, o[n][4 * g + 3] * inv));
+      }
+    return;
+  }
+  // this split's state of row myr: {m, l} and the unnormalised O (neutral where the row saw none of it)
+  const long slot = (((long)pbase * a.H + (long)hh * cnt + sp) << 5) + l32;
+  if (h32 == 0) *reinterpret_cast<float2*>(a.part_ml + 2 * slot) = make_float2(m, lt);
+  float* prow = a.part_o + slot * a.hd;
+#pragma unroll
+  for (int n = 0; n < NO; ++n)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d = n * 32 + 8 * g + 4 * h32;
+      if (d < a.hd)
+        *reinterpret_cast<float4*>(prow + d) = make_float4(o[n][4 * g], o[n][4 * g + 1], o[n][4 * g + 2], o[n][4 * g + 3]);
+    }
+}
+
+// The combine of one output block (sequence, 32-query block) with cnt > 1 splits and one head, as
+// attn_extend_combine_kernel: a thread per (row, 4 columns), the block's own count of splits in split
+// order.  Split 0 holds key 0, which every row sees, so M is a real max.
+__global__ __launch_bounds__(256) void attn_extend_ragged_combine_kernel(const RagArgs a) {
+  const int e = blockIdx.x / a.H, hh = blockIdx.x % a.H;
+  const int* cb = a.combs + 4 * e;
+  const int b = cb[0], qb = cb[1], cnt = cb[2], pbase = cb[3];
+  const RagSeq sq = rag_seq(a, b, qb, cnt, pbase);
+  if (!sq.ok || cnt < 2) return;
+  const int q0 = qb * 32, rows = min(sq.Tq - q0, 32), hd4 = a.hd >> 2;
+  const int i = blockIdx.y * 256 + threadIdx.x;
+  if (i >= rows * hd4) return;
+  const int r = i / hd4, d = (i % hd4) * 4;
+  const long slot0 = (((long)pbase * a.H + (long)hh * cnt) << 5) + r;
+  float ms[kExtSplitsMax], M = kNegBig;
+#pragma unroll
+  for (int s = 0; s < kExtSplitsMax; ++s) {
+    ms[s] = s < cnt ? a.part_ml[2 * (slot0 + 32L * s)] : kNegBig;
+    M = fmaxf(M, ms[s]);
+  }
+  float L = 0.f;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int s = 0; s < kExtSplitsMax; ++s) {
+    if (s < cnt) {
+      const float wgt = fexp2(ms[s] - M);
+      const float4 v = *reinterpret_cast<const float4*>(a.part_o + (slot0 + 32L * s) * a.hd + d);
+      L += wgt * a.part_ml[2 * (slot0 + 32L * s) + 1];
+      acc.x += wgt * v.x;
+      acc.y += wgt * v.y;
+      acc.z += wgt * v.z;
+      acc.w += wgt * v.w;
+    }
+  }
+  const float inv = 1.f / L;
+  bf16_t* orow = a.out + ((long)sq.cu + q0 + r) * a.D + hh * a.hd + d;
+  *reinterpret_cast<uint2*>(orow) = make_uint2(pack2(acc.x * inv, acc.y * inv), pack2(acc.z * inv, acc.w * inv));
+}
+
 int ext_cu_count() {
   static int ncu[64] = {0};
   int dev = 0;
@@ -553,6 +864,40 @@ ExtArgs ext_plan(const bf16_t* qkv_new, bf16_t* out, float* part, int B, int Tq,
   return a;
 }
 
+template <int NKS, int PF>
+void launch_ragged(const RagArgs& a, int items, hipStream_t stream) {
+  attn_extend_ragged_kernel<NKS, PF><<<items * a.H, 256, 0, stream>>>(a);
+}
+
+// Sequence b's key split of the ragged plan: enough splits to put two workgroups on every CU were every
+// output block (32 queries, one head) split alike, capped by the sequence's own tiles -- at least two
+// 64-key tiles per split, as ext_tiles_per_split reasons -- and by kExtSplitsMax.  A long history beside
+// short ones is split; the short ones are not.
+int rag_tiles_per_split(int tq, int base, long blocks) {
+  const int nt = cdiv(base + tq, 64);
+  long S = 2L * ext_cu_count() / std::max<long>(blocks, 1);
+  S = std::min<long>(S, std::min(kExtSplitsMax, nt / 2));
+  return cdiv(nt, std::max<long>(S, 1));
+}
+
+// walks the plan in table order: f(b, qb, cnt, pbase) per output block (pbase: the first partial slot
+// of a block with cnt > 1 splits)
+template <class F>
+void rag_walk(const int* tq, const int* base, int B, int H, F f) {
+  long blocks = 0;
+  for (int b = 0; b < B; ++b) blocks += (long)cdiv(tq[b], 32) * H;
+  int pbase = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tps = rag_tiles_per_split(tq[b], base[b], blocks);
+    for (int qb = 0; qb * 32 < tq[b]; ++qb) {
+      const int ntb = cdiv(base[b] + std::min(tq[b], qb * 32 + 32), 64);
+      const int cnt = cdiv(ntb, tps);
+      f(b, qb, cnt, tps, pbase);
+      if (cnt > 1) pbase += cnt;
+    }
+  }
+}
+
 }  // namespace
 
 namespace mg {
@@ -583,6 +928,84 @@ void attention_extend_kv8(const bf16_t* qkv_new, int8_t* kq, float* ks, bf16_t* 
   attn_extend_snap_kernel<<<cdiv(NV, 256 / (hd >> 3)), 256, 0, stream>>>(qkv_new, kq, ks, NV, Tq, H, hd, Tmax, base);
   if (hd % 16 == 0) launch_attend<16>(a, stream);
   else launch_attend<8>(a, stream);
+}
+
+ExtRaggedShape attention_extend_ragged_shape(const int* tq, const int* base, int B, int H) {
+  ExtRaggedShape sh{B, 0, 0, 0, 0};
+  for (int b = 0; b < B; ++b) sh.M += tq[b];
+  rag_walk(tq, base, B, H, [&](int, int, int cnt, int, int) {
+    sh.items += cnt;
+    if (cnt > 1) {
+      sh.combs += 1;
+      sh.slots += cnt;
+    }
+  });
+  return sh;
+}
+
+void attention_extend_ragged_plan(const int* tq, const int* base, int B, int H, int* plan, int* splits) {
+  const ExtRaggedShape sh = attention_extend_ragged_shape(tq, base, B, H);
+  if (plan) {
+    const int hdr[8] = {sh.B, sh.M, sh.items, sh.combs, sh.slots, H, 0, 0};
+    std::copy(hdr, hdr + 8, plan);
+    int* row_seq = plan + sh.row_seq();
+    int* row_pos = plan + sh.row_pos();
+    int* last = plan + sh.last();
+    int* seq = plan + sh.seq();
+    for (int b = 0, m = 0; b < B; ++b) {
+      seq[8 * b] = m;
+      seq[8 * b + 1] = base[b];
+      seq[8 * b + 2] = tq[b];
+      for (int r = 0; r < tq[b]; ++r, ++m) {
+        row_seq[m] = b;
+        row_pos[m] = base[b] + r;
+      }
+      last[b] = m - 1;
+      for (int j = 5; j < 8; ++j) seq[8 * b + j] = 0;
+    }
+    int* item = plan + sh.item();
+    int* comb = plan + sh.comb();
+    rag_walk(tq, base, B, H, [&](int b, int qb, int cnt, int tps, int pbase) {
+      seq[8 * b + 4] = tps;
+      for (int s = 0; s < cnt; ++s, item += 4) {
+        item[0] = b; item[1] = qb; item[2] = s | (cnt << 16); item[3] = pbase;
+      }
+      if (cnt > 1) {
+        comb[0] = b; comb[1] = qb; comb[2] = cnt; comb[3] = pbase;
+        comb += 4;
+      }
+    });
+    for (int b = 0; b < B; ++b) seq[8 * b + 3] = cdiv(cdiv(base[b] + tq[b], 64), seq[8 * b + 4]);
+  }
+  if (splits) {
+    long blocks = 0;
+    for (int b = 0; b < B; ++b) blocks += (long)cdiv(tq[b], 32) * H;
+    for (int b = 0; b < B; ++b)
+      splits[b] = cdiv(cdiv(base[b] + tq[b], 64), rag_tiles_per_split(tq[b], base[b], blocks));
+  }
+}
+
+void attention_extend_ragged(const bf16_t* qkv_new, bf16_t* cache, bf16_t* out, float* part, const int* plan,
+                             const ExtRaggedShape& sh, int H, int hd, long Tmax, hipStream_t stream) {
+  RagArgs a{};
+  a.qkv_new = qkv_new; a.cache = cache; a.out = out;
+  a.part_ml = part;
+  a.part_o = part ? part + (size_t)sh.slots * H * 32 * 2 : nullptr;
+  a.seq = plan + sh.seq(); a.items = plan + sh.item(); a.combs = plan + sh.comb();
+  a.B = sh.B; a.M = sh.M; a.H = H; a.hd = hd; a.D = H * hd; a.slots = part ? sh.slots : 0; a.Tmax = Tmax;
+  a.scale_log2 = 1.4426950408889634f / sqrtf((float)hd);
+  attn_extend_ragged_append_kernel<<<cdiv((long)sh.M * (a.D >> 2), 256), 256, 0, stream>>>(
+      qkv_new, cache, plan + sh.row_seq(), plan + sh.row_pos(), sh.M, sh.B, a.D, Tmax);
+  switch (nks_for(hd)) {
+    case 1: launch_ragged<1, 2>(a, sh.items, stream); break;
+    case 2: launch_ragged<2, 2>(a, sh.items, stream); break;
+    case 3: launch_ragged<3, 0>(a, sh.items, stream); break;
+    case 4: launch_ragged<4, 1>(a, sh.items, stream); break;
+    case 6: launch_ragged<6, 2>(a, sh.items, stream); break;
+    default: launch_ragged<8, 1>(a, sh.items, stream); break;
+  }
+  if (sh.combs > 0 && part)
+    attn_extend_ragged_combine_kernel<<<dim3(sh.combs * H, cdiv(32 * (hd >> 2), 256)), 256, 0, stream>>>(a);
 }
 
 }  // namespace mg

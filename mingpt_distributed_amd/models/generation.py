@@ -447,8 +447,13 @@ class _GpuCache(_Body):
         # prefix reuse (``_state_for(reuse=True)``): the tokens whose K/V rows the caches hold (bf16 or
         # int8), by row, in ``held[:, :nheld]`` (recorded after a reuse-enabled ``generate``; any prefill
         # clears it), and how many of them the last prefill of this state kept (``reused``; 0: a full one)
+        # ``hlen`` (``generate_batch(reuse_cache=True)``): the record's valid length by row, a host list, when
+        # the rows differ -- row b's cache then holds ``held[b, :hlen[b]]`` and ``nheld == min(hlen)``, so
+        # ``generate`` reads a ragged record correctly; None: every row holds ``nheld`` tokens.  ``reused``
+        # after a ragged extension is the per-row list
         self.held = torch.zeros(B, tmax, dtype=torch.long, device=self.dev) if rows is None else None
         self.nheld = self.reused = 0
+        self.hlen = None
         if rows is None:
             self.prefill(idx, last)
 
@@ -511,6 +516,7 @@ class _GpuCache(_Body):
         cfg = self.model.config
         B = idx.size(0)
         self.nheld = self.reused = 0
+        self.hlen = None
         if self.kv8:
             self._kv8_storage()
         x = self._prompt(idx, self._keep)
@@ -561,10 +567,55 @@ class _GpuCache(_Body):
 
     def hold(self, tokens):
         """Record that the caches hold the K/V rows of ``tokens`` [B, n] (None: of nothing known)."""
-        self.nheld = 0
+        self.nheld, self.hlen = 0, None
         if tokens is not None and self.held is not None and tokens.size(1) <= self.tmax:
             self.nheld = tokens.size(1)
             self.held[:, :self.nheld].copy_(tokens)
+
+    def hold_rows(self, tokens, lens):
+        """Record that row b's cache holds the K/V rows of ``tokens[b, :lens[b]]`` (tokens [B, n] on the device,
+        ``lens`` a host list): the ragged record, ``nheld`` its minimum."""
+        self.nheld, self.hlen = 0, None
+        n = min(max(lens), tokens.size(1), self.tmax)
+        if self.held is not None and n >= 1:
+            self.held[:, :n].copy_(tokens[:, :n])
+            self.hlen = [min(int(v), n) for v in lens]
+            self.nheld = min(self.hlen)
+
+    def common_prefix_rows(self, idx, lengths):
+        """By row, how many leading tokens of ``idx[b, :lengths[b]]`` the record holds (``lengths`` a host
+        list), capped at lengths[b] - 1 -- one row at least has to run for the logits: one device reduction,
+        one read."""
+        hl = self.hlen if self.hlen is not None else [self.nheld] * self.B
+        n = min(max(hl), idx.size(1))
+        if n <= 0:
+            return [0] * self.B
+        same = (idx[:, :n] == self.held[:, :n]).long().cumprod(1).sum(1).tolist()
+        return [max(min(s, h, L - 1), 0) for s, h, L in zip(same, hl, lengths)]
+
+    def extend_ragged(self, idx, lengths, P):
+        """Prefill on top of what the caches hold, by row: of the right-padded batch ``idx`` [B, Lmax] with
+        ``lengths`` (a host list) run only row b's tokens P[b] .. lengths[b] - 1, packed into M = sum(lengths[b] -
+        P[b]) rows, behind the P[b] cached rows of that sequence.  One plan (``attention_extend_ragged_plan``:
+        the rows' sequences and positions, the last row of each sequence and the attention's work list) goes
+        to the device once and serves the token gather, the embedding's positions, every layer's
+        ``attention_extend_ragged`` and the gather of each sequence's last row; the blocks run on the route
+        of M rows and the LM head on the route of B rows, and ``logits`` [B, V] land where ``prefill`` leaves
+        them for a right-padded batch (row b's at its own last token)."""
+        C, bf = self.C, self.bf
+        tr, cfg = self.model.transformer, self.model.config
+        B, D, H = idx.size(0), cfg.n_embed, cfg.n_head
+        tq = [int(L) - int(p) for L, p in zip(lengths, P)]
+        M = sum(tq)
+        self.nheld, self.hlen = 0, None  # the rows past P[b] are overwritten: the caller records the new ones
+        plan = C.attention_extend_ragged_plan(tq, list(P), H, self.caches[0]).to(self.dev)
+        row_seq, row_pos, last = plan[8:8 + M], plan[8 + M:8 + 2 * M], plan[8 + 2 * M:8 + 2 * M + B]
+        tok = idx[row_seq.long(), row_pos.long()].view(M, 1)
+        x = C.embedding_fwd(tok, bf(tr.wte.weight), bf(tr.wpe.weight), 0.0, 0, row_pos, None, None, 1).view(M, D)
+        attend = lambda i, qkv: C.attention_extend_ragged(qkv, self.caches[i], H, tq, list(P), plan)
+        x = self._blocks(x, attend, self._route(M))
+        self.logits = self._head(x.index_select(0, last), self._route(B))[:, :cfg.vocab_size]
+        return self.logits
 
     def _decode(self, tok, pos, hpos, pos_stride=0, am_part=None, seq=None):
         """One decode step, with nothing from the host: embed token ``tok`` [B, 1] (int64, on the
@@ -1270,7 +1321,28 @@ def _reuse_kv8_pays(B, P, Tq):
     return not _REUSE_KV8_GATE or B * Tq <= 64 or B * P >= 2048
 
 
-def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
+# ``generate_batch(reuse_cache=True)``: the same kind of switch for the ragged extension (PERF.md 'Prefix
+# reuse, ragged').  False takes every common prefix (tests of the path, A/B)
+_REUSE_BATCH_GATE = True
+
+
+def _reuse_batch_pays(P, Tq):
+    """The measured rule for per-row kept prefixes ``P`` and new rows ``Tq`` (host lists; PERF.md 'Prefix reuse,
+    ragged', 36 cases on GPT-2 124M and gpt2-xl at B = 2 and 8): the M = sum(Tq) packed rows fit the skinny or the
+    rows GEMM (M <= 64: all 18 measured cases are faster, 1.31x to 4.94x, those that keep one token per row
+    included -- the padded prefill streams every weight on the MFMA GEMM for them), or the extension runs at least
+    4096 rows fewer than the padded prefill's B * Lmax (measured at 7200: 1.54x to 2.96x).  Slower outside it: one
+    kept token per row with M of 160 to 800 (0.86x to 0.95x).  Also outside it, on the safe side: M = 200 with
+    1800 rows fewer (1.01x and 1.02x, inside the ranges, on GPT-2 124M; 1.31x on gpt2-xl).  Not measured: M > 64
+    with between 1800 and 7200 rows fewer -- the bound sits at 4096, where the uniform extension's table has its
+    nearest measured win; B other than 2 and 8; histories past 900 tokens."""
+    if not _REUSE_BATCH_GATE:
+        return True
+    M, rows = sum(Tq), len(P) * max(p + t for p, t in zip(P, Tq))
+    return M <= 64 or rows - M >= 4096
+
+
+def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False, ragged=None):
     """The decode state the model keeps under ``slot`` -- ``_mg_decode_cache``, beside it ``_mg_beam_cache`` /
     ``_mg_spec_cache`` of ``rows`` decode rows, so that beam and speculative calls leave the plain loops
     and their graphs alone, and the KV8 state of each (``_kv_slot``) -- or a new one when the device,
@@ -1284,17 +1356,31 @@ def _state_for(model, slot, idx, tmax, rows=None, last=None, reuse=False):
     shares a prefix of P tokens with ``idx`` in every row -- P capped at T - 1: one row at least has to run
     for the logits -- only ``idx[:, P:]`` is run, on top of the cached rows (``_GpuCache.extend``), where
     that measured faster (``_reuse_pays``; a KV8 state: ``_reuse_kv8_pays``); else the prefill as ever.  ``reused`` on the state is P, 0 after a full
-    prefill."""
+    prefill.
+
+    ``ragged`` (a bf16 state; ``generate_batch(reuse_cache=True)``): the host list of the rows' lengths of the
+    right-padded ``idx``.  Under the same conditions row b keeps its own prefix of P_b tokens of its own record
+    (``common_prefix_rows``) and only the tokens behind it are run (``_GpuCache.extend_ragged``), when some
+    P_b >= 1 and ``_reuse_batch_pays`` says so; ``reused`` is then the list of the P_b."""
     c = model.__dict__.get(slot)
     if c is None or c.B != (rows or idx.size(0)) or c.tmax != tmax or c.dev != idx.device:
         c = model.__dict__[slot] = _GpuCache(model, idx, tmax, last, rows, kv8=slot in _KV8_SLOTS.values())
+    elif rows is None and ragged is not None:
+        P = None
+        if c.held is not None and (c.hlen is not None or c.nheld > 0) and c._stamp() == c.stamp:
+            P = c.common_prefix_rows(idx, ragged)
+        if P is not None and max(P) >= 1 and _reuse_batch_pays(P, [L - p for L, p in zip(ragged, P)]):
+            c.extend_ragged(idx, ragged, P)
+            c.reused = P
+        else:
+            c.prefill(idx, last)
     elif rows is None:
         P = 0
         if reuse and last is None and c.held is not None and c.nheld > 0 and c._stamp() == c.stamp:
             P = min(c.common_prefix(idx), idx.size(1) - 1)
         if P >= 1 and (_reuse_kv8_pays if c.kv8 else _reuse_pays)(idx.size(0), P, idx.size(1) - P):
             c.extend(idx[:, P:], P)
-            c.nheld, c.reused = 0, P  # the rows past P are overwritten: the caller records the new ones
+            c.nheld, c.hlen, c.reused = 0, None, P  # the rows past P are overwritten: the caller records the new ones
         else:
             c.prefill(idx, last)
     return c
@@ -1644,7 +1730,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
                    top_k: Optional[int] = None, seed: Optional[int] = None, eos_token: Optional[int] = None,
                    pad_token: int = 0, top_p: Optional[float] = None, return_logprobs: bool = False,
                    repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                   no_repeat_ngram_size: int = 0, kv_cache: str = "bf16"):
+                   no_repeat_ngram_size: int = 0, kv_cache: str = "bf16", reuse_cache: bool = False):
     """Decode a batch of prompts of different lengths in one go; returns ``(tokens, lengths)``, or
     with ``return_logprobs`` ``(tokens, lengths, logprobs)``: float32 of ``tokens``' shape, entry
     [b, j] the model's log-probability of ``tokens[b, j]`` given ``tokens[b, :j]`` at every generated
@@ -1672,10 +1758,22 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
     ``kv_cache``: ``"bf16"`` or ``"int8"``, the KV8 model and the int8 cache of ``generate``.
 
+    ``reuse_cache``: ragged prefix reuse on the GPU, for a batch of conversations that each grew by a turn.  The
+    decode state records, by row, the tokens whose K/V rows its caches hold after a call with the argument; the
+    next such call with the same number of rows keeps row b's longest prefix of its own record (at most its
+    length - 1) and runs only the tokens behind it, packed with no padding, each layer attending with
+    ``attention_extend_ragged`` (``_GpuCache.extend_ragged``) -- where ``_reuse_batch_pays`` allows it, else the
+    padded prefill as ever.  The decode loop is the same either way.  ``generate(reuse_cache=True)`` and this
+    share one record.  bf16 state only: with ``kv_cache="int8"`` it is a ValueError.  A call without the argument
+    clears the record.  On the CPU it is ignored, as ``generate`` ignores it there.
+
     On the GPU the right-padded batch is prefilled once and the token loop is one captured step
     replayed back to back (``_GpuCache.ragged``): per-row positions and finished flags live in
     device memory.  On the CPU each row runs through the cache path on its own."""
     slot, kv8 = _kv_slot("generate_batch", kv_cache)
+    if kv8 and reuse_cache:
+        raise ValueError("generate_batch: reuse_cache=True with kv_cache='int8' is not there yet (the ragged "
+                         "extension runs on the bf16 state only)")
     rows, device = _ragged_prompts(prompts)
     V = model.config.vocab_size
     lens = [r.numel() for r in rows]
@@ -1699,7 +1797,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     if device.type == "cuda":
         return _generate_batch_gpu(model, tokens[:, :Lmax].contiguous(), lengths, max_new_tokens, temperature,
                                    do_sample, top_k, seed, eos_token, int(pad_token), top_p, return_logprobs, pwords,
-                                   slot)
+                                   slot, lens if reuse_cache else None)
     for b, r in enumerate(rows):  # the executable definition of the semantics
         cache = _CpuCache(model, r.view(1, -1), kv8)
         logits, n = cache.logits, lens[b]
@@ -1723,7 +1821,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
 
 def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sample, top_k, seed, eos_token,
-                        pad_token, top_p=None, logprobs=False, proc=None, slot="_mg_decode_cache"):
+                        pad_token, top_p=None, logprobs=False, proc=None, slot="_mg_decode_cache", reuse=None):
     """The GPU half of ``generate_batch``: prefill the right-padded batch ``idx`` [B, Lmax] once --
     causal attention makes every position before a row's length exact -- take row b's logits at
     column lengths[b] - 1, pick the first token with the loop's own pick kernel, then replay the
@@ -1731,9 +1829,12 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     ``_EXIT_EVERY`` replays; stopping early changes nothing, since a step leaves finished rows as
     they are.  ``logprobs``: the loops with the lse kernel, and the state's ``lp`` buffer (zero but
     at the generated positions) as a third result.  ``proc`` (``_proc_words``): the loops with the
-    process kernel in front of the pick, the first pick included.  ``slot``: the decode state's."""
+    process kernel in front of the pick, the first pick included.  ``slot``: the decode state's.  ``reuse``
+    (``reuse_cache``): the rows' lengths as a host list -- the prefill may then be the ragged extension
+    (``_state_for``), and the rows the caches hold afterwards are recorded: row b's tokens but its last one,
+    which was picked and not fed (a finished row keeps rewriting its last cache row: not counted either)."""
     B, Lmax = idx.shape
-    cache = _state_for(model, slot, idx, model.block_size, last=lengths - 1)
+    cache = _state_for(model, slot, idx, model.block_size, last=lengths - 1, ragged=reuse)
     words = _ragged_words(seed, temperature, top_k, eos_token, top_p)
     greedy = not do_sample
     st = cache.ragged_start(idx, lengths, words, greedy, logprobs=logprobs, proc=proc)
@@ -1743,6 +1844,8 @@ def _generate_batch_gpu(model, idx, lengths, max_new_tokens, temperature, do_sam
     W = Lmax + max_new_tokens
     cols = torch.arange(W, device=idx.device).view(1, W)
     tokens = torch.where(cols < out_len.view(B, 1), st["seq"][:, :W], torch.full_like(cols, pad_token))
+    if reuse is not None:
+        cache.hold_rows(st["seq"], (out_len - 1).tolist())
     if logprobs:
         return tokens, out_len, st["lp"][:, :W].clone()
     return tokens, out_len

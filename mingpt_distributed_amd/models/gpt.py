@@ -253,20 +253,23 @@ class GPT(nn.Module):
                        eos_token: Optional[int] = None, pad_token: int = 0, top_p: Optional[float] = None,
                        return_logprobs: bool = False, repetition_penalty: float = 1.0,
                        presence_penalty: float = 0.0, frequency_penalty: float = 0.0, no_repeat_ngram_size: int = 0,
-                       kv_cache: str = "bf16"):
+                       kv_cache: str = "bf16", reuse_cache: bool = False):
         """Decode prompts of different lengths in one batch, each row stopping at ``eos_token`` or
         after ``max_new_tokens``; returns ``(tokens, lengths)`` (``generation.generate_batch``).  No
         sliding window: the longest prompt plus ``max_new_tokens`` must fit ``block_size``.
         ``return_logprobs``: returns ``(tokens, lengths, logprobs)``.  The logits processors
         (``repetition_penalty`` ...) are those of ``generate``, per row over its own sequence, and so
-        is ``kv_cache``."""
+        is ``kv_cache``.  ``reuse_cache=True``: on the GPU each row keeps the prefix of its prompt that its own
+        KV cache rows still hold from the last such call and runs only the tokens behind it
+        (``attention_extend_ragged``; bf16 cache only)."""
         from .generation import generate_batch
 
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, do_sample=do_sample,
                               top_k=top_k, seed=seed, eos_token=eos_token, pad_token=pad_token, top_p=top_p,
                               return_logprobs=return_logprobs, repetition_penalty=repetition_penalty,
                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
-                              no_repeat_ngram_size=no_repeat_ngram_size, kv_cache=kv_cache)
+                              no_repeat_ngram_size=no_repeat_ngram_size, kv_cache=kv_cache,
+                              reuse_cache=reuse_cache)
 
     @torch.no_grad()
     def generate_beam(self, idx, max_new_tokens: int, num_beams: int, eos_token: Optional[int] = None,
